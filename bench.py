@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: volume-pairs/sec, forward+backward(+Adam), 256^3, 512 keypoints, TPS lambda=0.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS
 one of the N ranks; started plainly (`python bench.py --gpus N`, WORLD_SIZE unset) it starts the N ranks itself (self_launch)
@@ -12,8 +12,17 @@ One "step" = one training step of scripts/train.py:102-176 restated on this pack
 backward -> gradient all-reduce (RCCL, N > 1) -> Adam, on synthetic pairs that are resident in HBM before
 the timed region starts.  Weak scaling: every rank owns --pairs-per-gpu pairs (default 2 = BASELINE.json
 configs[2] "TPS lambda=0, bs=2 on 1xMI355X" at N=1 and configs[3] "bs=16 across 8 GPUs" at N=8).
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant
-kernel (the 3x3x3 conv, fp32 results from split-bf16 MFMA) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+Prints ONE JSON line on rank 0 with the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`).
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds everything else, after the timed
+steps: `roofline` for the dominant kernel (the 3x3x3 conv, fp32 results from split-bf16 MFMA) and per-kernel times from one
+profiled step, the side legs (Dice, fp32 MFMA, first-block bf16x6, use_amp, eval, groupwise, ConvNet, stand-alone sampler),
+the all-reduce timing and per-rank power / clock, and `cpu_baseline` (the oracle on the host cores, bounded sample).  A side
+leg's option sets its size: 0 by default in a plain run, the value given in its help under --full.
+
+--dump-outputs DIR writes what the last timed step computed, as DIR/<name>.npy (float32, the loss float64; a fixed seeded
+sample of any array above 2^22 values): the loss, the keypoints, the dense grid, the parameters after the optimizer step and
+their gradients.  The inputs (synthetic pairs, initial weights) depend only on the arguments.
 """
 import argparse
 import json
@@ -32,11 +41,22 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 (v_mfma_f32_32x32x16_bf16)
 HBM_PEAK_GBS = 8000.0
 
 
-def parse():
+# side legs and their sizes under --full (a plain run: 0 unless given)
+FULL_DEFAULTS = {"also_f32": 3, "first_block_exact": 3, "amp": 3, "dice": 3, "eval_steps": 3, "groupwise": 8, "convnet": 3,
+                 "sampler": 1, "cpu_256": 1}
+DUMP_MAX_VALUES = 2 ** 22      # per array: 16.8 MB in float32; the dumped set stays below 64 MB
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline and per-kernel figures, every side leg, the all-reduce timing, per-rank "
+                         "power / clock and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--keypoints", type=int, default=512)
     ap.add_argument("--transform", default="tps_0")
@@ -50,32 +70,40 @@ def parse():
                          "64 thr 6.46, 128 thr 12.05, 256 thr 73.7 -- ATen / oneDNN oversubscribe, so the fastest "
                          "setting is the default and the count actually used is reported as `cores`")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="bound of the cpu_baseline sample")
-    ap.add_argument("--also-f32", type=int, default=3,
+    ap.add_argument("--also-f32", type=int, default=None,
                     help="N > 0: also time N steps with the exact fp32-MFMA convolutions (v_mfma_f32_32x32x2_f32) and "
-                         "report them as f32_mfma_* next to the f16x3 headline (N = 1 rank only)")
-    ap.add_argument("--first-block-exact", type=int, default=3,
+                         "report them as f32_mfma_* next to the f16x3 headline (N = 1 rank only; --full: 3)")
+    ap.add_argument("--first-block-exact", type=int, default=None,
                     help="N > 0: also time N steps with the first encoder block's 32 -> 16 data gradient on bf16x6 (24 bits at "
                          "every magnitude; backbone_ops.set_first_block_dgrad) -> first_block_exact_ms_per_step: the price of "
-                         "the option DESIGN section 4 describes; never the headline")
-    ap.add_argument("--amp", type=int, default=3,
+                         "the option DESIGN section 4 describes; never the headline (--full: 3)")
+    ap.add_argument("--amp", type=int, default=None,
                     help="N > 0: also time N steps with KeyMorph(use_amp=True) -- the one-product fp16 backbone "
-                         "(keymorph/model.py:176-191) -> amp_pairs_per_s, amp_roofline against 2.5 PFLOP/s; never the headline")
-    ap.add_argument("--dice", type=int, default=3,
+                         "(keymorph/model.py:176-191) -> amp_pairs_per_s, amp_roofline against 2.5 PFLOP/s; never the headline "
+                         "(--full: 3)")
+    ap.add_argument("--dice", type=int, default=None,
                     help="N > 0: also time N steps of the Dice branch (scripts/train.py:146-164: a 14-class one-hot "
-                         "segmentation warped with the same grid + DiceLoss as the loss) -> dice_pairs_per_s")
-    ap.add_argument("--eval-steps", type=int, default=3,
+                         "segmentation warped with the same grid + DiceLoss as the loss) -> dice_pairs_per_s (--full: 3)")
+    ap.add_argument("--eval-steps", type=int, default=None,
                     help="N > 0: also time N evaluation passes (scripts/pairwise_register_eval.py:116-171: model.eval(), "
-                         "no_grad, a list of transform types, aligned points, align_img per type) -> eval_pairs_per_s")
-    ap.add_argument("--groupwise", type=int, default=8,
+                         "no_grad, a list of transform types, aligned points, align_img per type) -> eval_pairs_per_s (--full: 3)")
+    ap.add_argument("--groupwise", type=int, default=None,
                     help="S > 0: also time KeyMorph.groupwise_register over S synthetic subjects at --size (BASELINE "
-                         "configs[4]: 8 subjects, 512 keypoints, TPS, num_iters 5) -> groupwise_subjects_per_s")
-    ap.add_argument("--convnet", type=int, default=3,
-                    help="N > 0: also time N training steps with the ConvNet(instance norm) backbone (keymorph/net.py:7-36)")
-    ap.add_argument("--sampler", type=int, default=1, help="report stand-alone align_img GB/s for C = 1 and C = 14")
-    ap.add_argument("--cpu-256", type=int, default=1,
-                    help="1: also time the oracle ONCE at the metric's shape (size^3, 512 keypoints, affine, fwd+bwd; "
-                         "~1 min, ~50 GB of host RAM; skipped when less than 96 GB is available)")
-    return ap.parse_args()
+                         "configs[4]: 8 subjects, 512 keypoints, TPS, num_iters 5) -> groupwise_subjects_per_s (--full: 8)")
+    ap.add_argument("--convnet", type=int, default=None,
+                    help="N > 0: also time N training steps with the ConvNet(instance norm) backbone (keymorph/net.py:7-36) "
+                         "(--full: 3)")
+    ap.add_argument("--sampler", type=int, default=None,
+                    help="1: report stand-alone align_img GB/s for C = 1 and C = 14 (--full: 1)")
+    ap.add_argument("--cpu-256", type=int, default=None,
+                    help="1: with the CPU baseline (--full), also time the oracle ONCE at the metric's shape (size^3, 512 "
+                         "keypoints, affine, fwd+bwd; ~1 min, ~50 GB of host RAM; skipped when less than 96 GB is available) "
+                         "(--full: 1)")
+    a = ap.parse_args(argv)
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v if a.full else 0)
+    return a
 
 
 def _free_port():
@@ -140,12 +168,15 @@ def build_model(K, device):
     return KeyMorph(net, K, 3, max_train_keypoints=None).to(device).train()
 
 
-def train_step(model, flat, opt, img_f, img_m, tt, seg_f=None, seg_m=None):
+def train_step(model, flat, opt, img_f, img_m, tt, seg_f=None, seg_m=None, keep=None):
     """scripts/train.py:102-176.  seg_* given: the Dice branch (loss_fn == "dice"): the one-hot moving segmentation is
-    warped with the same grid (bilinear, so that it is differentiable) and soft Dice is the loss."""
+    warped with the same grid (bilinear, so that it is differentiable) and soft Dice is the loss.  `keep` (a dict) receives
+    the forward's result as keep["res"]."""
     from keymorph_amd import loss_ops, ops, utils
     flat.zero_grad()
     res = model(img_f, img_m, transform_type=tt, return_aligned_points=False)[tt]
+    if keep is not None:
+        keep["res"] = res
     if seg_f is None:
         loss, _img_a = ops.warp_mse(img_m, res["grid"], img_f)   # align_img + MSELoss, one pass
     else:
@@ -157,6 +188,28 @@ def train_step(model, flat, opt, img_f, img_m, tt, seg_f=None, seg_m=None):
     scale = flat.allreduce_grads()
     opt.step(scale)
     return loss
+
+
+def dump_outputs(path, arrays):
+    """name -> tensor, written as path/<name>.npy: float64 stays float64, everything else float32.  An array of more than
+    DUMP_MAX_VALUES values is replaced by the values at DUMP_MAX_VALUES flat indices drawn from a generator seeded with 0
+    (the same indices for the same shape).  -> name -> what was written, for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    notes = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        n = t.numel()
+        what = f"{tuple(t.shape)} {t.dtype}".replace("torch.", "")
+        if n > DUMP_MAX_VALUES:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, n, (DUMP_MAX_VALUES,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            what = f"seeded sample of {DUMP_MAX_VALUES} of the {n} values of {what}"
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        notes[name] = what
+    return notes
 
 
 def synthetic_segmentation(img, classes=14):
@@ -440,26 +493,31 @@ def main():
     for _ in range(a.warmup):
         loss = train_step(model, flat, opt, img_f, img_m, tt)
     sync()
+    last = {}
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        loss = train_step(model, flat, opt, img_f, img_m, tt)
+    for i in range(a.steps):      # the last step hands its forward result on (the dumped outputs)
+        loss = train_step(model, flat, opt, img_f, img_m, tt, keep=last if i == a.steps - 1 else None)
     sync()
     dt = time.perf_counter() - t0
-    power_w, sclk_mhz = gpu_sensors(dev.index if dev.index is not None else 0)      # right after the timed steps
-    sensors = torch.tensor([power_w if power_w is not None else float("nan"), sclk_mhz if sclk_mhz is not None else float("nan")],
-                           dtype=torch.float64, device=dev)
-    rank_sensors = [sensors.tolist()]
+    rank_sensors = None
+    if a.full:
+        power_w, sclk_mhz = gpu_sensors(dev.index if dev.index is not None else 0)      # right after the timed steps
+        sensors = torch.tensor([power_w if power_w is not None else float("nan"),
+                                sclk_mhz if sclk_mhz is not None else float("nan")], dtype=torch.float64, device=dev)
+        rank_sensors = [sensors.tolist()]
+        if world > 1:
+            every_s = [torch.empty_like(sensors) for _ in range(world)]
+            torch.distributed.all_gather(every_s, sensors)
+            rank_sensors = [x.tolist() for x in every_s]
     rank_ms = [1000 * dt / a.steps]
-    allreduce_ms = 0.0
+    allreduce_ms = 0.0 if world == 1 else None
     if world > 1:
-        every_s = [torch.empty_like(sensors) for _ in range(world)]
-        torch.distributed.all_gather(every_s, sensors)
-        rank_sensors = [x.tolist() for x in every_s]
         t = torch.tensor([dt], device=dev)
         every = [torch.empty_like(t) for _ in range(world)]
         torch.distributed.all_gather(every, t)
         rank_ms = [1000 * float(x.item()) / a.steps for x in every]       # each rank's own clock around the same K steps
         dt = max(float(x.item()) for x in every)                          # MAX over ranks
+    if world > 1 and a.full:
         # the step's only exchange, timed alone: the flat gradient bucket summed over the ranks (RCCL over xGMI)
         g = flat.grad.clone()
         torch.distributed.all_reduce(g)
@@ -475,6 +533,12 @@ def main():
     # keypoints coincide): refuse to report it
     if not (math.isfinite(loss_val) and bool(torch.isfinite(flat.flat).all()) and bool(torch.isfinite(flat.grad).all())):
         raise SystemExit(f"bench.py: non-finite loss / parameters / gradients after the timed steps (loss {loss_val})")
+    dumped = None
+    if a.dump_outputs and rank == 0:      # before any side leg moves the parameters on
+        dumped = dump_outputs(a.dump_outputs, {
+            "loss": loss.detach().double(), "points_f": last["res"]["points_f"], "points_m": last["res"]["points_m"],
+            "grid": last["res"]["grid"], "params": flat.flat, "grads": flat.grad})
+    last.clear()
 
     def timed(nsteps, **kw):
         sync()
@@ -741,37 +805,29 @@ def main():
         torch.distributed.all_reduce(probe)
         rccl_ranks = int(probe.item())
 
-    # one extra (untimed) step with HIP events around every library launch -> per-kernel roofline
-    _lib.profiler.reset()
-    _lib.profiler.enabled = True
-    train_step(model, flat, opt, img_f, img_m, tt)
-    prof = _lib.profiler.summary()
-    if os.environ.get("KMH_BENCH_DETAIL") and rank == 0:
-        for name, ea, eb, meta in _lib.profiler.records:
-            if meta and "shape" in meta:
-                ms = ea.elapsed_time(eb)
-                print(f"# {name:18s} {str(meta['shape']):34s} {ms:8.3f} ms {meta['flops'] / ms / 1e9:7.1f} TF", file=sys.stderr)
-    # algorithmic bytes of the dominant kernel's launches: input + output tensor of each, once (fp32)
-    # the dominant kernel family: every launch of conv3_fwd_g_kernel / conv3_fwd_bf_kernel, i.e. kmh_conv3d_fwd_bf and its
-    # pooling-epilogue variant kmh_conv3d_fwd_bf_pool (same kernel, the output written pooled: 1/8 of the output bytes)
-    conv_names = ("kmh_conv3d_fwd",) if a.conv == "f32" else ("kmh_conv3d_fwd_bf", "kmh_conv3d_fwd_bf_pool")
-    conv_alg_bytes = [4.0 * m["shape"][0] * m["shape"][1] * m["shape"][2] * m["shape"][3] *
-                      (m["shape"][4] + m["shape"][5] * (0.125 if name.endswith("_pool") else 1.0))
-                      for name, _, _, m in _lib.profiler.records if name in conv_names and m and "shape" in m]
-    _lib.profiler.enabled = False
+    prof, conv_alg_bytes = None, []
+    if a.full:
+        # one extra (untimed) step with HIP events around every library launch -> per-kernel roofline
+        _lib.profiler.reset()
+        _lib.profiler.enabled = True
+        train_step(model, flat, opt, img_f, img_m, tt)
+        prof = _lib.profiler.summary()
+        if os.environ.get("KMH_BENCH_DETAIL") and rank == 0:
+            for name, ea, eb, meta in _lib.profiler.records:
+                if meta and "shape" in meta:
+                    ms = ea.elapsed_time(eb)
+                    print(f"# {name:18s} {str(meta['shape']):34s} {ms:8.3f} ms {meta['flops'] / ms / 1e9:7.1f} TF", file=sys.stderr)
+        # algorithmic bytes of the dominant kernel's launches: input + output tensor of each, once (fp32)
+        # the dominant kernel family: every launch of conv3_fwd_g_kernel / conv3_fwd_bf_kernel, i.e. kmh_conv3d_fwd_bf and its
+        # pooling-epilogue variant kmh_conv3d_fwd_bf_pool (same kernel, the output written pooled: 1/8 of the output bytes)
+        conv_names = ("kmh_conv3d_fwd",) if a.conv == "f32" else ("kmh_conv3d_fwd_bf", "kmh_conv3d_fwd_bf_pool")
+        conv_alg_bytes = [4.0 * m["shape"][0] * m["shape"][1] * m["shape"][2] * m["shape"][3] *
+                          (m["shape"][4] + m["shape"][5] * (0.125 if name.endswith("_pool") else 1.0))
+                          for name, _, _, m in _lib.profiler.records if name in conv_names and m and "shape" in m]
+        _lib.profiler.enabled = False
     peak_mem = torch.cuda.max_memory_allocated() / 2 ** 30
 
     if rank == 0:
-        conv = {"ms": 0.0, "flops": 0.0, "calls": 0}
-        for nm in conv_names:
-            for k in conv:
-                conv[k] += prof.get(nm, {}).get(k, 0)
-        conv["calls"] = max(conv["calls"], 1)
-        wg = prof.get("kmh_conv3d_wgrad" if a.conv == "f32" else "kmh_conv3d_wgrad_bf", {"ms": 0.0, "flops": 0.0, "calls": 1})
-        conv_tf = conv["flops"] / max(conv["ms"], 1e-9) / 1e9
-        total_ms = sum(v["ms"] for v in prof.values())
-        gs = prof.get("kmh_warp_mse_fwd_grad", prof.get("kmh_warp_mse_fwd", prof.get("kmh_grid_sample3d_fwd", {"ms": 0, "bytes": 0})))
-        gsb = prof.get("kmh_grid_sample3d_bwd_grid", {"ms": 0, "bytes": 0})
         backend = torch.distributed.get_backend() if world > 1 else None
         transport = (rccl_transport_summary(rccl_log) if (rccl_log and world > 1 and backend == "nccl") else
                      ({"backend": backend} if world > 1 else None))
@@ -801,11 +857,11 @@ def main():
                              "torch.distributed.run / external") if world > 1 else None,
                 "rank_ms_per_step_min_max": [min(rank_ms), max(rank_ms)],
                 # every rank's GPU right after the timed steps (amdgpu hwmon: power1_average, freq1_input): ranks under
-                # different power caps / clocks show up here before they show up as a scaling loss
+                # different power caps / clocks show up here before they show up as a scaling loss (--full)
                 "rank_power_w_min_max": ([min(p for p, _ in rank_sensors), max(p for p, _ in rank_sensors)]
-                                         if all(p == p for p, _ in rank_sensors) else None),
+                                         if rank_sensors and all(p == p for p, _ in rank_sensors) else None),
                 "rank_sclk_mhz_min_max": ([min(c for _, c in rank_sensors), max(c for _, c in rank_sensors)]
-                                          if all(c == c for _, c in rank_sensors) else None),
+                                          if rank_sensors and all(c == c for _, c in rank_sensors) else None),
                 "rccl_transport": transport,
                 "rccl_transport_check": transport_check,
                 "allreduce_ms_per_step": allreduce_ms,
@@ -829,26 +885,41 @@ def main():
                                "bf16x6": "fp32 operands split into bf16 hi+mid+lo, 6 MFMA products, fp32 accumulate",
                                "f32": "v_mfma_f32_32x32x2_f32"}[a.conv],
             },
-            "roofline": roofline(a.conv, conv_tf) | {
-                "launches": conv["calls"],
-                "avg_launch_ms": conv["ms"] / max(conv["calls"], 1),
-                "share_of_step_kernel_time": conv["ms"] / max(total_ms, 1e-9),
-                "algorithmic_bytes_per_launch": (sum(conv_alg_bytes) / len(conv_alg_bytes)) if conv_alg_bytes else None,
-            },
-            "kernels_ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
-            "wgrad_tflops": wg["flops"] / max(wg["ms"], 1e-9) / 1e9,
-            # warp + MSE + d(loss)/d(grid) are ONE launch (kmh_warp_mse_fwd_grad): 36 algorithmic bytes per voxel
-            # (grid 12 + volume 4 + fixed 4 + warped 4 + dgrid 12) where the three-launch route moved 68
-            "grid_sample": {"kernel": "sample_fwd_lc_kernel<0,true,true> (warp + MSE + grid gradient, one pass)",
-                            "ms": gs["ms"], "algorithmic_GB": gs.get("bytes", 0) / 1e9,
-                            "achieved_GBps": gs.get("bytes", 0) / max(gs["ms"], 1e-9) / 1e6,
-                            "frac_of_hbm_peak": gs.get("bytes", 0) / max(gs["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS,
-                            "separate_bwd_ms": gsb["ms"]},
             "loss": loss_val,
             "peak_mem_gib": peak_mem,
         }
+        if dumped is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        if prof is not None:
+            conv = {"ms": 0.0, "flops": 0.0, "calls": 0}
+            for nm in conv_names:
+                for k in conv:
+                    conv[k] += prof.get(nm, {}).get(k, 0)
+            conv["calls"] = max(conv["calls"], 1)
+            wg = prof.get("kmh_conv3d_wgrad" if a.conv == "f32" else "kmh_conv3d_wgrad_bf", {"ms": 0.0, "flops": 0.0, "calls": 1})
+            conv_tf = conv["flops"] / max(conv["ms"], 1e-9) / 1e9
+            total_ms = sum(v["ms"] for v in prof.values())
+            gs = prof.get("kmh_warp_mse_fwd_grad", prof.get("kmh_warp_mse_fwd", prof.get("kmh_grid_sample3d_fwd", {"ms": 0, "bytes": 0})))
+            gsb = prof.get("kmh_grid_sample3d_bwd_grid", {"ms": 0, "bytes": 0})
+            out.update({
+                "roofline": roofline(a.conv, conv_tf) | {
+                    "launches": conv["calls"],
+                    "avg_launch_ms": conv["ms"] / max(conv["calls"], 1),
+                    "share_of_step_kernel_time": conv["ms"] / max(total_ms, 1e-9),
+                    "algorithmic_bytes_per_launch": (sum(conv_alg_bytes) / len(conv_alg_bytes)) if conv_alg_bytes else None,
+                },
+                "kernels_ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
+                "wgrad_tflops": wg["flops"] / max(wg["ms"], 1e-9) / 1e9,
+                # warp + MSE + d(loss)/d(grid) are ONE launch (kmh_warp_mse_fwd_grad): 36 algorithmic bytes per voxel
+                # (grid 12 + volume 4 + fixed 4 + warped 4 + dgrid 12) where the three-launch route moved 68
+                "grid_sample": {"kernel": "sample_fwd_lc_kernel<0,true,true> (warp + MSE + grid gradient, one pass)",
+                                "ms": gs["ms"], "algorithmic_GB": gs.get("bytes", 0) / 1e9,
+                                "achieved_GBps": gs.get("bytes", 0) / max(gs["ms"], 1e-9) / 1e6,
+                                "frac_of_hbm_peak": gs.get("bytes", 0) / max(gs["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS,
+                                "separate_bwd_ms": gsb["ms"]},
+            })
         out.update(extra)
-        if not a.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
+        if a.full and not a.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
             # order matters: the full-size oracle (child process) and the HIP comparison first, the in-process 128^3 sample
             # (which changes this process's intra-op thread count) last
             big = cpu_baseline_at_size(a.size, a.keypoints, a.cpu_threads) if a.cpu_256 else {}

@@ -96,10 +96,21 @@ def test_install_refuses_after_the_reference_was_imported(tmp_path):
     _run(code, [str(tmp_path)])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/keymorph"), reason="the reference checkout exists only in the build container")
-def test_install_over_the_real_reference_checkout():
-    """In the build container: the REAL package is the parent.  Its __init__ (`from . import model`, ...) picks up the
-    aliases, its viz_tools is its own file, and none of the third-party imports of the replaced modules (nibabel, skimage,
-    h5py) is needed any more."""
-    _run("import keymorph_amd.dropin as d\np = d.install()\nassert p.__file__.startswith('/root/reference')\n"
-         + SCRIPT_IMPORTS + CHECKS + "import keymorph\nassert keymorph.__version__ == '2.0.1'\n", ["/root/reference"])
+def test_install_over_a_full_checkout(tmp_path):
+    """A complete checkout is the parent: a stand-in with every module of the maintainer's package, each replaced one
+    raising on import (as if its third-party imports -- nibabel, skimage, h5py -- were missing).  Its __init__ imports
+    all its submodules and picks up the aliases, its viz_tools is its own file, and no replaced module is ever executed."""
+    pkg = tmp_path / "keymorph"
+    (pkg / "unet3d").mkdir(parents=True)
+    own = ("augmentation", "keypoint_aligners", "layers", "loss_ops", "model", "net", "utils")
+    (pkg / "__init__.py").write_text('__version__ = "standin"\n' + "".join(f"from . import {m}\n" for m in own + ("viz_tools",)))
+    for m in own + ("transformations", "unet3d/model"):
+        (pkg / f"{m}.py").write_text(f"raise ImportError('the checkout\\'s own {m} must not be imported')\n")
+    (pkg / "unet3d" / "__init__.py").write_text("")
+    (pkg / "viz_tools.py").write_text(textwrap.dedent("""
+        def imshow_img_and_points_3d(*a, **k): pass
+        def imshow_registration_2d(*a, **k): pass
+        def imshow_registration_3d(*a, **k): pass
+    """))
+    _run(f"import keymorph_amd.dropin as d\np = d.install()\nassert p.__file__ == {str(pkg / '__init__.py')!r}\n"
+         + SCRIPT_IMPORTS + CHECKS + "import keymorph\nassert keymorph.__version__ == 'standin'\n", [str(tmp_path)])

@@ -255,18 +255,25 @@ def test_pair_loader_shim(tmp_path):
     assert first == [(f["img"]["path"], m["img"]["path"]) for f, m in PairLoader(subs, steps=5, seed=3)]
 
 
-def test_nifti_reader_on_reference_example_data():
-    """build container only (the GPU box has no /root/reference): example_data_half's label maps are 256^3 float64
-    with 14 labels and an LPS-flipped identity affine."""
-    import glob
+def test_nifti_reader_on_reference_example_data(tmp_path):
+    """example_data_half's label maps are 256^3 float64 with 14 labels and an LPS-flipped identity affine.
+    The first seg_m file is rebuilt from fixtures: its own 352-byte header (tests/golden/example_half_seg_header.bin,
+    verbatim) followed by its label map at stride 2 (cfg1_example_half_128.npz label_0) repeated back to 256^3."""
+    import gzip
     import numpy as np
-    import pytest
-    files = sorted(glob.glob("/root/reference/example_data_half/seg_m/*.nii.gz"))
-    if not files:
-        pytest.skip("reference example data not present")
     from keymorph_amd.io import read_nifti
-    a, A = read_nifti(files[0], dtype=None)
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    with open(os.path.join(golden, "example_half_seg_header.bin"), "rb") as f:
+        header = f.read()
+    lab = np.load(os.path.join(golden, "cfg1_example_half_128.npz"))["label_0"]
+    vol = lab.repeat(2, 0).repeat(2, 1).repeat(2, 2).astype("<f8")
+    path = tmp_path / "seg_m.nii.gz"
+    with gzip.open(path, "wb", compresslevel=1) as f:
+        f.write(header)
+        f.write(vol.tobytes(order="F"))
+    a, A = read_nifti(str(path), dtype=None)
     assert a.shape == (256, 256, 256) and a.dtype == np.float64
+    assert np.array_equal(a, vol)
     assert np.array_equal(np.unique(a), np.arange(14.0))
     np.testing.assert_allclose(A, np.diag([-1.0, -1.0, 1.0, 1.0]))
 
@@ -490,3 +497,34 @@ def test_amp_scope_is_per_thread_and_travels_with_the_autograd_node():
     assert log[0] == ("fwd", True) and log[1] == ("fwd", False)
     assert log[2][0] == "bwd" and log[2][1] is True            # the forward's setting, not the last one seen
     assert torch.equal(x.grad, torch.full((3,), 2.0)) and B.amp_enabled() is B._AMP_DEFAULT
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain bench.py run times the headline alone: every side leg's size is 0 unless given, --full turns them all on at
+    their sizes, an explicit size wins either way.  dump_outputs writes float32 (float64 stays float64) and replaces an array
+    of more than DUMP_MAX_VALUES values by a seeded sample: the same values for the same input."""
+    import importlib
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    plain, full = bench.parse(["--steps", "7"]), bench.parse(["--full", "--dice", "1"])
+    assert plain.steps == 7 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) == 0 for k in bench.FULL_DEFAULTS)
+    assert full.dice == 1 and all(getattr(full, k) == v for k, v in bench.FULL_DEFAULTS.items() if k != "dice")
+    assert bench.parse(["--convnet", "2"]).convnet == 2
+    assert bench.parse(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+
+    n = bench.DUMP_MAX_VALUES
+    big = torch.arange(n + 2, dtype=torch.float32).reshape(-1, 3)
+    arrays = {"loss": torch.tensor(0.25, dtype=torch.float64), "small": torch.arange(6, dtype=torch.int32).reshape(2, 3),
+              "big": big}
+    notes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    loss, small, got = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("loss", "small", "big"))
+    assert loss.dtype == np.float64 and float(loss) == 0.25
+    assert small.dtype == np.float32 and small.shape == (2, 3) and small.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert got.dtype == np.float32 and got.shape == (n,) and "seeded sample" in notes["big"]
+    assert np.all(np.diff(got) >= 0) and got.max() < n + 2            # values of the array at sorted flat indices
+    assert np.array_equal(got, np.load(tmp_path / "b" / "big.npy"))

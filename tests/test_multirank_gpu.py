@@ -122,7 +122,7 @@ def test_bench_self_launch_runs_the_hip_step_on_n_ranks(world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     if shared:
         env.update(KEYMORPH_DIST_BACKEND="gloo", KEYMORPH_SHARE_GPU="1")
-    args = ["--gpus", str(world), "--size", "32", "--keypoints", "16", "--steps", "2", "--warmup", "1", "--dice", "1",
+    args = ["--gpus", str(world), "--full", "--size", "32", "--keypoints", "16", "--steps", "2", "--warmup", "1", "--dice", "1",
             "--also-f32", "0", "--eval-steps", "1", "--groupwise", "8" if world == 8 else "3", "--convnet", "0", "--sampler", "0",
             "--transform", "tps_1"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, env=env, capture_output=True, text=True,

@@ -189,3 +189,35 @@ def test_use_checkpoint_bit_identical_gradients_and_smaller_peak(size, levels, t
         assert torch.isfinite(g0[k]).all() and torch.equal(g0[k], g1[k]), k
     print(f"use_checkpoint at {size}^3, {levels} levels: peak device memory over the step {m0 / 2**20:.0f} MiB -> {m1 / 2**20:.0f} MiB")
     assert m1 < shrink * m0, (m0, m1)      # (40^3, three levels: the step's peak is mostly the TPS grid and the workspaces)
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """bench.py without --full prints the headline alone (no roofline, side-leg or CPU-baseline keys) over exactly --steps
+    timed steps, and --dump-outputs DIR holds what the last of them computed: the loss of the line, the keypoints, the grid,
+    the parameters after the optimizer step and their gradients, float32 / float64, well under 64 MB."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "32", "--keypoints", "16", "--steps", "2",
+                        "--warmup", "1", "--transform", "tps_1", "--dump-outputs", str(out)], env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and abs(d["value"] - 2 * 1000 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert not {"roofline", "kernels_ms", "cpu_baseline", "dice_pairs_per_s", "f32_mfma_ms_per_step", "eval_pairs_per_s",
+                "groupwise_subjects_per_s", "convnet_pairs_per_s", "align_img_standalone"} & set(d), d.keys()
+    names = ("loss", "points_f", "points_m", "grid", "params", "grads")
+    assert sorted(os.listdir(out)) == sorted(f"{k}.npy" for k in names) and sorted(d["outputs"]["arrays"]) == sorted(names)
+    got = {k: np.load(out / f"{k}.npy") for k in names}
+    assert got["loss"].dtype == np.float64 and float(got["loss"]) == d["loss"]
+    assert got["points_f"].shape == got["points_m"].shape == (2, 16, 3) and got["grid"].shape == (2, 32, 32, 32, 3)
+    assert got["params"].shape == got["grads"].shape and got["params"].ndim == 1
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for k, v in got.items() if k != "loss")
+    assert float(np.abs(got["grads"]).max()) > 0
+    assert sum(os.path.getsize(out / f"{k}.npy") for k in names) < 64e6
