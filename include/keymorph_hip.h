@@ -102,6 +102,23 @@ int kmh_label_presence(const long long* seg, long long n, int nflags, int* flags
 int kmh_one_hot_select(const long long* seg, int N, long long V, const long long* labels, int C, void* out,
                        int out_i64, void* stream);
 
+/* ---- evaluation metrics: keymorph/loss_ops.py:66-158 (fast_dice, dice, hausdorff_distance) ---- */
+/* a, b: channel 0 of N samples (sample n at + n * sstride elements, each (D,H,W) contiguous); dtype 0 f32, 1 f64, 2 f16,
+ * 3 bf16, 4 one byte, 5 int16, 6 int32, 7 int64, a voxel is set iff its value != 0.  out_sq[n] = squared Hausdorff distance
+ * of the two 6-connected surfaces with spacing (sz, sy, sx) along (D, H, W): +inf if one surface is empty, NaN if both are.
+ * ws: kmh_hausdorff3d_ws_bytes(D, H, W) bytes (per sample; samples run one after the other). */
+size_t kmh_hausdorff3d_ws_bytes(int D, int H, int W);
+int kmh_hausdorff3d(const void* a, const void* b, int dtype_a, int dtype_b, long long sstride_a, long long sstride_b, int N,
+                    int D, int H, int W, double sz, double sy, double sx, void* ws, double* out_sq, void* stream);
+/* the squared distance map of one mask's surface (same passes; tests): out (D,H,W) fp64, +inf if the surface is empty */
+size_t kmh_edt3d_sq_ws_bytes(int D, int H, int W);
+int kmh_edt3d_sq(const void* a, int dtype, int D, int H, int W, double sz, double sy, double sx, void* ws, double* out,
+                 void* stream);
+/* counts (3 * nlab uint64, zeroed by the caller) = {|x = l|, |y = l|, |x = l and y = l|}; C > 0: labels = channel argmax of
+ * (N, C, V) maps of dtype 0 f32 / 1 f64, nlab = C <= 4096; C == 0: labels = (byte != 0) of N * V bytes, nlab = 2. */
+int kmh_label_counts(const void* x, const void* y, int dtype, int N, int C, long long V, unsigned long long* counts,
+                     void* stream);
+
 /* ---- a9: AffineTransform.get_flow_field, keymorph/transformations.py:37-79 and
  *      uniform_norm_grid keymorph/utils.py:387-398.  mat (N,3,4) = inverse_transform_matrix[:, :3, :]
  *      acting on ij coords; out (N,D,H,W,3) already flipped to xyz. */

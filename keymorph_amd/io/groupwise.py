@@ -4,7 +4,7 @@
     <group_dir>/registration_results/{type}_grid_{i:03}.npy        KeyMorph.groupwise_register(save_results_to_disk=True)
     <group_dir>/img_a_{type}/img_a_{type}_{i:03}.npy               aligned images
     <group_dir>/seg_a_{type}/seg_a_{type}_{i:03}.npy               aligned segmentations (bilinear)
-    <group_dir>/metrics-{type}.json                                {"mse", "softdice", "harddice", "harddiceroi", "jdstd", "jdlessthan0"}
+    <group_dir>/metrics-{type}.json                                {"mse", "softdice", "harddice", "harddiceroi", "hausd", "jdstd", "jdlessthan0"}
     <group_dir>/points_m-{aug}.npy, points_a-{aug}-{type}.npy      keypoints of the first subject before / after
 Host-side file plumbing; every warp and metric runs on the GPU (align_img, loss_ops)."""
 import json
@@ -60,7 +60,7 @@ def evaluate_group(registration_model, group_dir, transform_types, device, metri
         for name in metrics:
             if name == "mse":
                 m["mse"] = loss_ops.MSEPairwiseLoss()(img_a_paths).item()
-            elif name in ("softdice", "harddice", "harddiceroi"):
+            elif name in ("softdice", "harddice", "harddiceroi", "hausd"):
                 assert seg_available
                 seg_names.append(name)
             elif name in ("jdstd", "jdlessthan0"):

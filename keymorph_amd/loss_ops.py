@@ -1,4 +1,7 @@
 """Losses with the reference's call surface (keymorph/loss_ops.py:9-63), HIP underneath."""
+import math
+
+import numpy as np
 import torch
 
 from . import ops
@@ -96,6 +99,161 @@ def jdlessthan0(disp, as_percentage=False):
 
 
 # --------------------------------------------------------------------------
+# segmentation eval metrics on the GPU (keymorph/loss_ops.py:66-158; callers pairwise_register_eval.py:329-331,
+# groupwise_register_eval.py:492-511): csrc/metrics.hip computes the surfaces, distance transforms and label counts
+# --------------------------------------------------------------------------
+class MetricInputError(TypeError, NotImplementedError):
+    """A metric input that is neither a torch tensor nor a numpy array.  A TypeError, as in the reference (`len(None)`),
+    and a NotImplementedError, as the placeholder this function replaced raised."""
+
+
+HAUSDORFF_SAMPLING = (1.25, 1.25, 10.0)     # keymorph/loss_ops.py:157, spacing along array axes (D, H, W)
+_HD_DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.bool: 4, torch.uint8: 4,
+              torch.int8: 4, torch.int16: 5, torch.int32: 6, torch.int64: 7}
+
+
+def _on_gpu(x, fn):
+    """A tensor or ndarray as a tensor on the current GPU (the reference accepts both, utils._check_type); GPU tensors stay
+    where they are."""
+    if isinstance(x, np.ndarray):
+        if x.dtype.kind == "u" and x.dtype.itemsize > 1:        # same-width signed view: "!= 0" is unchanged
+            x = x.view(np.dtype(f"int{8 * x.dtype.itemsize}"))
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    elif not isinstance(x, torch.Tensor):
+        raise MetricInputError(f"{fn}: expected a torch.Tensor or a numpy.ndarray, got {type(x).__name__}")
+    x = x.detach()
+    dev = torch.cuda.current_device()
+    if not x.is_cuda:
+        return x.to(torch.device("cuda", dev))
+    if x.device.index != dev:
+        from ._lib import KeymorphHipError
+        raise KeymorphHipError(f"{fn}: input is on {x.device} but the current device is cuda:{dev}")
+    return x
+
+
+def _channel0(x, fn):
+    """Channel 0 of a (bs, C, D, H, W) input on the GPU, read in place where the layout allows it (no copy of C channels)."""
+    if not isinstance(x, (torch.Tensor, np.ndarray)):
+        raise MetricInputError(f"{fn}: expected a torch.Tensor or a numpy.ndarray, got {type(x).__name__}")
+    if x.ndim != 5:
+        raise ValueError(f"{fn}: expected a (bs, C, D, H, W) segmentation, got shape {tuple(x.shape)}")
+    t = _on_gpu(x[:, 0], fn)
+    if t.dtype not in _HD_DTYPES:
+        raise TypeError(f"{fn}: unsupported dtype {t.dtype}")
+    if t.shape[0] > 0 and not t[0].is_contiguous():
+        t = t.contiguous()
+    return t
+
+
+def hausdorff_distance(test_seg, gt_seg, sampling=HAUSDORFF_SAMPLING):
+    """Hausdorff distance between the surfaces of channel 0 ("brain surface") of two (bs, C, D, H, W) segmentations,
+    averaged over the batch (keymorph/loss_ops.py:121-158); a Python float.
+
+    A voxel is set iff its value != 0 (NaN included), the surface is the set minus its 6-neighbour erosion with a zero
+    border, and `sampling` weights the array axes (D, H, W).  The reference's sampling makes every squared distance an exact
+    multiple of 1/16, so the value equals the reference's bit for bit.  Differences from the reference: if exactly one
+    surface of a sample is empty the sample's distance is inf (the reference returns a number left over from scipy's
+    feature transform); both empty raises ValueError (the reference's max() of an empty array)."""
+    from . import _lib
+    from .ops import _p, _stream, check
+    a = _channel0(test_seg, "hausdorff_distance")
+    b = _channel0(gt_seg, "hausdorff_distance")
+    if a.shape != b.shape:
+        raise ValueError(f"hausdorff_distance: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+    N, D, H, W = a.shape
+    sq = []
+    if N > 0:
+        lib = _lib.load()
+        ws = torch.empty(int(lib.kmh_hausdorff3d_ws_bytes(D, H, W)), dtype=torch.uint8, device=a.device)
+        out = torch.empty(N, dtype=torch.float64, device=a.device)
+        sz, sy, sx = (float(v) for v in sampling)
+        check(lib.kmh_hausdorff3d(_p(a), _p(b), _HD_DTYPES[a.dtype], _HD_DTYPES[b.dtype], a.stride(0), b.stride(0), N, D, H,
+                                  W, sz, sy, sx, _p(ws), _p(out), _stream()), "kmh_hausdorff3d")
+        sq = out.cpu().tolist()
+    hd = 0
+    for i, v in enumerate(sq):
+        if v != v:
+            raise ValueError(f"hausdorff_distance: sample {i}: both surfaces are empty")
+        hd += math.sqrt(v)
+    return hd / N
+
+
+def surface_distance_map_sq(seg, sampling=HAUSDORFF_SAMPLING):
+    """Squared distance from every voxel to the surface of `seg != 0` ((D, H, W) tensor or array), the map
+    hausdorff_distance reduces; fp64 on the GPU, +inf everywhere if the surface is empty."""
+    from . import _lib
+    from .ops import _p, _stream, check
+    if not isinstance(seg, (torch.Tensor, np.ndarray)) or seg.ndim != 3:
+        raise ValueError("surface_distance_map_sq: expected a (D, H, W) tensor or array")
+    t = _channel0(seg[None, None], "surface_distance_map_sq")[0].contiguous()
+    D, H, W = t.shape
+    lib = _lib.load()
+    ws = torch.empty(int(lib.kmh_edt3d_sq_ws_bytes(D, H, W)), dtype=torch.uint8, device=t.device)
+    out = torch.empty((D, H, W), dtype=torch.float64, device=t.device)
+    sz, sy, sx = (float(v) for v in sampling)
+    check(lib.kmh_edt3d_sq(_p(t), _HD_DTYPES[t.dtype], D, H, W, sz, sy, sx, _p(ws), _p(out), _stream()), "kmh_edt3d_sq")
+    return out
+
+
+def _label_counts(x, y, fn, binary):
+    """(|x = l|, |y = l|, |x = l and y = l|) per label as int64 numpy arrays, counted on the GPU."""
+    from . import _lib
+    from .ops import _p, _stream, check
+    tx, ty = _on_gpu(x, fn), _on_gpu(y, fn)
+    assert tx.shape == ty.shape, "both inputs should have same size, had {} and {}".format(tuple(tx.shape), tuple(ty.shape))
+    if binary:
+        for t in (tx, ty):
+            if t.dtype != torch.bool and bool(((t != 0) & (t != 1)).any()):
+                raise ValueError(f"{fn}: expected 0/1 inputs")
+        tx, ty = ((t.view(torch.uint8) if t.dtype == torch.bool else (t != 0).to(torch.uint8)).contiguous() for t in (tx, ty))
+        N, C, V, dt = 1, 0, tx.numel(), 0
+    else:
+        if tx.dim() < 2:
+            raise ValueError(f"{fn}: expected (bs, C, ...) inputs")
+        # exact conversions only: argmax ties and order are those of the original values
+        wide = torch.float64 if tx.dtype in (torch.float64, torch.int32, torch.int64) else torch.float32
+        tx, ty = tx.to(wide).contiguous(), ty.to(wide).contiguous()
+        N, C = tx.shape[:2]
+        V, dt = tx[0, 0].numel(), (1 if wide == torch.float64 else 0)
+    nlab = C if C else 2
+    counts = torch.zeros(3 * nlab, dtype=torch.int64, device=tx.device)
+    if N * V > 0:
+        lib = _lib.load()
+        check(lib.kmh_label_counts(_p(tx), _p(ty), dt, N, C, V, _p(counts), _stream()), "kmh_label_counts")
+    cx, cy, cxy = counts.cpu().numpy().reshape(3, nlab)
+    return cx, cy, cxy
+
+
+def _dice_from_counts(cx, cy, cxy):
+    """keymorph/loss_ops.py:109-111 on counts: 2 * sum(x * y) / (sum(x) + sum(y)) (nan for two empty inputs, as numpy)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(2 * np.int64(cxy) / (np.int64(cx) + np.int64(cy)))
+
+
+def fast_dice(x, y):
+    """Mean Dice over the labels present in either channel-argmax map, pooled over the batch (keymorph/loss_ops.py:66-106);
+    a Python float equal to the reference's.  Argmax and counts run on the GPU; the arithmetic on the handful of per-label
+    counts is the reference's numpy expression.  With one label present this is dice(...) = 1.0, for tensors as for arrays
+    (the reference crashes there on torch inputs)."""
+    cx, cy, cxy = _label_counts(x, y, "fast_dice", binary=False)
+    labels = np.nonzero(cx + cy)[0]
+    if len(labels) > 1:
+        hx, hy, diag = (c[labels].astype(np.float64) for c in (cx, cy, cxy))
+        dice_score = 2 * diag / (hy + hx + 1e-5)
+    else:
+        l = labels[0]
+        dice_score = _dice_from_counts(cx[l], cy[l], cxy[l])
+    return float(np.mean(dice_score))
+
+
+def dice(x, y):
+    """2 * sum(x * y) / (sum(x) + sum(y)) of two 0/1 arrays or tensors (keymorph/loss_ops.py:109-111), counted on the GPU;
+    a Python float (nan for two empty inputs)."""
+    cx, cy, cxy = _label_counts(x, y, "dice", binary=True)
+    return _dice_from_counts(cx[1], cy[1], cxy[1])
+
+
+# --------------------------------------------------------------------------
 # groupwise evaluation metrics over files or tensor stacks (keymorph/loss_ops.py:406-551; callers
 # scripts/groupwise_register_eval.py:478-515): the pairwise / per-grid averages, HIP losses underneath
 # --------------------------------------------------------------------------
@@ -148,15 +306,21 @@ class HardDicePairwiseLoss(_AvgPairwiseLoss):
         super().__init__(DiceLoss(hard=True).forward)
 
 
+class HausdorffPairwiseLoss(_AvgPairwiseLoss):
+    def __init__(self):
+        super().__init__(hausdorff_distance)
+
+
 class MultipleAvgSegPairwiseMetric(torch.nn.Module):
-    """Several pairwise segmentation metrics in one sweep over the files (loss_ops.py:499-527).  'hausd' (scipy /
-    skimage surface distances on the host) is outside the registration path and not provided."""
+    """Several pairwise segmentation metrics in one sweep over the files (loss_ops.py:499-527)."""
 
     def __init__(self):
         super().__init__()
-        self.name2fn = {"harddice": DiceLoss(hard=True).forward,
+        self.name2fn = {"dice": fast_dice,
+                        "harddice": DiceLoss(hard=True).forward,
                         "harddiceroi": DiceLoss(hard=True, return_regions=True).forward,
-                        "softdice": DiceLoss().forward}
+                        "softdice": DiceLoss().forward,
+                        "hausd": hausdorff_distance}
 
     def forward(self, batch_of_imgs, fn_names):
         for name in fn_names:
@@ -199,13 +363,9 @@ class AvgJDLessThan0(MultipleAvgGridMetric):
         return super().forward(batch_of_grids, ["jdlessthan0"])["jdlessthan0"]
 
 
-# Host-side scipy / skimage metrics of the reference that are not on the path: the names exist so that
+# Host-side metrics of the reference that are not on the path: the names exist so that
 # `import keymorph.loss_ops as loss_ops` users can reference them; calling / constructing raises NotImplementedError.
 from ._absent import absent_class as _absent_class, absent_function as _absent_function   # noqa: E402
 
-fast_dice = _absent_function("fast_dice", "keymorph/loss_ops.py:66")
-dice = _absent_function("dice", "keymorph/loss_ops.py:109")
-hausdorff_distance = _absent_function("hausdorff_distance", "keymorph/loss_ops.py:142")
 LC2 = _absent_class("LC2", "keymorph/loss_ops.py:250", torch.nn.Module)
 ImageLC2 = _absent_class("ImageLC2", "keymorph/loss_ops.py:305", torch.nn.Module)
-HausdorffPairwiseLoss = _absent_class("HausdorffPairwiseLoss", "keymorph/loss_ops.py:459", torch.nn.Module)
