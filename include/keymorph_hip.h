@@ -119,6 +119,19 @@ int kmh_edt3d_sq(const void* a, int dtype, int D, int H, int W, double sz, doubl
 int kmh_label_counts(const void* x, const void* y, int dtype, int N, int C, long long V, unsigned long long* counts,
                      void* stream);
 
+/* ---- LC2 / ImageLC2 similarity: keymorph/loss_ops.py:250-391 (LC2.forward/run :262-302, ImageLC2.forward/run :335-391) ---- */
+/* us, mr: (N, S, S, S) contiguous, tiled into P^3 patches without overlap (nP = S / P per axis, the remainder dropped; patch
+ * ((n nP + pz) nP + py) nP + px, B = N nP^3; LC2 is P = S).  radii: HOST array of R <= 8 radii, each with P - (2r + 1) even
+ * and >= 2, r <= 511.  out: B floats = per patch the mean over the radii of clamp((var - dist) / max(var, beta), 0, 1), or one float
+ * (reduce_mean != 0) = their mean.  ws: kmh_lc2_ws_bytes(B, R) bytes, written here and read by kmh_lc2_bwd. */
+size_t kmh_lc2_ws_bytes(int num_patches, int num_radii);
+int kmh_lc2_fwd(const float* us, const float* mr, int N, int S, int P, const int* radii, int R, double alpha, double beta,
+                int reduce_mean, void* ws, float* out, void* stream);
+/* the reference's autograd of the same: gout = B floats (or one with reduce_mean); dus, dmr (N, S, S, S), every voxel written
+ * (zero outside the crops and their 1-voxel halos); either may be NULL. */
+int kmh_lc2_bwd(const float* us, const float* mr, const float* gout, int N, int S, int P, const int* radii, int R,
+                int reduce_mean, const void* ws, float* dus, float* dmr, void* stream);
+
 /* ---- a9: AffineTransform.get_flow_field, keymorph/transformations.py:37-79 and
  *      uniform_norm_grid keymorph/utils.py:387-398.  mat (N,3,4) = inverse_transform_matrix[:, :3, :]
  *      acting on ij coords; out (N,D,H,W,3) already flipped to xyz. */

@@ -62,6 +62,9 @@ PROTOS = {
     "kmh_edt3d_sq_ws_bytes": (_sz, [_i, _i, _i]),
     "kmh_edt3d_sq": (_i, [_f, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _f, _f, _f]),
     "kmh_label_counts": (_i, [_f, _f, _i, _i, _i, _ll, _f, _f]),
+    "kmh_lc2_ws_bytes": (_sz, [_i, _i]),
+    "kmh_lc2_fwd": (_i, [_f, _f, _i, _i, _i, _f, _i, C.c_double, C.c_double, _i, _f, _f, _f]),
+    "kmh_lc2_bwd": (_i, [_f, _f, _f, _i, _i, _i, _f, _i, _i, _f, _f, _f, _f]),
     "kmh_affine_build_matrix": (_i, [_f, _f, _f, _f, _f, _i, _f]),
     "kmh_affine_points_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _f]),
     "kmh_com3d_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),

@@ -363,9 +363,71 @@ class AvgJDLessThan0(MultipleAvgGridMetric):
         return super().forward(batch_of_grids, ["jdlessthan0"])["jdlessthan0"]
 
 
-# Host-side metrics of the reference that are not on the path: the names exist so that
-# `import keymorph.loss_ops as loss_ops` users can reference them; calling / constructing raises NotImplementedError.
-from ._absent import absent_class as _absent_class, absent_function as _absent_function   # noqa: E402
+# --------------------------------------------------------------------------
+# LC2 / ImageLC2 on the GPU (keymorph/loss_ops.py:250-391): csrc/lc2.hip forms the gradient magnitude, the moments, the 3 x 3
+# solve and the backward; ImageLC2's patch tiling is index arithmetic inside the kernels (no patch batch is copied)
+# --------------------------------------------------------------------------
+_LC2_ALPHA, _LC2_BETA = 1e-3, 1e-2          # run()'s defaults, the values forward() uses (loss_ops.py:268, 360)
 
-LC2 = _absent_class("LC2", "keymorph/loss_ops.py:250", torch.nn.Module)
-ImageLC2 = _absent_class("ImageLC2", "keymorph/loss_ops.py:305", torch.nn.Module)
+
+def _difference_filter():
+    """The reference's `f` (loss_ops.py:254-260): channel k holds +1 / -1 taps on either side of the centre along W, H, D, the
+    conv3d weight of the central differences whose norm is g.  Kept as the attribute; the kernels apply it implicitly."""
+    f = torch.zeros(3, 1, 3, 3, 3)
+    for k, (dz, dy, dx) in enumerate(((0, 0, 1), (0, 1, 0), (1, 0, 0))):
+        f[k, 0, 1 - dz, 1 - dy, 1 - dx] = 1
+        f[k, 0, 1 + dz, 1 + dy, 1 + dx] = -1
+    return f
+
+
+class LC2(torch.nn.Module):
+    """LC2 similarity of (bs, 1, S, S, S) pairs with S odd (keymorph/loss_ops.py:250-302), on the GPU: forward() returns the
+    per-sample mean of run() over `radiuses`, shape (bs,), float32, differentiable in both inputs.  A radius with
+    2r + 1 >= S raises ValueError (the reference's crop is empty there and its reshape fails)."""
+
+    def __init__(self, radiuses=(3, 5, 7)):
+        super().__init__()
+        self.radiuses = radiuses
+        self.f = _difference_filter()
+
+    def forward(self, us, mr):
+        return self._volumes(us, mr, tuple(self.radiuses), _LC2_ALPHA, _LC2_BETA)
+
+    def run(self, us, mr, radius=9, alpha=_LC2_ALPHA, beta=_LC2_BETA):
+        return self._volumes(us, mr, (radius,), alpha, beta)
+
+    @staticmethod
+    def _volumes(us, mr, radii, alpha, beta):
+        us, mr = us.squeeze(1), mr.squeeze(1)
+        assert us.shape == mr.shape
+        assert us.shape[1] == us.shape[2] == us.shape[3]
+        assert us.shape[1] % 2 == 1, "Input must be odd size"
+        return ops.lc2(us, mr, us.shape[1], radii, alpha, beta)
+
+
+class ImageLC2(torch.nn.Module):
+    """LC2 over non-overlapping patch_size^3 patches of (N, 1, S, S, S) volumes (keymorph/loss_ops.py:305-391), on the GPU:
+    S // patch_size patches per axis (the remainder dropped), in (N, nD, nH, nW) order; forward() returns their mean
+    (reduction "mean") or the per-patch vector (None), float32, differentiable in both inputs.  The reference's assertions
+    are kept, its odd-channel check included; like the reference it works for one channel only (ValueError otherwise)."""
+
+    def __init__(self, patch_size=51, radiuses=(5,), reduction="mean"):
+        super().__init__()
+        self.patch_size = patch_size
+        self.radii = radiuses
+        assert reduction in ["mean", None]
+        self.reduction = reduction
+        self.f = _difference_filter()
+
+    def forward(self, us, mr):
+        assert us.shape == mr.shape, f"Input and target have different shapes, {us.shape} vs {mr.shape}"
+        assert us.shape[-1] == us.shape[-2] == us.shape[-3], f"Dimensions must be equal, currently {us.shape}"
+        assert us.shape[1] % 2 == 1, f"Input must be odd size, currently {us.shape}"
+        if us.dim() != 5:
+            raise ValueError(f"ImageLC2: expected (N, 1, S, S, S) volumes, got {tuple(us.shape)}")
+        return ops.lc2(us, mr, self.patch_size, tuple(self.radii), _LC2_ALPHA, _LC2_BETA, self.reduction == "mean")
+
+    def run(self, us, mr, radius=9, alpha=_LC2_ALPHA, beta=_LC2_BETA):
+        """run() on a batch of (B, 1, P, P, P) patches -> (B,)."""
+        us, mr = us.squeeze(1), mr.squeeze(1)
+        return ops.lc2(us, mr, us.shape[-1], (radius,), alpha, beta)

@@ -572,3 +572,64 @@ class _Com3d(torch.autograd.Function):
 def com3d(feat: Tensor) -> Tensor:
     """(N,K,D,H,W) -> (N,K,3) in (z,y,x) order, [-1,1]."""
     return _Com3d.apply(feat)
+
+
+# --------------------------------------------------------------------------
+# LC2 / ImageLC2 similarity (keymorph/loss_ops.py:250-391)
+# --------------------------------------------------------------------------
+class _LC2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, us, mr, patch, radii, alpha, beta, mean):
+        import ctypes
+        shape = us.shape
+        us, mr = _prep(us, "us"), _prep(mr, "mr")
+        lib = _lib.load()
+        N, S = shape[0], shape[-1]
+        if mr.shape != shape or us.numel() != N * S ** 3:
+            raise ValueError(f"lc2: expected two (N, [1,] S, S, S) volumes, got {tuple(shape)} and {tuple(mr.shape)}")
+        nP = S // patch
+        B, R = N * nP ** 3, len(radii)
+        rad = (ctypes.c_int * R)(*radii)
+        ws = torch.empty(max(int(lib.kmh_lc2_ws_bytes(B, R)), 1), dtype=torch.uint8, device=us.device)
+        out = torch.empty(() if mean else (B,), dtype=torch.float32, device=us.device)
+        check(lib.kmh_lc2_fwd(_p(us), _p(mr), N, S, patch, rad, R, alpha, beta, int(mean), _p(ws), _p(out), _stream()),
+              "kmh_lc2_fwd")
+        ctx.save_for_backward(us, mr, ws)
+        ctx.args = (N, S, patch, radii, int(mean), shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        import ctypes
+        lib = _lib.load()
+        us, mr, ws = ctx.saved_tensors
+        N, S, patch, radii, mean, shape = ctx.args
+        gout = _prep(gout)
+        rad = (ctypes.c_int * len(radii))(*radii)
+        dus = torch.empty_like(us) if ctx.needs_input_grad[0] else None
+        dmr = torch.empty_like(mr) if ctx.needs_input_grad[1] else None
+        check(lib.kmh_lc2_bwd(_p(us), _p(mr), _p(gout), N, S, patch, rad, len(radii), mean, _p(ws), _p(dus), _p(dmr),
+                              _stream()), "kmh_lc2_bwd")
+        return (None if dus is None else dus.view(shape)), (None if dmr is None else dmr.view(shape)), \
+            None, None, None, None, None
+
+
+def lc2(us: Tensor, mr: Tensor, patch: int, radii: Sequence[int], alpha: float = 1e-3, beta: float = 1e-2,
+        mean: bool = False) -> Tensor:
+    """LC2 of two (N, [1,] S, S, S) volumes tiled into non-overlapping patch^3 patches (S // patch per axis, the remainder
+    dropped): per patch the mean over `radii` of clamp((var - dist) / max(var, beta), 0, 1) on the centred (2r + 1)^3 crop ->
+    (N (S // patch)^3,) float32 in (n, pz, py, px) order, or its mean over the patches if `mean`.  Differentiable in both
+    volumes.  A radius whose centred crop [pad:-pad] of a patch is not 2r + 1 wide (pad <= 0, or patch - (2r + 1) odd) raises
+    ValueError: the reference's reshape fails there (keymorph/loss_ops.py:283-286)."""
+    patch, radii = int(patch), tuple(int(r) for r in radii)
+    if us.shape != mr.shape or us.dim() not in (4, 5) or (us.dim() == 5 and us.shape[1] != 1) \
+            or not us.shape[-1] == us.shape[-2] == us.shape[-3]:
+        raise ValueError(f"lc2: expected two (N, [1,] S, S, S) volumes, got {tuple(us.shape)} and {tuple(mr.shape)}")
+    if not radii or us.shape[-1] < patch or us.shape[0] < 1:
+        raise ValueError(f"lc2: no radius, or no {patch}^3 patch in a volume of shape {tuple(us.shape)}")
+    for r in radii:
+        w = 2 * r + 1
+        pad = (patch - w) // 2
+        if pad < 1 or patch - 2 * pad != w:
+            raise ValueError(f"lc2: radius {r} does not fit a patch of {patch}: the crop [{pad}:-{pad}] is not {w} voxels wide")
+    return _LC2.apply(us, mr, patch, radii, float(alpha), float(beta), bool(mean))
