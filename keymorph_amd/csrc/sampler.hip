@@ -6,6 +6,15 @@
 // L2 / Infinity Cache because neighbouring voxels sample neighbouring texels).  Each thread
 // owns VPT=4 consecutive output voxels so the grid is read as 3 x 16-B loads and the output
 // written as one 16-B store per channel.
+//
+// Source coordinate (unnorm_clip): ((g + 1) * size - 1) / 2 in fp32 with every operation rounded on its own, as ATen's CPU
+// grid_sampler_3d computes it -- the product is kept out of -ffp-contract=fast's fused multiply-add, because one ulp of the
+// coordinate moves floor() to the neighbouring cell at lattice points (the grid gradient then takes that cell's difference)
+// and flips the clamp mask at the first and last voxel centre.  Then ATen's clip_coordinates_set_grad: <= 0 -> 0 and
+// >= size - 1 -> size - 1, both with a zero derivative.
+// NaN coordinates: clamped to the far border (size - 1) of their axis, as ATen's forward does; a voxel with a NaN
+// coordinate passes no gradient to the grid (all three components 0) nor to the volume, as ATen's backward.  So every
+// coordinate that reaches floor() lies in [0, size - 1] and every corner address derived from it is inside the volume.
 #include "common.h"
 #include <cstdlib>
 
@@ -21,14 +30,25 @@ struct Tap {
 };
 
 __device__ __forceinline__ float unnorm_clip(float g, int size, float& mult) {
-  // ((g+1)*size-1)/2 then clip_coordinates_set_grad: borders count as out of bounds for the grad
-  float v = ((g + 1.f) * (float)size - 1.f) * 0.5f;
-  float hi = (float)(size - 1);
+  // ((g+1)*size-1)/2 then clip_coordinates_set_grad: borders count as out of bounds for the grad.  The product is rounded
+  // on its own, as ATen's CPU kernel rounds it: under -ffp-contract=fast it would be fused into the subtraction (one
+  // v_fma_f32, one rounding), and one ulp of the coordinate moves floor() to the neighbouring cell at lattice points and
+  // flips the clamp mask at the first and last voxel centre.  The empty asm makes the product opaque, so it stays a
+  // v_mul_f32 followed by a v_add_f32 (__fmul_rn and `#pragma clang fp contract(off)` are both contracted anyway).
+  float p = (g + 1.f) * (float)size;
+  asm volatile("" : "+v"(p));
+  const float v = (p - 1.f) * 0.5f;
+  const float hi = (float)(size - 1);
   if (v <= 0.f) { mult = 0.f; return 0.f; }
-  if (v >= hi) { mult = 0.f; return hi; }
+  if (!(v < hi)) { mult = 0.f; return hi; }      // v >= hi, and NaN: the far border (ATen's clip_coordinates)
   mult = 0.5f * (float)size;
   return v;
 }
+
+// a voxel with a NaN coordinate passes no gradient at all (ATen's backward finds none of its corners inside the volume).
+// Tested where the gradient is written, on the coordinates still in registers or LDS there (not in make_tap: keeping the
+// flag live across the channel loop costs the fused warp + MSE + gradient kernel 6 VGPRs and a wave per SIMD).
+__device__ __forceinline__ bool any_nan(float gx, float gy, float gz) { return gx != gx || gy != gy || gz != gz; }
 
 __device__ __forceinline__ Tap make_tap(float gx, float gy, float gz, int D, int H, int W) {
   Tap t;
@@ -170,6 +190,7 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_kernel(
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {
     t[i] = make_tap(g[i][0], g[i][1], g[i][2], D, H, W);
+    if (any_nan(g[i][0], g[i][1], g[i][2])) t[i].mx = t[i].my = t[i].mz = 0.f;
     gx[i] = gy[i] = gz[i] = 0.f;
   }
   const long long plane = (long long)D * H * W;
@@ -371,7 +392,8 @@ __global__ __launch_bounds__(TPB) void sample_fwd_lc_kernel(
 #pragma unroll
       for (int u = 0; u < ILP; ++u) {
         const int l = tid + (j0 + u) * TPB;
-        sg[l * 3] = ggx[u] * t[u].mx; sg[l * 3 + 1] = ggy[u] * t[u].my; sg[l * 3 + 2] = ggz[u] * t[u].mz;
+        const float k = any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2]) ? 0.f : 1.f;
+        sg[l * 3] = ggx[u] * t[u].mx * k; sg[l * 3 + 1] = ggy[u] * t[u].my * k; sg[l * 3 + 2] = ggz[u] * t[u].mz * k;
       }
     }
   }
@@ -439,7 +461,8 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_lc_kernel(
 #pragma unroll
     for (int u = 0; u < ILP; ++u) {
       const int l = tid + (j0 + u) * TPB;
-      sg[l * 3] = gx[u] * t[u].mx; sg[l * 3 + 1] = gy[u] * t[u].my; sg[l * 3 + 2] = gz[u] * t[u].mz;
+      const float k = any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2]) ? 0.f : 1.f;
+      sg[l * 3] = gx[u] * t[u].mx * k; sg[l * 3 + 1] = gy[u] * t[u].my * k; sg[l * 3 + 2] = gz[u] * t[u].mz * k;
     }
   }
   __syncthreads();
@@ -1061,6 +1084,7 @@ __global__ __launch_bounds__(TPB) void warp_dice_grad_kernel(
         const int l = tid + (j0 + u) * TPB;
         float mx, my, mz;                              // d(ix)/d(gx) incl. the clamp mask, from the coordinates still in sg
         unnorm_clip(sg[l * 3], W, mx); unnorm_clip(sg[l * 3 + 1], H, my); unnorm_clip(sg[l * 3 + 2], D, mz);
+        if (any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2])) mx = my = mz = 0.f;
         sg[l * 3] = gx[u] * mx; sg[l * 3 + 1] = gy[u] * my; sg[l * 3 + 2] = gz[u] * mz;
       }
     }
@@ -1120,6 +1144,7 @@ __global__ __launch_bounds__(TPB) void sample_bwd_input_kernel(
   const long long v = (long long)blockIdx.x * TPB + threadIdx.x;
   if (v >= ovox) return;
   const float* gp = grid + ((long long)n * ovox + v) * 3;
+  if (any_nan(gp[0], gp[1], gp[2])) return;             // no gradient from a voxel with a NaN coordinate (as ATen)
   Tap t = make_tap(gp[0], gp[1], gp[2], D, H, W);
   const long long plane = (long long)D * H * W;
   const float wx[2] = {1.f - t.fx, t.fx}, wy[2] = {1.f - t.fy, t.fy}, wz[2] = {1.f - t.fz, t.fz};

@@ -205,6 +205,11 @@ def mse_loss(a: Tensor, b: Tensor) -> Tensor:
     return _MSE.apply(a, b)
 
 
+# rows per launch of kmh_dice_sums / kmh_rows_axpby: the sums' block partials (rows, blocks, 3) must fit the 65536 x 3
+# reduction workspace and the launch grid has one row of blocks per row
+_DICE_ROWS = 32768
+
+
 class _DiceRows(torch.autograd.Function):
     """per-row Dice loss 1 - (2 sum tp + 1)/(sum p^2 + sum t^2 + 1); rows = n*c."""
 
@@ -214,8 +219,10 @@ class _DiceRows(torch.autograd.Function):
         pred, target = _prep(pred), _prep(target)
         R, V = pred.shape
         sums = torch.empty((R, 3), dtype=torch.float32, device=pred.device)
-        check(lib.kmh_dice_sums(_p(pred), _p(target), R, V, _p(sums), _p(_reduce_ws(pred.device)), _stream()),
-              "kmh_dice_sums")
+        for r0 in range(0, R, _DICE_ROWS):
+            r = min(_DICE_ROWS, R - r0)
+            check(lib.kmh_dice_sums(_p(pred[r0:]), _p(target[r0:]), r, V, _p(sums[r0:]), _p(_reduce_ws(pred.device)),
+                                    _stream()), "kmh_dice_sums")
         num = 2 * sums[:, 0] + 1
         den = sums[:, 1] + sums[:, 2] + 1
         ctx.save_for_backward(pred, target, num, den)
@@ -230,7 +237,10 @@ class _DiceRows(torch.autograd.Function):
         ca = (-2.0 * g / den).contiguous()
         cb = (2.0 * g * num / (den * den)).contiguous()
         dpred = torch.empty_like(pred)
-        check(lib.kmh_rows_axpby(_p(target), _p(pred), _p(ca), _p(cb), R, V, _p(dpred), _stream()), "kmh_rows_axpby")
+        for r0 in range(0, R, _DICE_ROWS):
+            r = min(_DICE_ROWS, R - r0)
+            check(lib.kmh_rows_axpby(_p(target[r0:]), _p(pred[r0:]), _p(ca[r0:]), _p(cb[r0:]), r, V, _p(dpred[r0:]),
+                                     _stream()), "kmh_rows_axpby")
         return dpred, None
 
 
