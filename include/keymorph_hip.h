@@ -210,7 +210,8 @@ int kmh_conv3d_pack_weight(const float* w, float* packed, int Cout, int Cin, int
 int kmh_conv3d_fwd(const float* x, const float* scale, const float* shift, const float* mask,
                    const float* packed_w, const float* bias, float* y, int N, int D, int H, int W, int Cin,
                    int Cout, int relu_in, int relu_out, void* stream);
-/* Split-operand variant of the same convolution (csrc/conv_bf.hip): fp32 operands are split into 16-bit pieces and
+/* Split-operand variant of the same convolution (csrc/conv_bf.hip; fused decoder operator csrc/conv_up2.hip, weight gradient
+ * csrc/conv_wgrad.hip): fp32 operands are split into 16-bit pieces and
  * multiplied on the 16-bit matrix cores with fp32 accumulation.  terms = 2 ("f16x3", the host default): operands
  * range-scaled by powers of two (ascale / wscale = {S, 1/S} device pairs, see kmh_absmax_scale) and split into fp16
  * hi + lo, 3 MFMAs per product block; terms = 3 ("bf16x6"): bf16 hi + mid + lo, 6 MFMAs, no scales.  Both are

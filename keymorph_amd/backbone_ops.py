@@ -405,7 +405,7 @@ def conv3_up2_dgrad(dz: Tensor, weight: Tensor, Cs: int, Cl: int, dscale: Option
                     stats_out: Optional[Tensor] = None, dz_blocked: bool = False) -> Tensor:
     """dz (N,D,H,W,Cout), weight (Cout, Cs+Cl, 3,3,3) -> (N,D/2,H/2,W/2,Cl): for every low voxel the sum over its 8
     children of the data gradient with respect to the nearest-x2 upsampled channels [Cs, Cs+Cl) -- computed at low
-    resolution with 64 pre-summed taps (csrc/conv_bf.hip: conv3_up2_dgrad)."""
+    resolution with 64 pre-summed taps (csrc/conv_up2.hip: conv3_up2_dgrad)."""
     lib = _lib.load()
     N, D, H, W, Cout = dz.shape      # (a channel-blocked dz keeps the dense tensor's nominal shape)
     terms = _TERMS[CONV_MODE]
@@ -535,7 +535,7 @@ class _SingleConvGCR(torch.autograd.Function):
                                                  _p(ystats), _stream()), "kmh_conv3d_first_layer_fwd")
         elif upsrc is not None:
             # x = cat(skip, up2(low)): the upsampled channels' 27 taps fall on 2x2x2 low-resolution voxels per output
-            # parity, so their contribution comes from `low` with 8 pre-summed taps (csrc/conv_bf.hip: conv3_up2) and
+            # parity, so their contribution comes from `low` with 8 pre-summed taps (csrc/conv_up2.hip: conv3_up2) and
             # the 27-tap kernel runs over the skip channels only, adding it in its epilogue
             skip, low = upsrc
             y = _up2_forward(skip, low, scale, shift, ascale, weight, N, D, H, W, skip.shape[-1], low.shape[-1], Cout,

@@ -23,13 +23,14 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=h
          "-Wno-unused-result", "-ffp-contract=fast"]
 
 
-# Per-file extra flags.  conv_wgrad.hip (= the weight-gradient section of conv_bf.hip as its own translation unit): LLVM's
-# "max-ILP" scheduling strategy -- the wave-specialised weight-gradient kernels (several waves per SIMD, no explicit scheduling
-# groups) run 2-4 % faster with it (profiles/r5z_llvm_sched_strategy_max_ilp.txt).  NOT for conv_bf.hip itself: under max-ILP
-# hipcc spills an in-flight destination of conv3_fwd_g_kernel<2>'s inline-asm loads (tools/scan_asm_inflight.py finds it).
+# Per-file extra flags.  conv_wgrad.hip (the split-operand weight gradient): LLVM's "max-ILP" scheduling strategy -- its
+# wave-specialised kernels (several waves per SIMD, no explicit scheduling groups) run 2-4 % faster with it
+# (profiles/r5z_llvm_sched_strategy_max_ilp.txt).  This is why the weight gradient is a translation unit of its own and NOT part
+# of conv_bf.hip: under max-ILP hipcc spills an in-flight destination of conv3_fwd_g_kernel<2>'s inline-asm loads
+# (tools/scan_asm_inflight.py finds it).
 # norm.hip: its streaming kernels keep more loads in flight under max-ILP (kmh_maxpool3d_bwd_lazy -25 %, kmh_maxpool3d_bwd_split
-# -7 %, GroupNorm kernels unchanged); headcom.hip, grids.hip and the fused decoder kernels get SLOWER with it (+18 % / +4 % / +5 %)
-# and keep the default (profiles/r5z_llvm_sched_strategy_max_ilp.txt).
+# -7 %, GroupNorm kernels unchanged); headcom.hip, grids.hip and the fused decoder kernels (conv_up2.hip) get SLOWER with it
+# (+18 % / +4 % / +5 %) and keep the default (profiles/r5z_llvm_sched_strategy_max_ilp.txt).
 _MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 FILE_FLAGS = {"conv_wgrad.hip": _MAX_ILP, "norm.hip": _MAX_ILP}
 
@@ -63,13 +64,15 @@ def _digest(path: str) -> str:
     with open(path, "rb") as f:
         text = f.read()
     h.update(text)
-    for inc in re.findall(rb'^#include "([^"]+)"', text, re.M):      # local includes (common.h; conv_wgrad.hip includes conv_bf.hip)
-        q = os.path.join(CSRC, inc.decode())
-        if os.path.exists(q):
-            with open(q, "rb") as f:
-                h.update(f.read())
-    with open(os.path.join(CSRC, "common.h"), "rb") as f:
-        h.update(f.read())
+    seen, todo = set(), [text]
+    while todo:                                        # every local header, headers' own includes too (conv_split.h -> common.h)
+        for inc in re.findall(rb'^#include "([^"]+)"', todo.pop(), re.M):
+            q = os.path.join(CSRC, inc.decode())
+            if q not in seen and os.path.exists(q):
+                seen.add(q)
+                with open(q, "rb") as f:
+                    todo.append(f.read())
+                h.update(todo[-1])
     return h.hexdigest()
 
 

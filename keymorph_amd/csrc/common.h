@@ -99,7 +99,7 @@ __device__ __forceinline__ int xcd_remap(int b, int total) {
 
 
 // ---------------------------------------------------------------------------------------------
-// Split-operand arithmetic shared by csrc/conv_bf.hip and csrc/headcom.hip.
+// Split-operand arithmetic shared by the convolution units (csrc/conv_bf.hip, conv_up2.hip, conv_wgrad.hip) and csrc/headcom.hip.
 // TERMS == 3: bf16 hi+mid+lo (24 bits), 6 products ("bf16x6").  TERMS == 2: FP16 hi+lo (22 bits: a 2^-23
 // representation error, the size of fp32's own rounding), 3 products ("f16x3") -- half the MFMA work.  fp16's narrow
 // exponent makes that accurate only if every operand tensor is first scaled by a power of two (exact) so that its

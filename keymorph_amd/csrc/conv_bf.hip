@@ -6,13 +6,13 @@
 // Both are fp32-class (5e-7 against fp64, like the fp32 MFMA); on CDNA4 the 16-bit MFMA rate is 16x the fp32 MFMA rate,
 // so this is 16/3 = 5.3x (16/6 = 2.7x) the fp32-MFMA roofline -- the 3xTF32 / BF16x9 idea on gfx950's 32x32x16 tile.
 //
-// Kernels in this file:
+// Kernels in this file, the forward / data-gradient family (fused decoder operator: conv_up2.hip, weight gradient: conv_wgrad.hip):
 //   conv3_fwd_bf_kernel<NT, TERMS, MR, ZP, ZT>   forward and data gradient (same kernel on tap-mirrored weights);
 //                                                 NT = 32-wide cout tiles per wave, MR = rows per wave, ZP = z-paired N
 //                                                 tile for Cout <= 16, ZT = output-plane pairs per brick
-//   conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW>   weight gradient, producer / consumer waves (the default)
-//   conv3_wgrad_bf_kernel<NT, TERMS>             weight gradient, single-role (bf16x6, odd channel counts, huge volumes)
-//   pack_weight_bf_kernel, wgrad_bf_reduce_kernel, first_layer_fold_kernel
+//   conv3_fwd_g_kernel<NT, ZP, POOL>             the same on big launches: persistent workgroups, LDS-DMA staging, eight waves
+//   conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, AMP> one wave per SIMD, hand-counted waits (audited: keymorph_amd/isa_audit.py)
+//   pack_weight_bf_kernel<TERMS>
 //
 // Forward: same brick / wave decomposition as conv.hip (32x8x2 output voxels per 4-wave workgroup, 4 rows x NT
 // channel tiles per wave), but:
@@ -27,28 +27,13 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include "common.h"
+#include "conv_split.h"
 #include <type_traits>
 
 namespace {
 
-typedef kmh_f32x16 f32x16;
-typedef kmh_bf16x8 bf16x8;     // 8 x 16-bit fragment (bf16 or fp16 bits; see common.h for the split arithmetic)
-}  // namespace (the typedefs every part of this file uses)
-
-// Two translation units share this file: csrc/conv_wgrad.hip defines KMH_TU_WGRAD and compiles ONLY the weight-gradient section
-// (with LLVM's max-ILP scheduling strategy, keymorph_amd/build.py: its wave-specialised kernels run 2-4 % faster with it),
-// this file compiles everything else with the default strategy -- under max-ILP hipcc spills an in-flight destination of the
-// inline-asm loads of conv3_fwd_g_kernel<2> right behind its load (found by tools/scan_asm_inflight.py).
-#ifndef KMH_TU_WGRAD
-#define KMH_TU_WGRAD 0
-#endif
-#if !KMH_TU_WGRAD
-namespace {
-
 constexpr int TX = 32, TZ = 2;
 constexpr int HX = TX + 2, HZ = TZ + 2;
-constexpr int KC = 8;              // channels per LDS refill (= half of the MFMA K)
 // MR = output rows (M-tiles) per wave: brick height TY = 2*MR.  MR = 4: 32x8x2 brick, 1360-voxel halo;
 // MR = 2: 32x4x2 brick, 816-voxel halo -> 39 KB of LDS (TERMS = 3) and 64 accumulator registers, i.e. 3-4
 // resident workgroups per CU instead of 2.
@@ -443,8 +428,6 @@ constexpr int G_OFF_BYTES = G_NLD * G_TPB * 4;                         // the DM
 constexpr int G_IMG_BYTES = 8 * 32 * 64 * 4;                           // fragment images (65 280 B) / epilogue tiles (8 x 8 KB)
 constexpr int G_LDS_BYTES = G_SLOTS * 16 + G_IMG_BYTES + G_OFF_BYTES;  // 65 280 + 65 536 + 16 384 = 147 200
 
-typedef __attribute__((address_space(3))) void* kmh_lds_ptr;
-typedef const __attribute__((address_space(1))) void* kmh_glb_ptr;
 
 // POOL (NT = 1, not z-paired: 16 < Cout <= 32): the epilogue applies MaxPool3d(2) (floor mode, ATen's first-max rule)
 // to the brick it just computed -- a 32 x 8 x 4 brick at an even origin holds 16 x 4 x 2 whole windows -- and writes
@@ -1645,7 +1628,8 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
 }
 
 }  // namespace
-// use_amp per call (common.h): the state is the calling thread's, set for the duration of ONE entry-point call.
+// use_amp per call (common.h): the state is the calling thread's, set for the duration of ONE entry-point call.  Defined here for
+// the library: called by KmhAmpCall and the launchers of this file, conv_up2.hip, conv_wgrad.hip and headcom.hip.
 static thread_local bool t_amp_call = false;
 bool kmh_amp_enabled() { return t_amp_call; }
 bool kmh_amp_call_begin(int* terms) {
@@ -1655,1060 +1639,7 @@ bool kmh_amp_call_begin(int* terms) {
   return prev;
 }
 void kmh_amp_call_end(bool prev) { t_amp_call = prev; }
-namespace {
-static inline int cout_pad(int Cout) { return Cout > 64 ? (Cout + 127) & ~127 : (Cout + 63) & ~63; }
-static inline bool use_zpair(int Cout) { return Cout <= 16; }
-
-// =============================================================================================
-// 3x3x3 convolution over a NEAREST-UPSAMPLED (x2) tensor without the upsampled tensor: the decoder's first convolution
-// reads cat(skip, up2(low)); for the `low` channels the 27 taps of an output voxel of parity p = (pz, py, px) fall on
-// only 2 x 2 x 2 low-resolution voxels (per axis: parity 0 -> offsets {-1: tap -1; 0: taps 0, +1}, parity 1 ->
-// {0: taps -1, 0; +1: tap +1}), so with the taps of one low voxel summed beforehand (pack_weight_up_kernel) every
-// output costs 8 multiply-adds per channel instead of 27.  Zero padding is consistent: padded positions -1 / 2L map to
-// the low voxels -1 / L, which are outside too.  The kernel writes the low channels' contribution (descaled, no bias
-// / ReLU); kmh_conv3d_fwd_bf over the skip channels then adds it in its epilogue (`addend`).
-// Workgroup = 32 x 4 x 1 low voxels (-> 64 x 8 x 2 outputs), 8 waves: wave = ((pz, py), 32-cout tile) and holds both
-// px parities of 4 rows (8 accumulator tiles); K = 16 = (low tap jx = lane half) x 8 channels; 4 tap pairs per parity.
-// Chunks are double-buffered in LDS: the loads of chunk c+1 are in flight during the MFMAs of chunk c.
-constexpr int UX = 32, UY = 4;
-constexpr int UHX = UX + 2, UHY = UY + 2, UPL = UHX * UHY * 3;      // 612 halo voxels of the low tensor
-constexpr int UP_TPB = 512;
-constexpr int UP_NST = 32;                                          // 8 parities x 4 tap pairs
-
-template <int TERMS>
-__global__ __launch_bounds__(256) void pack_weight_up_kernel(const float* __restrict__ w, __bf16* __restrict__ out,
-                                                             int Cout, int Ctot, int cofs, int Cl, int CoutP, int nchunk,
-                                                             const float* __restrict__ wscale) {
-  const long long total = (long long)nchunk * UP_NST * 2 * CoutP * 8;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    const int c = (int)(e & 7);
-    long long r = e >> 3;
-    const int col = (int)(r % CoutP); r /= CoutP;
-    const int h = (int)(r & 1); r >>= 1;
-    const int su = (int)(r % UP_NST);
-    const int chunk = (int)(r / UP_NST);
-    const int ci = chunk * 8 + c, p = su >> 2, st = su & 3;
-    const int par[3] = {p >> 2, (p >> 1) & 1, p & 1}, j[3] = {st >> 1, st & 1, h};
-    int lo[3], hi[3];                                   // tap range (0..2) of each axis that lands on low offset j
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = par[a] == 0 ? (j[a] == 0 ? 0 : 1) : (j[a] == 0 ? 0 : 2);
-      hi[a] = par[a] == 0 ? (j[a] == 0 ? 0 : 2) : (j[a] == 0 ? 1 : 2);
-    }
-    float v = 0.f;
-    if (ci < Cl && col < Cout) {
-      const float* wr = w + ((long long)col * Ctot + cofs + ci) * 27;
-      for (int kz = lo[0]; kz <= hi[0]; ++kz)
-        for (int ky = lo[1]; ky <= hi[1]; ++ky)
-          for (int kx = lo[2]; kx <= hi[2]; ++kx) v += wr[kz * 9 + ky * 3 + kx];
-    }
-    float rem = wscale ? v * wscale[0] : v;
-#pragma unroll
-    for (int t = 0; t < TERMS; ++t) {
-      float back;
-      const unsigned short hb = to16<TERMS>(rem, back);
-      reinterpret_cast<unsigned short*>(out)[((((long long)chunk * TERMS + t) * UP_NST + su) * 2 + h) * CoutP * 8 +
-                                             (long long)col * 8 + c] = hb;
-      rem -= back;
-    }
-  }
-}
-
-template <int TERMS, bool AMP = false>
-__global__ __launch_bounds__(UP_TPB, 2) void conv3_up2_fwd_kernel(
-    const float* __restrict__ xl, const float* __restrict__ scale, const float* __restrict__ shift, int Ctot, int cofs,
-    const bf16x8* __restrict__ wp, float* __restrict__ y, int Dl, int Hl, int Wl, int Cl, int Cout, int CoutP,
-    int tiles_x, int tiles_y, const float* __restrict__ ascale, const float* __restrict__ wscale) {
-  __shared__ bf16x8 sIn[2][TERMS][UPL];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const int n = blockIdx.z;
-  const int ncog = (Cout + 63) / 64;
-  const int item = xcd_remap(blockIdx.x, gridDim.x);
-  const int cog = item % ncog, brick = item / ncog;
-  const int bx = brick % tiles_x, by = (brick / tiles_x) % tiles_y, zl = brick / (tiles_x * tiles_y);
-  const int x0 = bx * UX, y0 = by * UY;
-  const int pz = (wv >> 1) & 1, py = wv & 1, nt = wv >> 2;
-  const int co = cog * 64 + 32 * nt + li;
-
-  f32x16 acc[2][UY];
-#pragma unroll
-  for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-    for (int m = 0; m < UY; ++m)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[pl][m][r] = 0.f;
-  const float sA = ascale ? ascale[0] : 1.f;
-  const float desc = (ascale ? ascale[1] : 1.f) * (wscale ? wscale[1] : 1.f);
-  const int nchunk = Cl / KC;
-
-  // staging descriptors: up to 2 halo voxels per thread, the same for every chunk
-  constexpr int NV = (UPL + UP_TPB - 1) / UP_TPB;      // 2
-  int sv_rel[NV];
-  bool sv_in[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = tid + i * UP_TPB;
-    const int lx = v % UHX, ly = (v / UHX) % UHY, lz = v / (UHX * UHY);
-    const int gx = x0 + lx - 1, gy = y0 + ly - 1, gz = zl + lz - 1;
-    sv_in[i] = (v < UPL) && ((unsigned)gx < (unsigned)Wl) && ((unsigned)gy < (unsigned)Hl) && ((unsigned)gz < (unsigned)Dl);
-    sv_rel[i] = sv_in[i] ? ((gz * Hl + gy) * Wl + gx) * Cl : 0;
-  }
-  const float* xn = xl + (long long)n * Dl * Hl * Wl * Cl;
-  float pv[NV][8];
-  auto fetch = [&](int ch) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const float* p = xn + sv_rel[i] + ch * KC;       // a valid address also for padding voxels (zeroed at commit)
-      const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-      pv[i][0] = a.x; pv[i][1] = a.y; pv[i][2] = a.z; pv[i][3] = a.w;
-      pv[i][4] = b.x; pv[i][5] = b.y; pv[i][6] = b.z; pv[i][7] = b.w;
-    }
-  };
-  auto commit = [&](int ch, int stage) {
-    float csc[8], csh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      csc[j] = (scale ? scale[(long long)n * Ctot + cofs + ch * KC + j] : 1.f) * sA;
-      csh[j] = (scale ? shift[(long long)n * Ctot + cofs + ch * KC + j] : 0.f) * sA;
-    }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = tid + i * UP_TPB;
-      if (v < UPL) {
-        float val[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) val[j] = sv_in[i] ? pv[i][j] * csc[j] + csh[j] : 0.f;   // zero padding AFTER the norm
-        bf16x8 parts[TERMS];
-        split8<TERMS>(val, parts);
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) sIn[stage][t][v] = parts[t];
-      }
-    }
-  };
-
-  const int wbase = (pz * UHY + py) * UHX + li + lh;   // + (jz * UHY + jy + m) * UHX + px: this lane's A voxel
-  const int subase = (pz * 4 + py * 2) * 4;            // first step of parity (pz, py, 0)
-  fetch(0);
-  commit(0, 0);
-  __syncthreads();
-  for (int ch = 0; ch < nchunk; ++ch) {
-    const int stage = ch & 1;
-    if (ch + 1 < nchunk) fetch(ch + 1);
-    const bf16x8* wc = wp + (long long)ch * TERMS * UP_NST * 2 * CoutP + lh * CoutP + co;
-    constexpr int BD = 4;                               // B ring depth over the wave's 8 (px, tap pair) steps
-    bf16x8 bq[BD][TERMS];
-#pragma unroll
-    for (int d = 0; d < BD; ++d)
-#pragma unroll
-      for (int q = 0; q < TERMS; ++q)
-        bq[d][q] = wc[((long long)(q * UP_NST + subase + d)) * 2 * CoutP];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {                       // k = px * 4 + tap pair
-      const int pl = k >> 2, st = k & 3;
-      bf16x8 b[TERMS];
-#pragma unroll
-      for (int q = 0; q < TERMS; ++q) b[q] = bq[k % BD][q];
-      if (k + BD < 8) {
-#pragma unroll
-        for (int q = 0; q < TERMS; ++q)
-          bq[k % BD][q] = wc[((long long)(q * UP_NST + subase + k + BD)) * 2 * CoutP];
-      }
-      const int off = wbase + ((st >> 1) * UHY + (st & 1)) * UHX + pl;
-#pragma unroll
-      for (int m = 0; m < UY; ++m) {
-        bf16x8 a[TERMS];
-#pragma unroll
-        for (int q = 0; q < TERMS; ++q) a[q] = sIn[stage][q][off + m * UHX];
-        if (TERMS == 3) {
-          acc[pl][m] = mfma16<TERMS>(a[2], b[0], acc[pl][m]);
-          acc[pl][m] = mfma16<TERMS>(a[1], b[1], acc[pl][m]);
-          acc[pl][m] = mfma16<TERMS>(a[0], b[2], acc[pl][m]);
-        }
-        if constexpr (!AMP) {
-          acc[pl][m] = mfma16<TERMS>(a[1], b[0], acc[pl][m]);
-          acc[pl][m] = mfma16<TERMS>(a[0], b[1], acc[pl][m]);
-        }
-        acc[pl][m] = mfma16<TERMS>(a[0], b[0], acc[pl][m]);
-      }
-    }
-    if (ch + 1 < nchunk) commit(ch + 1, stage ^ 1);    // the other stage: its readers finished a chunk ago
-    __syncthreads();
-  }
-  // epilogue: one channel per lane in the accumulators -> 16 bytes per lane after a per-wave transposition through the
-  // (now idle) fragment images: 32 store instructions per lane instead of 128 (the store path is issue-bound, see
-  // conv3_fwd_g_kernel).  Cout % 4 == 0 is guaranteed by the caller (upcat_conv_ok: channels % 8 == 0).
-  const int D = 2 * Dl, H = 2 * Hl, W = 2 * Wl;
-  const int gz = 2 * zl + pz;
-  float* tile = reinterpret_cast<float*>(&sIn[0][0][0]) + wv * (32 * 32);
-  const int c4 = lane & 7, vx = lane >> 3;
-  const int cq = cog * 64 + 32 * nt + 4 * c4;
-  const bool cq_ok = cq < Cout;
-#pragma unroll
-  for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-    for (int m = 0; m < UY; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tile[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = acc[pl][m][r] * desc;
-      const bool row_ok = cq_ok && y0 + m < Hl;
-      const int gy = 2 * (y0 + m) + py;
-      float* yp = y + ((((long long)n * D + gz) * H + gy) * W) * Cout + cq;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int xx = vx + 8 * k, xlw = x0 + xx;
-        const float4 v = *reinterpret_cast<const float4*>(tile + xx * 32 + 4 * c4);
-        if (row_ok && xlw < Wl) *reinterpret_cast<float4*>(yp + (long long)(2 * xlw + pl) * Cout) = v;
-      }
-    }
-}
-
-// ---- data gradient of the same operator: ds[m][ci] = sum over the 4 x 4 x 4 high-resolution positions u = 2m + t,
-// t in {-1, 0, 1, 2} per axis, of Wt[t][co][ci] dz[u][co] -- the sum over a low voxel's 8 children of the gradient with
-// respect to the upsampled tensor, computed at LOW resolution with 64 (pre-summed) taps instead of 8 x 27.  Per axis
-// t <-> (output parity p, low offset index j) of the forward: -1 <-> (1, 1), 0 <-> (0, 1), 1 <-> (1, 0), 2 <-> (0, 0).
-// Workgroup = 16 x 4 x 1 low voxels; LDS = the 34 x 10 x 4 high-resolution halo of dz (8 channels, hi + lo);
-// wave = 32-channel tile of ci; K = 16 = (x tap pair) x 8 dz channels; 32 steps per chunk.
-constexpr int DUX = 16, DUY = 4;                                           // low brick of the data gradient: 16 x 4 x 1
-constexpr int DHX = 2 * DUX + 2, DHY = 2 * DUY + 2, DPL = DHX * DHY * 4;   // 34 x 10 x 4 = 1360 halo voxels of dz
-constexpr int DUP_NST = 32;                                                // (tz, ty) x (x tap pair)
-constexpr int DUP_TPB = 256;                                               // 4 waves = the 4 channel tiles of 128 ci
-
-template <int TERMS>
-__global__ __launch_bounds__(256) void pack_weight_upt_kernel(const float* __restrict__ w, __bf16* __restrict__ out,
-                                                              int Cout, int Ctot, int cofs, int Cl, int CiP, int nchunk,
-                                                              const float* __restrict__ wscale) {
-  const long long total = (long long)nchunk * DUP_NST * 2 * CiP * 8;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    const int c = (int)(e & 7);                        // dz channel inside the chunk
-    long long r = e >> 3;
-    const int col = (int)(r % CiP); r /= CiP;          // input (low) channel
-    const int h = (int)(r & 1); r >>= 1;
-    const int s = (int)(r % DUP_NST);
-    const int chunk = (int)(r / DUP_NST);
-    const int co = chunk * 8 + c;
-    const int idx[3] = {s >> 3, (s >> 1) & 3, 2 * (s & 1) + h};     // t + 1 per axis (z, y, x)
-    int lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int par = (idx[a] + 1) & 1, j = idx[a] <= 1 ? 1 : 0;
-      lo[a] = par == 0 ? (j == 0 ? 0 : 1) : (j == 0 ? 0 : 2);
-      hi[a] = par == 0 ? (j == 0 ? 0 : 2) : (j == 0 ? 1 : 2);
-    }
-    float v = 0.f;
-    if (co < Cout && col < Cl) {
-      const float* wr = w + ((long long)co * Ctot + cofs + col) * 27;
-      for (int kz = lo[0]; kz <= hi[0]; ++kz)
-        for (int ky = lo[1]; ky <= hi[1]; ++ky)
-          for (int kx = lo[2]; kx <= hi[2]; ++kx) v += wr[kz * 9 + ky * 3 + kx];
-    }
-    float rem = wscale ? v * wscale[0] : v;
-#pragma unroll
-    for (int t = 0; t < TERMS; ++t) {
-      float back;
-      const unsigned short hb = to16<TERMS>(rem, back);
-      reinterpret_cast<unsigned short*>(out)[((((long long)chunk * TERMS + t) * DUP_NST + s) * 2 + h) * CiP * 8 +
-                                             (long long)col * 8 + c] = hb;
-      rem -= back;
-    }
-  }
-}
-
-template <int TERMS, bool AMP = false>
-__global__ __launch_bounds__(DUP_TPB, TERMS == 2 ? 2 : 3) void conv3_up2_dgrad_kernel(
-    const float* __restrict__ dz /* (N,2Dl,2Hl,2Wl,Cout) */, const bf16x8* __restrict__ wp,
-    float* __restrict__ ds /* (N,Dl,Hl,Wl,Cl) */, int Dl, int Hl, int Wl, int Cl, int CiP, int Cout, int tiles_x,
-    int tiles_y, const float* __restrict__ dscale, const float* __restrict__ wscale,
-    double* __restrict__ stats_partial /* (N, bricks, Cl, 2) | NULL: per-brick (sum ds, sum ds^2) of every channel */,
-    int in_blocked /* dz is channel-blocked (N, Cout/8, 2Dl, 2Hl, 2Wl, 8): a chunk's 32 bytes per voxel are contiguous ACROSS
-                      voxels, whole lines per request instead of 32-byte pieces of 64-byte sectors */) {
-  // Workgroup = 16 x 4 x 1 low voxels = two M tiles of (16 x, 2 y); wave = one 32-channel tile of ci, both M tiles.
-  // 43.5 KB of LDS; two (f16x3, prefetching: 224 registers) or three (bf16x6) workgroups per CU, whose staging and MFMA
-  // phases overlap.
-  __shared__ bf16x8 sIn[TERMS][DPL];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const int n = blockIdx.z;
-  const int ncig = (Cl + 127) / 128;
-  const int item = xcd_remap(blockIdx.x, gridDim.x);
-  const int cig = item % ncig, brick = item / ncig;
-  const int bx = brick % tiles_x, by = (brick / tiles_x) % tiles_y, zl = brick / (tiles_x * tiles_y);
-  const int x0 = bx * DUX, y0 = by * DUY;
-  const int ci = cig * 128 + 32 * wv + li;
-  const int D = 2 * Dl, H = 2 * Hl, W = 2 * Wl;
-
-  f32x16 acc[2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-  const float sD = dscale ? dscale[0] : 1.f;
-  const float desc = (dscale ? dscale[1] : 1.f) * (wscale ? wscale[1] : 1.f);
-  const int nchunk = (Cout + KC - 1) / KC;
-  const float* dn = dz + (long long)n * D * H * W * Cout;
-  constexpr int NV = (DPL + DUP_TPB - 1) / DUP_TPB;    // 6
-  // row li of an M tile = low voxel (x = li & 15, y = 2 mt + (li >> 4)); its halo origin is (2 y, 2 x)
-  const int abase = (2 * (li >> 4)) * DHX + 2 * (li & 15) + lh;
-
-  // the next chunk's halo is fetched into registers under this chunk's MFMAs (staging it at the top of its own chunk left
-  // an HBM round trip exposed per chunk and workgroup)
-  float4 pre[NV][2];
-  auto fetch = [&](int ch) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = tid + i * DUP_TPB;
-      pre[i][0] = pre[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (v < DPL) {
-        const int lx = v % DHX, ly = (v / DHX) % DHY, lz = v / (DHX * DHY);
-        const int gx = 2 * x0 - 1 + lx, gy = 2 * y0 - 1 + ly, gz = 2 * zl - 1 + lz;
-        if ((unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H && (unsigned)gz < (unsigned)D) {
-          const long long vox = ((long long)gz * H + gy) * W + gx;
-          const float* p = in_blocked ? dn + ((long long)ch * D * H * W + vox) * KC : dn + vox * Cout + ch * KC;
-          if ((Cout & 3) == 0) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-              if (ch * KC + 4 * q < Cout) pre[i][q] = *reinterpret_cast<const float4*>(p + 4 * q);
-          } else {
-            float t8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (ch * KC + j < Cout) t8[j] = p[j];
-            pre[i][0] = make_float4(t8[0], t8[1], t8[2], t8[3]);
-            pre[i][1] = make_float4(t8[4], t8[5], t8[6], t8[7]);
-          }
-        }
-      }
-    }
-  };
-  constexpr bool PF = TERMS == 2;                       // (the three-term variant has no registers to spare: it fetches in place)
-  if (PF) fetch(0);
-  for (int ch = 0; ch < nchunk; ++ch) {
-    __syncthreads();                                    // the previous chunk's readers are done
-    if (!PF) fetch(ch);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = tid + i * DUP_TPB;
-      if (v < DPL) {
-        const float val[8] = {pre[i][0].x * sD, pre[i][0].y * sD, pre[i][0].z * sD, pre[i][0].w * sD,
-                              pre[i][1].x * sD, pre[i][1].y * sD, pre[i][1].z * sD, pre[i][1].w * sD};
-        bf16x8 parts[TERMS];
-        split8<TERMS>(val, parts);
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) sIn[t][v] = parts[t];
-      }
-    }
-    __syncthreads();
-    if (PF && ch + 1 < nchunk) fetch(ch + 1);
-    const bf16x8* wc = wp + (long long)ch * TERMS * DUP_NST * 2 * CiP + lh * CiP + ci;
-    constexpr int BD = 4;
-    bf16x8 bq[BD][TERMS];
-#pragma unroll
-    for (int d = 0; d < BD; ++d)
-#pragma unroll
-      for (int q = 0; q < TERMS; ++q) bq[d][q] = wc[((long long)(q * DUP_NST + d)) * 2 * CiP];
-#pragma unroll 1
-    for (int tz = 0; tz < 4; ++tz) {                    // 8 steps per z tap: the ring (depth 4) index stays constant
-#pragma unroll
-      for (int s8 = 0; s8 < 8; ++s8) {
-        const int s = tz * 8 + s8;
-        bf16x8 b[TERMS];
-#pragma unroll
-        for (int q = 0; q < TERMS; ++q) b[q] = bq[s8 % BD][q];
-        if (s + BD < DUP_NST) {
-#pragma unroll
-          for (int q = 0; q < TERMS; ++q) bq[s8 % BD][q] = wc[((long long)(q * DUP_NST + s + BD)) * 2 * CiP];
-        }
-        const int off = abase + (tz * DHY + (s8 >> 1)) * DHX + 2 * (s8 & 1);
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          bf16x8 a[TERMS];
-#pragma unroll
-          for (int q = 0; q < TERMS; ++q) a[q] = sIn[q][off + 4 * m * DHX];
-          if (TERMS == 3) {
-            acc[m] = mfma16<TERMS>(a[2], b[0], acc[m]);
-            acc[m] = mfma16<TERMS>(a[1], b[1], acc[m]);
-            acc[m] = mfma16<TERMS>(a[0], b[2], acc[m]);
-          }
-          if constexpr (!AMP) {
-            acc[m] = mfma16<TERMS>(a[1], b[0], acc[m]);
-            acc[m] = mfma16<TERMS>(a[0], b[1], acc[m]);
-          }
-          acc[m] = mfma16<TERMS>(a[0], b[0], acc[m]);
-        }
-      }
-    }
-  }
-  if (ci >= Cl) return;
-  float s1 = 0.f, s2 = 0.f;                             // <= 32 values per lane: fp32, then fp64 per brick
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;  // row of the M tile
-      const int gx = x0 + (row & 15), gy = y0 + 2 * m + (row >> 4);
-      if (gx < Wl && gy < Hl) {
-        const float v = acc[m][r] * desc;
-        ds[((((long long)n * Dl + zl) * Hl + gy) * Wl + gx) * Cl + ci] = v;
-        s1 += v;
-        s2 = fmaf(v, v, s2);
-      }
-    }
-  }
-  if (stats_partial) {                                  // the consumer's GroupNorm backward wants sum ds per channel
-    double d1 = (double)s1, d2 = (double)s2;
-    d1 += __shfl_xor(d1, 32, 64);
-    d2 += __shfl_xor(d2, 32, 64);
-    if (lh == 0) {
-      double* o = stats_partial + (((long long)n * gridDim.x / ncig + brick) * Cl + ci) * 2;
-      o[0] = d1; o[1] = d2;
-    }
-  }
-}
-
-// ---- weight gradient of the same operator: C_n (Cl x J) = A_n^T B_n over the low-resolution voxels, A = the normalised
-// low tensor (V x Cl), B = the box sums of dz (V x J, J = 27 Cout, norm.hip: up2_boxsum_kernel).  Both operands have the
-// reduction index slowest, so both are transposed while they are staged (voxel pairs packed into 32-bit LDS words, like
-// the 27-tap weight gradient's images).  Workgroup = 128 x 128 tile of C over one K slab, 32 voxels per step; wave = 64 x 64.
-// Bound: a CU streams in ~10 B / cycle (256 CUs: 5.1 TB/s), this tile loads (128 + 128) x 4 B per 2 x 128 x 128 multiply-adds.  A
-// 128 x 256 tile on 8 waves (1.33x the intensity) needs 176 registers = ONE workgroup per CU and is no faster (2.97 vs 2.86 ms).
-constexpr int GK = 32;                        // voxels per staging step (64: two workgroups per CU, 5 % slower)
-constexpr int GPITCH = GK * 2 + 16;           // bytes per LDS row (32 x 2 B + pad: 5 x 16 B, conflict-free b128 reads)
-template <int TERMS, bool AMP = false>
-__global__ __launch_bounds__(256, 3) void up2_wgrad_gemm_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                                float* __restrict__ Cp, int V, int Cl, int J, int kslab,
-                                                                int ntn, int ntm, const float* __restrict__ ascale,
-                                                                const float* __restrict__ bscale,
-                                                                const float* __restrict__ a_scale /* (N, Cl) | NULL */,
-                                                                const float* __restrict__ a_shift, int xcd) {
-  __shared__ __attribute__((aligned(16))) unsigned char sA[TERMS][128 * GPITCH];
-  __shared__ __attribute__((aligned(16))) unsigned char sB[TERMS][128 * GPITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const int n = blockIdx.z;
-  // The column tiles of one (row tile, K slab) read the SAME rows of A.  Dealt round-robin over the XCDs, every XCD's L2 fetched
-  // them for itself: 14.75 GB per launch for 7.25 GB of G at 64^3 x 128 x 1728 (PMC), and the launch ran at the HBM rate of THAT.
-  // With one contiguous item range per XCD (xcd_remap) the tiles of a slab sit on one XCD and walk the slab together: A comes
-  // from HBM once.  (KEYMORPH_UP2_GEMM_NO_XCD=1: the round-robin order, for A/B runs.)
-  int item = xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-  const int tn = item % ntn; item /= ntn;
-  const int tm = item % ntm;
-  const int slab = item / ntm;
-  const int m0 = tm * 128, n0 = tn * 128;
-  const int wm = wv & 1, wn = wv >> 1;
-  const float sa = ascale ? ascale[0] : 1.f, sb = bscale ? bscale[0] : 1.f;
-  const float desc = (ascale ? ascale[1] : 1.f) * (bscale ? bscale[1] : 1.f);
-  const float* An = A + (long long)n * V * Cl;
-  const float* Bn = B + (long long)n * V * J;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int k_beg = slab * kslab;
-  int k_end = k_beg + kslab;
-  if (k_end > V) k_end = V;
-  // staging items: (voxel pair kp, column quad cq) -> 2 float4 loads, 4 packed words per term.  Eight consecutive lanes take the
-  // eight quads of ONE 128-byte line of a voxel row (round 4; four lanes / 64-byte pieces before: 2.9 TB/s -> see DESIGN.md)
-  constexpr int NKP = GK / 2, NIT = GK / 16;   // voxel pairs per step, staging items per thread
-  float4 pa[NIT][2], pb[NIT][2];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int e = tid + i * 256, cq = (e & 7) + 8 * (e / (8 * NKP)), kp = (e >> 3) & (NKP - 1);   // lanes: 8 quads (one line) x 8 voxel pairs
-      const int k = k0 + 2 * kp;
-      const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int ca = m0 + 4 * cq, cb = n0 + 4 * cq;
-      pa[i][0] = (k < k_end && ca < Cl) ? *reinterpret_cast<const float4*>(An + (long long)k * Cl + ca) : z4;
-      pa[i][1] = (k + 1 < k_end && ca < Cl) ? *reinterpret_cast<const float4*>(An + (long long)(k + 1) * Cl + ca) : z4;
-      pb[i][0] = (k < k_end && cb < J) ? *reinterpret_cast<const float4*>(Bn + (long long)k * J + cb) : z4;
-      pb[i][1] = (k + 1 < k_end && cb < J) ? *reinterpret_cast<const float4*>(Bn + (long long)(k + 1) * J + cb) : z4;
-    }
-  };
-  // GroupNorm's per-(sample, channel) affine of the A operand, applied while it is staged (a_scale != NULL): the caller
-  // hands over the RAW low tensor and no normalised copy of it is written and read back
-  float4 csc[NIT], csh[NIT];
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    const int e = tid + i * 256, cq = (e & 7) + 8 * (e / (8 * NKP)), ca = m0 + 4 * cq;
-    csc[i] = make_float4(1.f, 1.f, 1.f, 1.f);
-    csh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a_scale && ca < Cl) {
-      csc[i] = *reinterpret_cast<const float4*>(a_scale + (long long)n * Cl + ca);
-      csh[i] = *reinterpret_cast<const float4*>(a_shift + (long long)n * Cl + ca);
-    }
-  }
-  auto commit = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int e = tid + i * 256, cq = (e & 7) + 8 * (e / (8 * NKP)), kp = (e >> 3) & (NKP - 1);   // (2-way LDS write conflicts at most)
-      const bool v0 = k0 + 2 * kp < k_end, v1 = k0 + 2 * kp + 1 < k_end;     // rows past the slab stay zero (no shift)
-      const float a0[4] = {v0 ? fmaf(pa[i][0].x, csc[i].x, csh[i].x) : 0.f, v0 ? fmaf(pa[i][0].y, csc[i].y, csh[i].y) : 0.f,
-                           v0 ? fmaf(pa[i][0].z, csc[i].z, csh[i].z) : 0.f, v0 ? fmaf(pa[i][0].w, csc[i].w, csh[i].w) : 0.f};
-      const float a1[4] = {v1 ? fmaf(pa[i][1].x, csc[i].x, csh[i].x) : 0.f, v1 ? fmaf(pa[i][1].y, csc[i].y, csh[i].y) : 0.f,
-                           v1 ? fmaf(pa[i][1].z, csc[i].z, csh[i].z) : 0.f, v1 ? fmaf(pa[i][1].w, csc[i].w, csh[i].w) : 0.f};
-      const float b0[4] = {pb[i][0].x, pb[i][0].y, pb[i][0].z, pb[i][0].w}, b1[4] = {pb[i][1].x, pb[i][1].y, pb[i][1].z, pb[i][1].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned w[TERMS];
-        split_pair<TERMS>(a0[j] * sa, a1[j] * sa, w);
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) *reinterpret_cast<unsigned*>(sA[t] + (4 * cq + j) * GPITCH + 4 * kp) = w[t];
-        split_pair<TERMS>(b0[j] * sb, b1[j] * sb, w);
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) *reinterpret_cast<unsigned*>(sB[t] + (4 * cq + j) * GPITCH + 4 * kp) = w[t];
-      }
-    }
-  };
-  fetch(k_beg);
-  for (int k0 = k_beg; k0 < k_end; k0 += GK) {
-    __syncthreads();                           // the previous step's fragment reads are done
-    commit(k0);
-    __syncthreads();
-    if (k0 + GK < k_end) fetch(k0 + GK);       // in flight during the MFMAs
-#pragma unroll
-    for (int s = 0; s < GK / 16; ++s) {
-      bf16x8 a[2][TERMS], b[2][TERMS];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) {
-          a[i][t] = *reinterpret_cast<const bf16x8*>(sA[t] + (64 * wm + 32 * i + li) * GPITCH + (16 * s + 8 * lh) * 2);
-          b[i][t] = *reinterpret_cast<const bf16x8*>(sB[t] + (64 * wn + 32 * i + li) * GPITCH + (16 * s + 8 * lh) * 2);
-        }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (TERMS == 3) {
-            acc[i][j] = mfma16<TERMS>(a[i][2], b[j][0], acc[i][j]);
-            acc[i][j] = mfma16<TERMS>(a[i][1], b[j][1], acc[i][j]);
-            acc[i][j] = mfma16<TERMS>(a[i][0], b[j][2], acc[i][j]);
-          }
-          if constexpr (!AMP) {
-            acc[i][j] = mfma16<TERMS>(a[i][1], b[j][0], acc[i][j]);
-            acc[i][j] = mfma16<TERMS>(a[i][0], b[j][1], acc[i][j]);
-          }
-          acc[i][j] = mfma16<TERMS>(a[i][0], b[j][0], acc[i][j]);
-        }
-    }
-  }
-  const int nslab = gridDim.x / (ntn * ntm);
-  float* Cn = Cp + ((long long)n * nslab + slab) * Cl * J;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + 64 * wn + 32 * j + li;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < Cl && col < J) Cn[(long long)row * J + col] = acc[i][j][r] * desc;
-      }
-    }
-}
-
-// C (N, Cl, J) = sum over the K slabs, fixed order, fp64
-__global__ __launch_bounds__(256) void up2_wgrad_reduce_kernel(const float* __restrict__ Cp, int nslab, long long per,
-                                                               float* __restrict__ C) {
-  const int n = blockIdx.y;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
-    double s = 0;
-    for (int k = 0; k < nslab; ++k) s += Cp[((long long)n * nslab + k) * per + e];
-    C[(long long)n * per + e] = (float)s;
-  }
-}
-
-
-// ---- round 5: the same product with the box sums formed ON THE FLY (the 27 box-sum tensors -- 4.5 GB written by up2_boxsum and
-// read back by the product above, which ran at the HBM rate of that -- never exist).  Reference: autograd of the decoder's
-// interpolate(nearest x2) + cat + SingleConv (keymorph/unet3d/buildingblocks.py:471-475, :46-78).
-// One K step = a 4 x 4 x 2 tile of low voxels (32).  Workgroup = 128 rows of Cl x (27 taps x 8 couts = 216 columns, 7 MFMA
-// tiles) over a slab of K tiles; wave = one 32-row tile x all 7 column tiles (112 accumulators).  Per step: the tile's
-// 10 x 10 x 6 window of dz (8 channels: 19 KB, prefetched during the previous step's MFMAs) goes to LDS as fp32, 192 threads form
-// the 32 x 27 x 8 box sums from it with the additions of up2_boxsum_tiled_kernel in the same order (bit-identical sums), scale
-// them by S_dz / 8, split them and write the B image; the A image (raw low tensor with GroupNorm's affine) as in the kernel above.
-// Two workgroups per CU (76.5 KB of LDS each): one's box sums (VALU) run beside the other's MFMAs.
-// Measured (profiles/r5r_up2_wgrad_fold.txt, N = 4, dz channel-blocked): 128 -> 64 at 128^3: 5.12 -> 2.95 ms, 256 -> 128 at 64^3:
-// 1.91 -> 1.40 ms.  With the box sums AND the MFMAs compiled out a launch still takes 2.08 / 1.03 ms: the kernel is bound by what
-// a CU can load (window 19.2 KB + A rows 16 KB per step: 9.2 GB per launch, mostly L2 hits, at ~ 10 B / cycle / CU); the box sums
-// add 0.5 ms, the MFMAs 0.25.  Fetching the window before or after the box sums: no difference.
-#ifndef WF_DMA                 // 1 = the dz window by LDS-DMA (0: through registers, the A/B arm)
-#define WF_DMA 1
-#endif
-#ifndef KMH_WF_MAP
-#define KMH_WF_MAP 1
-#endif
-#ifndef WF_EARLY_W
-#define WF_EARLY_W 1
-#endif
-constexpr int WF_HX = 10, WF_HY = 10, WF_HZ = 6, WF_VOX = WF_HX * WF_HY * WF_HZ;      // window of a 4 x 4 x 2 low tile
-constexpr int WF_NC = 224;                                                           // 216 columns, padded to 7 x 32
-// MODE (round 5, last): the kernel is bound by what a CU can load, so two of its workgroups become the two halves of ONE
-// 512-thread workgroup that share what they both read: MODE 1 = two cout octets over the same A rows (one A image, two windows
-// and B images: 54.4 KB of loads per step instead of 70.4), MODE 2 = two 128-row tiles over the same window and box sums (one
-// window and B image, two A images: 51.2 KB, and half the box-sum work).  MODE 0 = the 256-thread kernel, two per CU.
-// Measured (profiles/r5y_up2_wgrad_fold_modes.txt): MODE 2 -5 % where it applies (256 -> 128 at 64^3: 1.38 -> 1.31 ms); MODE 1
-// +3 % (128 -> 64 at 128^3: 2.79 -> 2.88 ms: 23 % fewer bytes, but one workgroup's phases no longer overlap another's) -- it is
-// compiled, tested and selectable (KEYMORPH_UP2_FOLD_MODE=1), not chosen.
-template <int MODE>
-constexpr int wf_lds_bytes() {
-  constexpr int NW = MODE == 1 ? 2 : 1, NA = MODE == 2 ? 2 : 1;
-  return NW * (WF_VOX * 2 * 16 + 2 * WF_NC * GPITCH) + NA * (2 * 128 * GPITCH + 1024);
-}
-template <bool AMP, int MODE>
-__global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold_kernel(
-    const float* __restrict__ xl, const float* __restrict__ dz, float* __restrict__ Cp, int Dl, int Hl, int Wl, int Cl, int Cout,
-    int tiles_x, int tiles_y, int ktiles, int tiles_per_slab, int ntm /* grid row tiles */, int nto /* grid column groups */,
-    const float* __restrict__ ascale, const float* __restrict__ dscale, const float* __restrict__ a_scale,
-    const float* __restrict__ a_shift, int dz_blocked, int xcd, const float* __restrict__ zero16) {
-  constexpr int NW = MODE == 1 ? 2 : 1, NA = MODE == 2 ? 2 : 1;          // windows + B images, A images
-  constexpr int TPBF = MODE ? 512 : 256;
-  constexpr int W_BYTES = WF_VOX * 2 * 16, A_BYTES = 2 * 128 * GPITCH, B_BYTES = 2 * WF_NC * GPITCH;
-  extern __shared__ __attribute__((aligned(16))) unsigned char wf_lds[];
-  unsigned char* sW0 = wf_lds;                                                      // [NW][voxel][2 quads] fp32
-  unsigned char* sA0 = sW0 + NW * W_BYTES;                                          // [NA][2 terms][128 rows][GPITCH]
-  unsigned char* sB0 = sA0 + NA * A_BYTES;                                          // [NW][2 terms][224 rows][GPITCH]
-  float* sC0 = reinterpret_cast<float*>(sB0 + NW * B_BYTES);                        // [NA][2][128]: GroupNorm's affine of the A rows
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const int hf = MODE ? tid >> 8 : 0, t8 = tid & 255;                               // the thread's half, its index in it
-  const int hw = MODE ? wv >> 2 : 0, wq = wv & 3;                                   // the wave's half, its 32-row tile
-  const int n = blockIdx.z;
-  int item = xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-  const int tn = item % nto; item /= nto;                 // column group (the groups of one K slab read the same rows of xl)
-  const int tm = item % ntm;
-  const int slab = item / ntm;
-  const int oct_t = MODE == 1 ? 2 * tn + hf : tn, oct_w = MODE == 1 ? 2 * tn + hw : tn;              // cout octet: staged / multiplied
-  const int m0_t = (MODE == 2 ? 2 * tm + hf : tm) * 128, m0_w = (MODE == 2 ? 2 * tm + hw : tm) * 128;  // first row: staged / multiplied
-  const int iw_t = MODE == 1 ? hf : 0, ia_t = MODE == 2 ? hf : 0;                   // the images this thread stages into
-  const int D = 2 * Dl, H = 2 * Hl, W = 2 * Wl;
-  const long long Vl = (long long)Dl * Hl * Wl, Vh = (long long)D * H * W;
-  const float sa = ascale[0], sb = dscale[0] * 0.125f;                             // box sums: |sum of 8| <= 8 max|dz|
-  const float desc = ascale[1] * dscale[1] * 8.f;
-  const float* xn = xl + (long long)n * Vl * Cl;
-  const float* dn = dz + (long long)n * Vh * Cout;
-  f32x16 acc[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  for (int e = tid; e < NW * 2 * 8 * GPITCH / 4; e += TPBF) {                       // columns 216 .. 223 stay zero
-    const int im = e / (2 * 8 * GPITCH / 4), r = e % (2 * 8 * GPITCH / 4), t = r / (8 * GPITCH / 4), w = r % (8 * GPITCH / 4);
-    reinterpret_cast<unsigned*>(sB0 + im * B_BYTES + t * WF_NC * GPITCH + 216 * GPITCH)[w] = 0u;
-  }
-  const int t_beg = slab * tiles_per_slab;
-  int t_end = t_beg + tiles_per_slab;
-  if (t_end > ktiles) t_end = ktiles;
-  // staging: the window (600 voxels x 2 quads = 1200 float4) by LDS-DMA, the A rows (16 voxel pairs x 32 quads) through registers
-  constexpr int NIW = MODE == 2 ? 3 : 5;                                            // window elements per thread
-  constexpr int NIA = MODE == 1 ? 1 : 2;                                            // A items per thread
-  float4 pw[WF_DMA ? 1 : NIW], pa[NIA][2];
-  int x0 = 0, y0 = 0, z0 = 0;                                                       // the tile the registers hold
-  auto fetch_w = [&](int t) {                             // the window of tile t
-    const int bx = t % tiles_x, by = (t / tiles_x) % tiles_y, bz = t / (tiles_x * tiles_y);
-    const int wx = 8 * bx - 1, wy = 8 * by - 1, wz = 4 * bz - 1;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4* sWt = reinterpret_cast<float4*>(sW0 + iw_t * W_BYTES);
-#pragma unroll
-    for (int i = 0; i < NIW; ++i) {
-      const int e = (MODE == 2 ? tid + i * 512 : t8 + i * 256), q = e & 1, v = e >> 1;
-      const int lx = v % WF_HX, ly = (v / WF_HX) % WF_HY, lz = v / (WF_HX * WF_HY);
-      const int ux = wx + lx, uy = wy + ly, uz = wz + lz;
-      const bool in = e < 2 * WF_VOX && (unsigned)ux < (unsigned)W && (unsigned)uy < (unsigned)H && (unsigned)uz < (unsigned)D;
-      const long long vox = in ? ((long long)uz * H + uy) * W + ux : 0;
-      const float* src = dz_blocked ? dn + ((long long)oct_t * Vh + vox) * 8 + 4 * q : dn + vox * Cout + 8 * oct_t + 4 * q;
-      if constexpr (WF_DMA != 0) {
-        // straight into the window (element e = lane-linear: 16 bytes per lane behind a wave-uniform base), no staging
-        // registers; voxels outside the volume copy 16 bytes of zeros.  (Past element 1199 a lane must not write: what
-        // follows the window in LDS is another image.)
-        if (e < 2 * WF_VOX)
-          __builtin_amdgcn_global_load_lds((kmh_glb_ptr)(in ? src : zero16), (kmh_lds_ptr)(sWt + (e - lane)), 16, 0, 0);
-      } else {
-        pw[i] = in ? *reinterpret_cast<const float4*>(src) : z4;
-      }
-    }
-  };
-  auto fetch_a = [&](int t) {                             // the A rows of tile t (which becomes the tile the registers hold)
-    const int bx = t % tiles_x, by = (t / tiles_x) % tiles_y, bz = t / (tiles_x * tiles_y);
-    x0 = 4 * bx; y0 = 4 * by; z0 = 2 * bz;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NIA; ++i) {
-      const int e = (MODE == 1 ? tid : t8 + i * 256), cq = (e & 7) + 8 * (e >> 7), kp = (e >> 3) & 15;      // 8 lanes: one 128-byte line of a voxel row
-      const int k = 2 * kp, gx = x0 + (k & 3), gy = y0 + ((k >> 2) & 3), gz = z0 + (k >> 4), ca = m0_t + 4 * cq;
-      const bool rowok = gy < Hl && gz < Dl && ca < Cl;
-      const float* src = xn + (((long long)gz * Hl + gy) * Wl + gx) * Cl + ca;
-      pa[i][0] = (rowok && gx < Wl) ? *reinterpret_cast<const float4*>(src) : z4;
-      pa[i][1] = (rowok && gx + 1 < Wl) ? *reinterpret_cast<const float4*>(src + Cl) : z4;
-    }
-  };
-  if ((MODE == 2 ? t8 : tid) < 128) {
-    const int c = MODE == 2 ? t8 : tid, ca = m0_t + c;
-    float* sC = sC0 + ia_t * 256;
-    sC[c] = (a_scale && ca < Cl) ? a_scale[(long long)n * Cl + ca] : 1.f;
-    sC[128 + c] = (a_scale && ca < Cl) ? a_shift[(long long)n * Cl + ca] : 0.f;
-  }
-  auto commit = [&]() {                                   // registers -> the window and the A image (tile x0, y0, z0)
-    if constexpr (WF_DMA == 0) {
-      float4* sWt = reinterpret_cast<float4*>(sW0 + iw_t * W_BYTES);
-#pragma unroll
-      for (int i = 0; i < NIW; ++i) {
-        const int e = (MODE == 2 ? tid + i * 512 : t8 + i * 256);
-        if (e < 2 * WF_VOX) sWt[e] = pw[i];
-      }
-    }
-    unsigned char* sA = sA0 + ia_t * A_BYTES;
-    const float* sC = sC0 + ia_t * 256;
-#pragma unroll
-    for (int i = 0; i < NIA; ++i) {
-      const int e = (MODE == 1 ? tid : t8 + i * 256), cq = (e & 7) + 8 * (e >> 7), kp = (e >> 3) & 15;
-      const int k = 2 * kp, gx = x0 + (k & 3), gy = y0 + ((k >> 2) & 3), gz = z0 + (k >> 4);
-      const bool rowok = gy < Hl && gz < Dl;
-      const bool v0 = rowok && gx < Wl, v1 = rowok && gx + 1 < Wl;              // voxels past the volume: zero rows (no shift)
-      const float4 sc = *reinterpret_cast<const float4*>(sC + 4 * cq), sh = *reinterpret_cast<const float4*>(sC + 128 + 4 * cq);
-      const float a0[4] = {v0 ? fmaf(pa[i][0].x, sc.x, sh.x) : 0.f, v0 ? fmaf(pa[i][0].y, sc.y, sh.y) : 0.f,
-                           v0 ? fmaf(pa[i][0].z, sc.z, sh.z) : 0.f, v0 ? fmaf(pa[i][0].w, sc.w, sh.w) : 0.f};
-      const float a1[4] = {v1 ? fmaf(pa[i][1].x, sc.x, sh.x) : 0.f, v1 ? fmaf(pa[i][1].y, sc.y, sh.y) : 0.f,
-                           v1 ? fmaf(pa[i][1].z, sc.z, sh.z) : 0.f, v1 ? fmaf(pa[i][1].w, sc.w, sh.w) : 0.f};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned w[2];
-        split_pair<2>(a0[j] * sa, a1[j] * sa, w);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) *reinterpret_cast<unsigned*>(sA + t * 128 * GPITCH + (4 * cq + j) * GPITCH + 4 * kp) = w[t];
-      }
-    }
-  };
-  auto boxes = [&]() {                                    // window -> the B image: thread = (low voxel m, kz, channel quad q)
-    const int bt = MODE == 1 ? t8 : tid;                  // (MODE 1: 192 threads of each half; else the first 192 of the workgroup)
-    if (bt >= 192) return;
-    const float4* sW = reinterpret_cast<const float4*>(sW0 + iw_t * W_BYTES);
-    unsigned char* sB = sB0 + iw_t * B_BYTES;
-#if KMH_WF_MAP
-    // a WAVE = one kz: (q, low voxel m) vary over its lanes.  With kz across the lanes (round 5) three lanes of every quad of
-    // lanes wrote the same bank of the B image (72 columns x 80 bytes = 0 mod 128 bytes between the kz groups) and read window
-    // planes 32 banks apart: 58 % of the kernel's LDS-active cycles were bank conflicts at 59 % LDS busy
-    // (profiles/r6n_lds_by_kernel.txt).  Same sums per (m, kz, q), same order: bit-identical.
-    const int q = bt & 1, kz = bt >> 6, m = (bt >> 1) & 31;
-#else
-    const int q = bt & 1, kz = (bt >> 1) % 3, m = bt / 6;
-#endif
-    const int lmx = m & 3, lmy = (m >> 2) & 3, lmz = m >> 4;
-    float4 Y[3][3];
-#pragma unroll
-    for (int a = 0; a < 9; ++a) (&Y[0][0])[a] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // window index i = u - (2m - 1) in 0..3 per axis; tap k (offset k - 1) sums i in {2 - k, 3 - k}
-#pragma unroll
-    for (int dzp = 0; dzp < 2; ++dzp) {
-      const int lz = 2 * lmz + (2 - kz) + dzp;
-#pragma unroll
-      for (int iy = 0; iy < 4; ++iy) {
-        const float4* row = sW + (((lz * WF_HY + 2 * lmy + iy) * WF_HX + 2 * lmx) * 2 + q);
-        const float4 a4[4] = {row[0], row[2], row[4], row[6]};
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const float4 u = a4[2 - kx], v = a4[3 - kx];
-          const float4 xs = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
-            if (iy == 2 - ky || iy == 3 - ky) {
-              Y[ky][kx].x += xs.x; Y[ky][kx].y += xs.y; Y[ky][kx].z += xs.z; Y[ky][kx].w += xs.w;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);     // (one window row at a time: 32 rows hoisted together spill the accumulators)
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) {
-      const float4 y = (&Y[0][0])[a];
-      const int col = (kz * 9 + a) * 8 + 4 * q;            // column = tap x 8 + cout within the octet
-      unsigned w01[2], w23[2];
-      split_pair<2>(y.x * sb, y.y * sb, w01);
-      split_pair<2>(y.z * sb, y.w * sb, w23);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        unsigned char* base = sB + t * WF_NC * GPITCH + col * GPITCH + 2 * m;
-        *reinterpret_cast<unsigned short*>(base) = (unsigned short)(w01[t] & 0xffffu);
-        *reinterpret_cast<unsigned short*>(base + GPITCH) = (unsigned short)(w01[t] >> 16);
-        *reinterpret_cast<unsigned short*>(base + 2 * GPITCH) = (unsigned short)(w23[t] & 0xffffu);
-        *reinterpret_cast<unsigned short*>(base + 3 * GPITCH) = (unsigned short)(w23[t] >> 16);
-      }
-    }
-  };
-  if (t_beg < t_end) { fetch_w(t_beg); fetch_a(t_beg); }
-  const unsigned char* sAw = sA0 + (MODE == 2 ? hw : 0) * A_BYTES;                  // the images this wave multiplies
-  const unsigned char* sBw = sB0 + (MODE == 1 ? hw : 0) * B_BYTES;
-  for (int t = t_beg; t < t_end; ++t) {
-    __syncthreads();                           // the previous step's fragment reads are done
-    commit();
-    if (WF_DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this lane's pieces of the window are in LDS
-    __syncthreads();
-    if (!WF_DMA && WF_EARLY_W && t + 1 < t_end) fetch_w(t + 1);      // the next window: in flight during the box sums and the MFMAs
-    boxes();
-    __syncthreads();
-    if (t + 1 < t_end) {                       // the next A rows: during the MFMAs (after the box sums: their registers are free again)
-      if (WF_DMA || !WF_EARLY_W) fetch_w(t + 1);
-      fetch_a(t + 1);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 a[2], b[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        a[q] = *reinterpret_cast<const bf16x8*>(sAw + q * 128 * GPITCH + (32 * wq + li) * GPITCH + (16 * s + 8 * lh) * 2);
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          b[q] = *reinterpret_cast<const bf16x8*>(sBw + q * WF_NC * GPITCH + (32 * j + li) * GPITCH + (16 * s + 8 * lh) * 2);
-        if constexpr (!AMP) {
-          acc[j] = mfma16<2>(a[1], b[0], acc[j]);
-          acc[j] = mfma16<2>(a[0], b[1], acc[j]);
-        }
-        acc[j] = mfma16<2>(a[0], b[0], acc[j]);
-      }
-    }
-  }
-  const int nslab = gridDim.x / (nto * ntm);
-  const int J = 27 * Cout;
-  float* Cn = Cp + ((long long)n * nslab + slab) * Cl * J;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const int col = 32 * j + li;
-    const int jj = (col >> 3) * Cout + 8 * oct_w + (col & 7);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = m0_w + 32 * wq + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (row < Cl && col < 216) Cn[(long long)row * J + jj] = acc[j][r] * desc;
-    }
-  }
-}
-
-}  // namespace
-
-static int up2_wgrad_slabs(int V, int Cl, int J, int N, int* kslab) {
-  const int tiles = ceil_div(Cl, 128) * ceil_div(J, 128) * N;
-  int want = 2048 / tiles;                    // ~2048 workgroups
-  if (want < 1) want = 1;
-  int ks = ceil_div(V, want);
-  ks = (ks + GK - 1) / GK * GK;
-  *kslab = ks;
-  return ceil_div(V, ks);
-}
-
-KMH_API size_t kmh_up2_wgrad_gemm_ws_bytes(int N, int V, int Cl, int J) {
-  int ks;
-  const int ns = up2_wgrad_slabs(V, Cl, J, N, &ks);
-  return (size_t)N * ns * Cl * J * sizeof(float);
-}
-
-/* C (N, Cl, J) = A^T B per sample: A (N, V, Cl) the normalised low tensor, B (N, V, J) the box sums (kmh_up2_boxsum);
- * Cl % 4 == 0, J % 4 == 0; ascale / bscale = {S, 1/S} range scales of A and B (terms == 2). */
-KMH_API int kmh_up2_wgrad_gemm(const float* A, const float* B, float* C, int N, int V, int Cl, int J, int terms,
-                               const float* ascale, const float* bscale, const float* a_scale, const float* a_shift,
-                               void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
-  if ((Cl & 3) || (J & 3) || (terms != 2 && terms != 3) || (terms == 2 && (!ascale || !bscale)) || (!a_scale != !a_shift))
-    return -22;
-  int ks;
-  const int ns = up2_wgrad_slabs(V, Cl, J, N, &ks);
-  const int ntn = ceil_div(J, 128), ntm = ceil_div(Cl, 128);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g(ntn * ntm * ns, 1, N);
-  static const int xcd = getenv("KEYMORPH_UP2_GEMM_NO_XCD") ? 0 : 1;
-  if (terms == 2)
-    if (kmh_amp_enabled())
-      up2_wgrad_gemm_kernel<2, true><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
-    else
-    up2_wgrad_gemm_kernel<2><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
-  else
-    up2_wgrad_gemm_kernel<3><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
-  const long long per = (long long)Cl * J;
-  int nb = ceil_div(per, 256);
-  if (nb > 1024) nb = 1024;
-  up2_wgrad_reduce_kernel<<<dim3(nb, N), 256, 0, s>>>((const float*)ws, ns, per, C);
-  return KMH_LAUNCH_CHECK();
-}
-
-// which fold kernel: 2 = two row tiles per workgroup (Cl > 128 with an even tile count), 1 = two cout octets, 0 = the 256-thread one
-// (KEYMORPH_UP2_FOLD_MODE=0|1|2 forces one where it applies: A/B runs)
-static int up2_fold_mode(int Cl, int Cout) {
-  const int ntm = ceil_div(Cl, 128), nto = Cout / 8;
-  int mode = (ntm % 2 == 0) ? 2 : 0;      // (MODE 1 measured 3 % SLOWER than two 256-thread workgroups per CU: forced only)
-  const char* env = getenv("KEYMORPH_UP2_FOLD_MODE");       // (read per call: the tests switch it)
-  if (env) {
-    const int want = atoi(env);
-    if (want == 0 || (want == 1 && nto % 2 == 0) || (want == 2 && ntm % 2 == 0)) mode = want;
-  }
-  return mode;
-}
-
-static int up2_fold_slabs(int N, int Dl, int Hl, int Wl, int Cl, int Cout, int* tiles_per_slab, int* ktiles) {
-  const int kt = ceil_div(Wl, 4) * ceil_div(Hl, 4) * ceil_div(Dl, 2);
-  const int mode = up2_fold_mode(Cl, Cout);
-  const int per = (Cout / 8) * ceil_div(Cl, 128) * N / (mode ? 2 : 1);       // workgroups per slab
-  int want = ceil_div(mode ? 256 : 512, per);               // one 512-thread or two 256-thread workgroups per CU
-  if (want < 1) want = 1;
-  if (want > kt) want = kt;
-  const int tps = ceil_div(kt, want);
-  *tiles_per_slab = tps;
-  *ktiles = kt;
-  return ceil_div(kt, tps);
-}
-
-/* 1 if kmh_up2_wgrad_fold takes this configuration (fp16 split, whole cout octets), else 0 */
-KMH_API int kmh_up2_wgrad_fold_ok(int Cl, int Cout, int terms) {
-  return (terms == 2 && Cl > 0 && (Cl & 3) == 0 && Cout > 0 && (Cout & 7) == 0) ? 1 : 0;
-}
-
-static inline size_t up2_fold_slab_bytes(int N, int Dl, int Hl, int Wl, int Cl, int Cout) {
-  int tps, kt;
-  const int ns = up2_fold_slabs(N, Dl, Hl, Wl, Cl, Cout, &tps, &kt);
-  return (((size_t)N * ns * Cl * 27 * Cout * sizeof(float)) + 255) & ~(size_t)255;
-}
-/* the partial slabs + 256 bytes of zeros (the source of window voxels outside the volume; written by every call on its stream) */
-KMH_API size_t kmh_up2_wgrad_fold_ws_bytes(int N, int Dl, int Hl, int Wl, int Cl, int Cout) {
-  return up2_fold_slab_bytes(N, Dl, Hl, Wl, Cl, Cout) + 256;
-}
-
-template <bool AMP, int MODE>
-static int launch_up2_fold(dim3 g, hipStream_t s, const float* xl, const float* dz, float* ws, int Dl, int Hl, int Wl, int Cl, int Cout,
-                           int kt, int tps, int ntm, int nto, const float* ascale, const float* dscale, const float* a_scale,
-                           const float* a_shift, int dz_blocked, int xcd, const float* zero16) {
-  constexpr int lds = wf_lds_bytes<MODE>();
-  hipError_t e = hipFuncSetAttribute((const void*)up2_wgrad_fold_kernel<AMP, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  up2_wgrad_fold_kernel<AMP, MODE><<<g, MODE ? 512 : 256, lds, s>>>(xl, dz, ws, Dl, Hl, Wl, Cl, Cout, ceil_div(Wl, 4), ceil_div(Hl, 4),
-                                                                  kt, tps, ntm, nto, ascale, dscale, a_scale, a_shift, dz_blocked,
-                                                                  xcd, zero16);
-  return 0;
-}
-
-/* C (N, Cl, 27 Cout) = kmh_up2_wgrad_gemm(xl, kmh_up2_boxsum(dz)) without the box-sum tensor: xl (N, Dl, Hl, Wl, Cl) the raw
- * low tensor (a_scale / a_shift: GroupNorm's affine, or both NULL), dz (N, 2Dl, 2Hl, 2Wl, Cout) or channel-blocked
- * (dz_blocked), ascale / dscale = {S, 1/S} range scales of the normalised low tensor and of dz; terms: 2, or 1 = hi x hi only
- * (use_amp); ws: kmh_up2_wgrad_fold_ws_bytes, 16-byte aligned. */
-KMH_API int kmh_up2_wgrad_fold(const float* xl, const float* dz, float* C, int N, int Dl, int Hl, int Wl, int Cl, int Cout,
-                               int terms, const float* ascale, const float* dscale, const float* a_scale, const float* a_shift,
-                               int dz_blocked, void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: hi x hi only (use_amp), for this call
-  if (!ws || ((uintptr_t)ws & 15) || !kmh_up2_wgrad_fold_ok(Cl, Cout, terms) || !ascale || !dscale || (!a_scale != !a_shift) || N <= 0 || N > 65535) return -22;
-  int tps, kt;
-  const int ns = up2_fold_slabs(N, Dl, Hl, Wl, Cl, Cout, &tps, &kt);
-  const int mode = up2_fold_mode(Cl, Cout);
-  const int nto = (Cout / 8) / (mode == 1 ? 2 : 1), ntm = ceil_div(Cl, 128) / (mode == 2 ? 2 : 1);      // as the grid sees them
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g(nto * ntm * ns, 1, N);
-  static const int xcd = getenv("KEYMORPH_UP2_GEMM_NO_XCD") ? 0 : 1;
-  // 256 bytes of zeros behind the slabs: the LDS-DMA source of window voxels outside the volume.  From the caller's workspace,
-  // zeroed on the caller's stream: no allocation, no host synchronisation, nothing process-wide (stream capture stays legal).
-  const float* zero16 = (const float*)((const char*)ws + up2_fold_slab_bytes(N, Dl, Hl, Wl, Cl, Cout));
-  if (hipMemsetAsync((void*)zero16, 0, 256, s) != hipSuccess) return -12;
-  const bool amp = kmh_amp_enabled();
-  int rc;
-#define KMH_FOLD(A, M) launch_up2_fold<A, M>(g, s, xl, dz, (float*)ws, Dl, Hl, Wl, Cl, Cout, kt, tps, ntm, nto, ascale, dscale, \
-                                             a_scale, a_shift, dz_blocked, xcd, zero16)
-  if (mode == 2) rc = amp ? KMH_FOLD(true, 2) : KMH_FOLD(false, 2);
-  else if (mode == 1) rc = amp ? KMH_FOLD(true, 1) : KMH_FOLD(false, 1);
-  else rc = amp ? KMH_FOLD(true, 0) : KMH_FOLD(false, 0);
-#undef KMH_FOLD
-  if (rc) return rc;
-  const long long per = (long long)Cl * 27 * Cout;
-  int nb = ceil_div(per, 256);
-  if (nb > 1024) nb = 1024;
-  up2_wgrad_reduce_kernel<<<dim3(nb, N), 256, 0, s>>>((const float*)ws, ns, per, C);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API size_t kmh_conv3d_up2_dgrad_pack_bytes(int Cout, int Cl, int terms) {
-  const int CiP = (Cl + 127) & ~127;
-  return (size_t)((Cout + 7) / 8) * terms * DUP_NST * 2 * CiP * 8 * sizeof(__bf16);
-}
-
-KMH_API int kmh_conv3d_up2_dgrad_pack_weight(const float* w, void* packed, int Cout, int Ctot, int cofs, int Cl, int terms,
-                                             const float* wscale, void* stream) {
-  if (cofs < 0 || cofs + Cl > Ctot || (terms != 2 && terms != 3) || (terms == 2 && !wscale)) return -22;
-  const int CiP = (Cl + 127) & ~127, nchunk = (Cout + 7) / 8;
-  const long long total = (long long)nchunk * DUP_NST * 2 * CiP * 8;
-  int nb = ceil_div(total, 256);
-  if (nb > 2048) nb = 2048;
-  hipStream_t s = (hipStream_t)stream;
-  if (terms == 2) pack_weight_upt_kernel<2><<<nb, 256, 0, s>>>(w, (__bf16*)packed, Cout, Ctot, cofs, Cl, CiP, nchunk, wscale);
-  else pack_weight_upt_kernel<3><<<nb, 256, 0, s>>>(w, (__bf16*)packed, Cout, Ctot, cofs, Cl, CiP, nchunk, wscale);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* ds (N,Dl,Hl,Wl,Cl) = for every low voxel, the sum over its 8 children of the gradient of conv3(up2(.), w[:, cofs:cofs+Cl])
- * with respect to the upsampled tensor, from dz (N,2Dl,2Hl,2Wl,Cout) (no ReLU mask operand: dz is already masked). */
-KMH_API size_t kmh_conv3d_up2_dgrad_stats_ws_bytes(int N, int Dl, int Hl, int Wl, int Cl) {
-  return (size_t)N * ceil_div(Wl, DUX) * ceil_div(Hl, DUY) * Dl * Cl * 2 * sizeof(double);
-}
-/* stats_out (N,Cl,2) doubles | NULL (then stats_ws may be NULL): per-channel (sum ds, sum ds^2), from the epilogue */
-KMH_API int kmh_conv3d_up2_dgrad(const float* dz, const void* packed, float* ds, int N, int Dl, int Hl, int Wl, int Cl,
-                                 int Cout, int terms, const float* dscale, const float* wscale, void* stats_ws,
-                                 double* stats_out, int in_blocked, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
-  if ((terms != 2 && terms != 3) || (terms == 2 && (!dscale || !wscale)) || (stats_out && !stats_ws)) return -22;
-  if (in_blocked && (Cout & 7)) return -22;               // whole 8-channel chunks
-  const int CiP = (Cl + 127) & ~127;
-  const int tx = ceil_div(Wl, DUX), ty = ceil_div(Hl, DUY);
-  dim3 g(tx * ty * Dl * ceil_div(Cl, 128), 1, N);
-  hipStream_t s = (hipStream_t)stream;
-  double* sp = stats_out ? (double*)stats_ws : nullptr;
-  if (terms == 2)
-    if (kmh_amp_enabled())
-      conv3_up2_dgrad_kernel<2, true><<<g, DUP_TPB, 0, s>>>(dz, (const bf16x8*)packed, ds, Dl, Hl, Wl, Cl, CiP, Cout, tx, ty, dscale, wscale, sp, in_blocked);
-    else
-    conv3_up2_dgrad_kernel<2><<<g, DUP_TPB, 0, s>>>(dz, (const bf16x8*)packed, ds, Dl, Hl, Wl, Cl, CiP, Cout, tx, ty, dscale, wscale, sp, in_blocked);
-  else
-    conv3_up2_dgrad_kernel<3><<<g, DUP_TPB, 0, s>>>(dz, (const bf16x8*)packed, ds, Dl, Hl, Wl, Cl, CiP, Cout, tx, ty, dscale, wscale, sp, in_blocked);
-  if (stats_out)
-    kmh_stats::final_kernel<<<dim3(ceil_div(Cl * 2, 256 / kWave), N), 256, 0, s>>>(sp, tx * ty * Dl, Cl, stats_out);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API size_t kmh_conv3d_up2_pack_bytes(int Cout, int Cl, int terms) {
-  return (size_t)(Cl / 8) * terms * UP_NST * 2 * cout_pad(Cout) * 8 * sizeof(__bf16);
-}
-
-/* w (Cout, Ctot, 3,3,3): the channels [cofs, cofs + Cl) are the upsampled ones; wscale {S, 1/S} must leave room for the
- * sum of 8 taps (the host passes the 27-tap scale / 8). */
-KMH_API int kmh_conv3d_up2_pack_weight(const float* w, void* packed, int Cout, int Ctot, int cofs, int Cl, int terms,
-                                       const float* wscale, void* stream) {
-  if ((Cl & 7) || cofs < 0 || cofs + Cl > Ctot || (terms != 2 && terms != 3) || (terms == 2 && !wscale)) return -22;
-  const int CoutP = cout_pad(Cout), nchunk = Cl / 8;
-  const long long total = (long long)nchunk * UP_NST * 2 * CoutP * 8;
-  int nb = ceil_div(total, 256);
-  if (nb > 2048) nb = 2048;
-  hipStream_t s = (hipStream_t)stream;
-  if (terms == 2) pack_weight_up_kernel<2><<<nb, 256, 0, s>>>(w, (__bf16*)packed, Cout, Ctot, cofs, Cl, CoutP, nchunk, wscale);
-  else pack_weight_up_kernel<3><<<nb, 256, 0, s>>>(w, (__bf16*)packed, Cout, Ctot, cofs, Cl, CoutP, nchunk, wscale);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* y (N, 2Dl, 2Hl, 2Wl, Cout) = conv3(up2_nearest(norm(xl)), w[:, cofs:cofs+Cl]) with norm = the (N, Ctot) GroupNorm
- * coefficients at channel offset cofs -- the contribution of the upsampled half of a decoder's concatenated input
- * (keymorph/unet3d/buildingblocks.py:471-475 + 46-78), to be passed as `addend` to kmh_conv3d_fwd_bf over the skip
- * half.  No bias, no activation. */
-KMH_API int kmh_conv3d_up2_fwd(const float* xl, const float* scale, const float* shift, int Ctot, int cofs,
-                               const void* packed, float* y, int N, int Dl, int Hl, int Wl, int Cl, int Cout, int terms,
-                               const float* ascale, const float* wscale, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
-  if ((Cl & 7) || (terms != 2 && terms != 3) || (terms == 2 && (!ascale || !wscale))) return -22;
-  if ((long long)Dl * Hl * Wl * Cl >= (1ll << 31)) return -22;
-  const int CoutP = cout_pad(Cout);
-  const int tx = ceil_div(Wl, UX), ty = ceil_div(Hl, UY);
-  dim3 g(tx * ty * Dl * ceil_div(Cout, 64), 1, N);
-  hipStream_t s = (hipStream_t)stream;
-  if (terms == 2)
-    if (kmh_amp_enabled())
-      conv3_up2_fwd_kernel<2, true><<<g, UP_TPB, 0, s>>>(xl, scale, shift, Ctot, cofs, (const bf16x8*)packed, y, Dl, Hl, Wl, Cl,
-                                                Cout, CoutP, tx, ty, ascale, wscale);
-    else
-    conv3_up2_fwd_kernel<2><<<g, UP_TPB, 0, s>>>(xl, scale, shift, Ctot, cofs, (const bf16x8*)packed, y, Dl, Hl, Wl, Cl,
-                                                Cout, CoutP, tx, ty, ascale, wscale);
-  else
-    conv3_up2_fwd_kernel<3><<<g, UP_TPB, 0, s>>>(xl, scale, shift, Ctot, cofs, (const bf16x8*)packed, y, Dl, Hl, Wl, Cl,
-                                                Cout, CoutP, tx, ty, ascale, wscale);
-  return KMH_LAUNCH_CHECK();
-}
+static inline bool use_zpair(int Cout) { return Cout <= 16; }      // the z-paired N tile (and weight packing) serves these
 
 KMH_API size_t kmh_conv3d_pack_bf_bytes(int Cout, int Cin, int transposed, int terms) {
   const int Co = transposed ? Cin : Cout, Ci = transposed ? Cout : Cin;
@@ -2730,6 +1661,12 @@ KMH_API int kmh_conv3d_pack_weight_bf(const float* w, void* packed, int Cout, in
   return KMH_LAUNCH_CHECK();
 }
 
+// the epilogue statistics' last step (stats_out != NULL), then the launch status every launcher returns
+static int finish_stats(double* stats_ws, int bricks, int Cout, int N, double* stats_out, hipStream_t s) {
+  if (stats_out) kmh_stats::final_kernel<<<dim3(ceil_div(Cout * 2, 256 / kWave), N), 256, 0, s>>>(stats_ws, bricks, Cout, stats_out);
+  return KMH_LAUNCH_CHECK();
+}
+
 /* x (N,D,H,W,Cin) -> y (N,D,H,W,Cout); `packed` from kmh_conv3d_pack_weight_bf for the SAME (Cin, Cout) view:
  * forward: pack(w, Cout, Cin, 0); data gradient: pack(w, Cout_w, Cin_w, 1) and call with Cin = Cout_w, Cout = Cin_w */
 template <int NT, int TERMS, int MR, bool ZP = false, int ZT = 1>
@@ -2743,10 +1680,41 @@ static int launch_fwd_bf(const float* x, const float* scale, const float* shift,
   conv3_fwd_bf_kernel<NT, TERMS, MR, ZP, ZT><<<g, BF_TPB, 0, s>>>(x, scale, shift, mask, wp, bias, y, D, H, W, Cin, Cout,
                                                              CoutP, relu_in, relu_out, tx, ty, tz, tzp, ascale, wscale,
                                                              stats_out ? stats_ws : nullptr, in_blocked, addend);
-  if (stats_out)
-    kmh_stats::final_kernel<<<dim3(ceil_div(Cout * 2, 256 / kWave), N), 256, 0, s>>>(stats_ws, tx * ty * tz, Cout,
-                                                                                  stats_out);
-  return KMH_LAUNCH_CHECK();
+  return finish_stats(stats_ws, tx * ty * tz, Cout, N, stats_out, s);
+}
+
+// What the two persistent kernels' launchers share.  Their grid: `total` virtual blocks per sample (32 x 8 x 4 bricks in (y, z)
+// patches of 8 x 8, x `groups` cout groups) and persistent workgroups, one per CU, over ONE work list of N * total bricks (a
+// multiple of 8 workgroups, so that every id of a workgroup's list falls on its own XCD)
+struct PersistentGrid { int tx, ty, tz, tzp, total, wgs; };
+static PersistentGrid persistent_grid(int N, int D, int H, int W, int groups) {
+  const int tx = ceil_div(W, TX), ty = ceil_div(H, GTY), tz = ceil_div(D, GTZ), tzp = ceil_div(tz, 8);
+  const int total = tx * ceil_div(ty, 8) * tzp * 64 * groups;
+  const long long all8 = ((long long)N * total + 7) / 8 * 8;
+  return {tx, ty, tz, tzp, total, all8 < 256 ? (int)all8 : 256};
+}
+template <typename K>
+static int allow_lds(K kernel, int bytes) {      // 0 or the hipError_t
+  return (int)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+// KMH_G_TRACE=1 (debug): cycle stamps of workgroup 0 to stderr.  trace_begin: the cleared buffer the kernel stamps into (NULL
+// unless tracing); trace_end: waits for the stream, prints the label and the differences between consecutive stamps.
+static long long* trace_begin(hipStream_t s) {
+  static long long* trace = nullptr;
+  static const bool tracing = getenv("KMH_G_TRACE") != nullptr;
+  if (tracing && !trace && hipMalloc(&trace, 240 * sizeof(long long)) != hipSuccess) trace = nullptr;
+  if (trace) (void)hipMemsetAsync(trace, 0, 240 * sizeof(long long), s);
+  return trace;
+}
+template <typename... A>
+static void trace_end(const long long* trace, hipStream_t s, const char* label, A... a) {
+  if (!trace) return;
+  long long h[240];
+  (void)hipStreamSynchronize(s);
+  (void)hipMemcpy(h, trace, sizeof(h), hipMemcpyDeviceToHost);
+  fprintf(stderr, label, a...);
+  for (int i = 1; i < 240 && h[i]; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
+  fprintf(stderr, "\n");
 }
 
 template <int NT, bool ZP, bool POOL = false>
@@ -2754,38 +1722,15 @@ static int launch_fwd_g(const float* x, const float* scale, const float* shift, 
                         float* y, int N, int D, int H, int W, int Cin, int Cout, int CoutP, int relu_in, int relu_out,
                         const float* ascale, const float* wscale, double* stats_ws, double* stats_out, hipStream_t s,
                         int in_blocked, const float* addend, unsigned* pool_arg = nullptr) {
-  hipError_t e = hipFuncSetAttribute((const void*)conv3_fwd_g_kernel<NT, ZP, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     G_LDS_BYTES);
-  if (e != hipSuccess) return (int)e;
-  const int tx = ceil_div(W, TX), ty = ceil_div(H, GTY), tz = ceil_div(D, GTZ);
-  const int typ = ceil_div(ty, 8), tzp = ceil_div(tz, 8);
-  const int total = tx * typ * tzp * 64 * (ZP ? 1 : ceil_div(Cout, 32 * NT));      // virtual blocks per sample
-  // persistent workgroups, one per CU, over ONE work list of N * total bricks (a multiple of 8 workgroups, so that every
-  // id of a workgroup's list falls on its own XCD)
-  long long all = (long long)N * total;
-  int wgs = 256;
-  if (wgs > ((all + 7) / 8) * 8) wgs = (int)(((all + 7) / 8) * 8);
-  dim3 g(wgs, 1, 1);
-  static long long* trace = nullptr;                       // KMH_G_TRACE=1 (debug): cycle stamps of workgroup 0 to stderr
-  static const bool tracing = getenv("KMH_G_TRACE") != nullptr;
-  if (tracing && !trace) { if (hipMalloc(&trace, 240 * sizeof(long long)) != hipSuccess) trace = nullptr; }
-  if (tracing && trace) (void)hipMemsetAsync(trace, 0, 240 * sizeof(long long), s);
-  conv3_fwd_g_kernel<NT, ZP, POOL><<<g, G_TPB, G_LDS_BYTES, s>>>(x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP,
-                                                                 relu_in, relu_out, tx, ty, tz, tzp, ascale, wscale,
-                                                                 stats_out ? stats_ws : nullptr, in_blocked, addend, total, N,
-                                                                 tracing ? trace : nullptr, pool_arg);
-  if (tracing && trace) {
-    long long h[240];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, trace, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr, "KMH_G_TRACE NT=%d ZP=%d Cin=%d Cout=%d D=%d:", NT, (int)ZP, Cin, Cout, D);
-    for (int i = 1; i < 240 && h[i]; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-    fprintf(stderr, "\n");
-  }
-  if (stats_out)
-    kmh_stats::final_kernel<<<dim3(ceil_div(Cout * 2, 256 / kWave), N), 256, 0, s>>>(stats_ws, tx * ty * tz, Cout,
-                                                                                  stats_out);
-  return KMH_LAUNCH_CHECK();
+  if (int e = allow_lds(conv3_fwd_g_kernel<NT, ZP, POOL>, G_LDS_BYTES)) return e;
+  const PersistentGrid g = persistent_grid(N, D, H, W, ZP ? 1 : ceil_div(Cout, 32 * NT));
+  long long* trace = trace_begin(s);
+  conv3_fwd_g_kernel<NT, ZP, POOL><<<dim3(g.wgs), G_TPB, G_LDS_BYTES, s>>>(x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP,
+                                                                           relu_in, relu_out, g.tx, g.ty, g.tz, g.tzp, ascale, wscale,
+                                                                           stats_out ? stats_ws : nullptr, in_blocked, addend,
+                                                                           g.total, N, trace, pool_arg);
+  trace_end(trace, s, "KMH_G_TRACE NT=%d ZP=%d Cin=%d Cout=%d D=%d:", NT, (int)ZP, Cin, Cout, D);
+  return finish_stats(stats_ws, g.tx * g.ty * g.tz, Cout, N, stats_out, s);
 }
 
 template <int NT, bool ZP = false, bool SPLIT = false, bool POOL = false>
@@ -2793,43 +1738,19 @@ static int launch_fwd_s(const float* x, const float* scale, const float* shift, 
                         int N, int D, int H, int W, int Cin, int Cout, int CoutP, int relu_in, int relu_out,
                         const float* ascale, const float* wscale, double* stats_ws, double* stats_out, hipStream_t s,
                         int in_blocked, const float* addend, unsigned* pool_arg = nullptr) {
-  hipError_t e = hipFuncSetAttribute((const void*)conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     S_LDS_BYTES);
-  if (e != hipSuccess) return (int)e;
-  const int tx = ceil_div(W, TX), ty = ceil_div(H, GTY), tz = ceil_div(D, GTZ);
-  const int typ = ceil_div(ty, 8), tzp = ceil_div(tz, 8);
-  const int total = tx * typ * tzp * 64 * (ZP ? 1 : ceil_div(Cout, 32 * NT));      // virtual blocks per sample
-  long long all = (long long)N * total;
-  int wgs = 256;                                          // persistent, one per CU
-  if (wgs > ((all + 7) / 8) * 8) wgs = (int)(((all + 7) / 8) * 8);
-  static long long* trace = nullptr;                       // KMH_G_TRACE=1 (debug): cycle stamps of workgroup 0 to stderr
-  static const bool tracing = getenv("KMH_G_TRACE") != nullptr;
-  if (tracing && !trace) { if (hipMalloc(&trace, 240 * sizeof(long long)) != hipSuccess) trace = nullptr; }
-  if (tracing && trace) (void)hipMemsetAsync(trace, 0, 240 * sizeof(long long), s);
+  if (int e = allow_lds(conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL>, S_LDS_BYTES)) return e;
+  const PersistentGrid g = persistent_grid(N, D, H, W, ZP ? 1 : ceil_div(Cout, 32 * NT));
+  long long* trace = trace_begin(s);
+#define KMH_S_ARGS x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, g.tx, g.ty, g.tz, g.tzp, ascale, wscale, \
+                   stats_out ? stats_ws : nullptr, in_blocked, addend, g.total, N, trace, pool_arg
   if (kmh_amp_enabled()) {
-    e = hipFuncSetAttribute((const void*)conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            S_LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true><<<dim3(wgs), S_TPB, S_LDS_BYTES, s>>>(
-        x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, tx, ty, tz, tzp, ascale, wscale,
-        stats_out ? stats_ws : nullptr, in_blocked, addend, total, N, tracing ? trace : nullptr, pool_arg);
+    if (int e = allow_lds(conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true>, S_LDS_BYTES)) return e;
+    conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true><<<dim3(g.wgs), S_TPB, S_LDS_BYTES, s>>>(KMH_S_ARGS);
   } else
-  conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL><<<dim3(wgs), S_TPB, S_LDS_BYTES, s>>>(x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP, relu_in,
-                                                               relu_out, tx, ty, tz, tzp, ascale, wscale,
-                                                               stats_out ? stats_ws : nullptr, in_blocked, addend, total, N,
-                                                               tracing ? trace : nullptr, pool_arg);
-  if (tracing && trace) {
-    long long h[240];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, trace, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr, "KMH_G_TRACE fwd_s NT=%d ZP=%d SPLIT=%d POOL=%d Cin=%d Cout=%d D=%d:", NT, (int)ZP, (int)SPLIT, (int)POOL, Cin, Cout, D);
-    for (int i = 1; i < 240 && h[i]; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-    fprintf(stderr, "\n");
-  }
-  if (stats_out)
-    kmh_stats::final_kernel<<<dim3(ceil_div(Cout * 2, 256 / kWave), N), 256, 0, s>>>(stats_ws, tx * ty * tz, Cout,
-                                                                                  stats_out);
-  return KMH_LAUNCH_CHECK();
+    conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL><<<dim3(g.wgs), S_TPB, S_LDS_BYTES, s>>>(KMH_S_ARGS);
+#undef KMH_S_ARGS
+  trace_end(trace, s, "KMH_G_TRACE fwd_s NT=%d ZP=%d SPLIT=%d POOL=%d Cin=%d Cout=%d D=%d:", NT, (int)ZP, (int)SPLIT, (int)POOL, Cin, Cout, D);
+  return finish_stats(stats_ws, g.tx * g.ty * g.tz, Cout, N, stats_out, s);
 }
 
 // the LDS-DMA kernel's preconditions: fp16 split, whole 8-channel chunks, no fused mask operand, and enough bricks to
@@ -3007,1060 +1928,3 @@ KMH_API int kmh_conv3d_fwd_bf(const float* x, const float* scale, const float* s
   }
 #undef KMH_BF_CALL
 }
-
-#endif   // !KMH_TU_WGRAD
-#if KMH_TU_WGRAD
-// =============================================================================================
-// Split-bf16 weight gradient: dW[tap][ci][co] = sum_v xn[v + tap][ci] * dz[v][co].
-// K of the MFMA = 16 consecutive voxels of one brick row, so BOTH operands need, per lane, 8 consecutive
-// voxels of ONE channel: the brick is transposed while it is staged into channel-major bf16 LDS images
-//   sXT[term][ci (+1 zero plane)][halo row][24]   plane pitch 1168 B (= 73 x 16 B: lanes = channels hit 16
-//   sDT[term][co][128 voxels]                     plane pitch  272 B (= 17 x 16 B)   distinct 16-B slots)
-// A fragment = aligned ds_read_b128 + ds_read_b32 around the window, then a funnel shift by the tap's x
-// offset (0 / 2 / 4 bytes: v_alignbyte for kx = 1, register renaming for kx = 2); B fragment = one aligned
-// ds_read_b128.  M rows are packed (tap, ci) with ci tiles of <= 16 channels (2 taps per 32-row tile),
-// tiles dealt to the 8 waves exactly like the fp32 kernel; per-wave partial slabs, deterministic reduce.
-namespace {
-
-constexpr int WX = 16, WY = 4, WZ = 2;
-constexpr int WHY = WY + 2, WHZ = WZ + 2;
-constexpr int XROWS = WHY * WHZ;           // 24 halo rows
-constexpr int XPITCH = 24;                 // elements per halo row (18 used)
-constexpr int XPLANE = 1168;               // bytes per channel plane (24 rows x 48 B = 1152, padded)
-constexpr int DPLANE = 272;                // bytes per cout plane (128 voxels x 2 B = 256, padded)
-constexpr int WV = WX * WY * WZ;           // 128
-// Round 6, the wave-specialised kernel: the x image is a RING of z planes.  Bricks are walked z-fastest, so a brick's 4-plane
-// halo window shares 2 planes with its predecessor's: only the 2 new planes (12 of 24 halo rows) are fetched, normalised and
-// split per brick -- the operand was 3.4 x redundant (432 halo voxels per 128-voxel brick), now 1.7 x.  8 ring planes: 4 being
-// multiplied, up to 4 being filled (the first brick of a z column fills all 4 and starts 4 planes further on, so it never
-// touches what the previous column's last brick is still being read from).
-constexpr int RZ = 8;                                  // ring planes
-// Plane pitch of the ring image: 2312 bytes = 578 words, i.e. 2 mod 32.  The consumers' A fragments are five dwords per lane that
-// the compiler reads with 4-byte instructions (ds_read2_b32: it scalarises a 16-byte load whose dwords feed the funnel shifts one by
-// one), whose 32-lane groups are 16 channels x 2 taps: with the pitch at 4 mod 32 words (2320 B = 145 x 16 B, chosen in round 2 for
-// 16-byte reads that the compiler never emitted) 32 lanes hit 8 banks -- 57 % of the LDS-active cycles were bank conflicts and the LDS
-// was 86 % busy (profiles/r6i_sq_counters_wgrad_ring.txt).  At 2 mod 32 the channels take 16 distinct banks and the producers'
-// 4-byte stores (channel quads 8 banks apart) stay conflict-free: -6 ... -11 % on every launch; 6, 10, 18 mod 32 the same, an ODD
-// pitch twice as slow (profiles/r6k_wgrad_ring_pitch_ab.txt).  KMH_WG_RPAD (A/B builds): bytes added to the 2304 of the rows.
-#ifndef KMH_WG_RPAD
-#define KMH_WG_RPAD 8
-#endif
-#ifndef KMH_WG_RROW
-#define KMH_WG_RROW 24          // elements (2 bytes) per halo row of the ring image (18 used; a lane reads 5 dwords from byte 0 or 16)
-#endif
-#ifndef KMH_WG_RZPAD
-#define KMH_WG_RZPAD 0          // bytes added to a ring plane
-#endif
-constexpr int XPITCH_R = KMH_WG_RROW;
-constexpr int ZSLOT = WHY * XPITCH_R * 2 + KMH_WG_RZPAD;   // bytes per ring plane inside a channel plane
-constexpr int XPLANE_R = RZ * ZSLOT + KMH_WG_RPAD;
-static_assert(XPITCH_R * 2 >= 36 && (XPLANE_R & 3) == 0 && (ZSLOT & 3) == 0, "a row holds 18 elements; dword-aligned planes");
-constexpr int WGB_TPB = 512;
-constexpr int MTWB = 2;                    // M tiles per wave (14 tiles over 8 waves)
-
-__device__ __forceinline__ unsigned pack2(__bf16 lo, __bf16 hi) {
-  return (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
-}
-
-// ---- pieces shared by the two weight-gradient kernels -----------------------------------------------------------
-// Tile dealing.  M-tile m = (kx group, slot): all 32 rows of a tile share the tap's x offset kx = m / TPK (the funnel
-// shift is then wave-uniform); within the kx group the 9 (kz, ky) taps are packed TPT = 32 / CP per tile.  The three
-// kx tiles of one slot read the SAME 20 bytes per lane and differ only in the shift, so with 8 tile groups and 5
-// slots (CP = 16: 15 tiles) waves 0-4 take (slot w, kx 0) and (slot w, kx 1) -- one LDS read feeds both fragments --
-// and waves 5-7 share out the five kx = 2 tiles.  Other shapes: round robin.
-struct WgradTiles {
-  int TPT, TPK, tile[MTWB], abase[MTWB], akx[MTWB];
-  int akz[MTWB];                                  // ring layout: the lane's tap kz (abase then holds no z term)
-  bool share_a;                                   // wave-uniform: tile 1 reuses tile 0's LDS words
-};
-__device__ __forceinline__ WgradTiles wgrad_deal_tiles(int CP, int MT, int TG, int tg, int li, int lh, bool ring = false) {
-  WgradTiles w;
-  w.TPT = 32 / CP;
-  w.TPK = (9 + w.TPT - 1) / w.TPT;
-  const bool paired = (TG == 8 && MT == 15);
-  w.share_a = paired && tg < 5;
-#pragma unroll
-  for (int j = 0; j < MTWB; ++j) {
-    int m = tg + TG * j;
-    if (paired) {
-      if (tg < 5) m = j * w.TPK + tg;                        // (kx = j, slot = tg)
-      else { const int k = (tg - 5) * 2 + j; m = k < 5 ? 2 * w.TPK + k : MT; }   // (kx = 2, slot = k); k = 5: none
-    }
-    w.tile[j] = m;
-    const int kx = m / w.TPK, slot = m - kx * w.TPK;
-    const int t9 = slot * w.TPT + li / CP, c = li % CP;
-    const bool valid = (m < MT) && (t9 < 9);
-    const int kz = t9 / 3, ky = t9 % 3;
-    w.abase[j] = valid ? (c * XPLANE + (kz * WHY + ky) * (XPITCH * 2) + 16 * lh) : (CP * XPLANE + 16 * lh);
-    w.akz[j] = 0;
-    if (ring) {      // the z offset is added per brick: ((ring base + row plane + kz) mod RZ) planes (the zero plane: any)
-      w.abase[j] = valid ? (c * XPLANE_R + ky * (XPITCH_R * 2) + 16 * lh) : (CP * XPLANE_R + 16 * lh);
-      w.akz[j] = valid ? kz : 0;
-    }
-    w.akx[j] = __builtin_amdgcn_readfirstlane(m < MT ? kx : 0);
-  }
-  return w;
-}
-
-// MFMA phase of one brick: one K16 step per brick row (z, y), this wave's k-split share of the rows
-// MODE (wave-uniform, fixed for the life of the wave) specialises the funnel shift of the A fragments:
-//   0  generic: any kx per tile, branch-free selects (8 VALU per fragment)
-//   1  the paired dealing's waves 0-4: tile 0 is kx = 0 (the words as read), tile 1 is kx = 1 of the SAME words
-//      (4 alignbyte); one LDS read feeds both
-//   2  the paired dealing's waves 5-7: both tiles are kx = 2, a pure register renaming (no VALU)
-template <int NT, int TERMS, int MODE = 0, bool AMP = false, bool RING = false>
-__device__ __forceinline__ void wgrad_mfma_brick(const unsigned char* sXT, const unsigned char* sDT, int xt_bytes,
-                                                 const WgradTiles& w, int ks, int KS, int li, int lh,
-                                                 f32x16 (&acc)[MTWB][NT], int ring_base = 0) {
-  constexpr int CO = 32 * NT;
-  // the paired dealing implies CP = 16 and no k-split (KS = 1): the row loop is unrolled and every LDS offset but the
-  // per-lane base is an instruction immediate
-  if (MODE != 0) xt_bytes = 17 * (RING ? XPLANE_R : XPLANE);
-  const unsigned char* sDTl = sDT + li * DPLANE + 16 * lh;
-  // RING: the byte offset of ring plane (base + zz + kz) mod RZ, per tile and output plane zz of the brick (per lane: kz is)
-  int zo[MTWB][WZ];
-#pragma unroll
-  for (int j = 0; j < MTWB; ++j)
-#pragma unroll
-    for (int z = 0; z < WZ; ++z) zo[j][z] = RING ? ((ring_base + z + w.akz[j]) & (RZ - 1)) * ZSLOT : 0;
-  auto one_row = [&](int row) {
-    const int zz = row / WY, yy = row - zz * WY;
-    const int arow = RING ? yy * (XPITCH_R * 2) : (zz * WHY + yy) * (XPITCH * 2);
-    const int brow = row * WX * 2;
-    bf16x8 b[NT][TERMS];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int q = 0; q < TERMS; ++q)
-        b[t][q] = *reinterpret_cast<const bf16x8*>(sDTl + (q * CO + 32 * t) * DPLANE + brow);
-    bf16x8 a[MTWB][TERMS];
-    uint4 wq[TERMS];
-    unsigned w4q[TERMS];
-#pragma unroll
-    for (int j = 0; j < MTWB; ++j) {
-#pragma unroll
-      for (int q = 0; q < TERMS; ++q) {
-        if (MODE == 1 ? j == 0 : (MODE == 2 || j == 0 || !w.share_a)) {
-          const unsigned char* p = sXT + q * xt_bytes + w.abase[j] + (RING ? zo[j][zz] : 0) + arow;
-          if constexpr (RING) {
-            // five dwords, read AS dwords (the ring's plane pitch is a multiple of 8, not of 16 bytes: see XPLANE_R)
-            const unsigned* p32 = reinterpret_cast<const unsigned*>(p);
-            wq[q] = make_uint4(p32[0], p32[1], p32[2], p32[3]);
-            w4q[q] = p32[4];
-          } else {
-            wq[q] = *reinterpret_cast<const uint4*>(p);
-            w4q[q] = *reinterpret_cast<const unsigned*>(p + 16);
-          }
-        }
-        const uint4 v = wq[q];
-        const unsigned v4 = w4q[q];
-        if (MODE == 1) {
-          uint4 r = v;
-          if (j == 1) {
-            r.x = __builtin_amdgcn_alignbyte(v.y, v.x, 2u);
-            r.y = __builtin_amdgcn_alignbyte(v.z, v.y, 2u);
-            r.z = __builtin_amdgcn_alignbyte(v.w, v.z, 2u);
-            r.w = __builtin_amdgcn_alignbyte(v4, v.w, 2u);
-          }
-          a[j][q] = __builtin_bit_cast(bf16x8, r);
-          continue;
-        }
-        if (MODE == 2) {
-          uint4 r;
-          r.x = v.y; r.y = v.z; r.z = v.w; r.w = v4;
-          a[j][q] = __builtin_bit_cast(bf16x8, r);
-          continue;
-        }
-        // branch-free funnel shift by the tile's (wave-uniform) tap x offset kx in {0, 1, 2} elements: kx = 2
-        // selects the next dword as source, kx = 1 shifts by two bytes -- no control flow between the LDS reads,
-        // so all fragment loads of a row are in flight together
-        const bool k2 = w.akx[j] == 2;
-        const unsigned sh = w.akx[j] == 1 ? 2u : 0u;
-        uint4 r;
-        r.x = __builtin_amdgcn_alignbyte(v.y, k2 ? v.y : v.x, sh);
-        r.y = __builtin_amdgcn_alignbyte(v.z, k2 ? v.z : v.y, sh);
-        r.z = __builtin_amdgcn_alignbyte(v.w, k2 ? v.w : v.z, sh);
-        r.w = __builtin_amdgcn_alignbyte(v4, k2 ? v4 : v.w, sh);
-        a[j][q] = __builtin_bit_cast(bf16x8, r);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < MTWB; ++j)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        if (TERMS == 3) {
-          acc[j][t] = mfma16<TERMS>(a[j][2], b[t][0], acc[j][t]);
-          acc[j][t] = mfma16<TERMS>(a[j][1], b[t][1], acc[j][t]);
-          acc[j][t] = mfma16<TERMS>(a[j][0], b[t][2], acc[j][t]);
-        }
-        if constexpr (!AMP) {
-          acc[j][t] = mfma16<TERMS>(a[j][1], b[t][0], acc[j][t]);
-          acc[j][t] = mfma16<TERMS>(a[j][0], b[t][1], acc[j][t]);
-        }
-        acc[j][t] = mfma16<TERMS>(a[j][0], b[t][0], acc[j][t]);
-      }
-  };
-  // (Round 6, measured and removed: the fragments of row r + 1 read into a second register set before row r's MFMAs -- the
-  // compiler's own order is "rrLM rrrrLM ...", 33 lgkmcnt waits per 48 MFMAs; with the read-ahead 14, all counted (lgkmcnt(10..12))
-  // -- changed no launch: 3.435 / 3.400 ms with / without at 16 -> 32, 2 x 256^3; N = 64 spills.  profiles/r6d_wgrad_readahead_ab.txt)
-  if (MODE != 0) {
-#pragma unroll
-    for (int row = 0; row < WY * WZ; ++row) one_row(row);
-  } else {
-    for (int row = ks; row < WY * WZ; row += KS) one_row(row);
-  }
-}
-
-// this wave's accumulators -> its partial slab (tap, ci, co)
-template <int NT>
-__device__ __forceinline__ void wgrad_store_partial(float* out, const WgradTiles& w, int MT, int CP, int ci0, int co0,
-                                                    int Cin, int Cout, int li, int lh, const f32x16 (&acc)[MTWB][NT]) {
-#pragma unroll
-  for (int j = 0; j < MTWB; ++j) {
-    const int m = w.tile[j];
-    if (m >= MT) continue;
-    const int kx = m / w.TPK, slot = m - kx * w.TPK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int co = co0 + 32 * t + li;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int t9 = slot * w.TPT + rr / CP, c = ci0 + rr % CP;
-        const int tap = t9 * 3 + kx;             // (kz*3 + ky)*3 + kx
-        if (t9 < 9 && c < Cin && co < Cout) out[((long long)tap * Cin + c) * Cout + co] = acc[j][t][r];
-      }
-    }
-  }
-}
-
-template <int NT, int TERMS>
-__global__ __launch_bounds__(WGB_TPB, 2) void conv3_wgrad_bf_kernel(
-    const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ dz, const float* __restrict__ dzmask, float* __restrict__ partial, int N, int D,
-    int H, int W, int Cin, int Cout, int relu_in, int CP, int MT, int TG, int KS, int ci_tiles, int tiles_x,
-    int tiles_y, int tiles_z, int bricks_per_slab, int nslab_total, int Cmem /* channel stride of x in memory */,
-    int ones_ch /* logical channel that reads as 1 inside the volume (-1: none) */,
-    const float* __restrict__ xscale /* {S, 1/S} of x | NULL */, const float* __restrict__ dscale /* of dz | NULL */) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smemb[];
-  constexpr int CO = 32 * NT;
-  const int xt_bytes = (CP + 1) * XPLANE;                 // one term of sXT
-  unsigned char* sXT = smemb;                             // [TERMS][(CP+1)][XPLANE]
-  unsigned char* sDT = smemb + TERMS * xt_bytes;          // [TERMS][CO][DPLANE]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  // work item = (slab, (ci tile, cout group)) with the tile index fastest, XCD-remapped: the workgroups that
-  // re-read the same bricks for different channel tiles run on the same XCD at the same time
-  const int ntile = gridDim.x / nslab_total;
-  const int item = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = item % ntile, slab = item / ntile;
-  const int cit = tile % ci_tiles, cog = tile / ci_tiles;
-  const int ci0 = cit * CP, co0 = cog * CO;
-  const int tg = wv % TG, ks = wv / TG;
-
-  const WgradTiles wt = wgrad_deal_tiles(CP, MT, TG, tg, li, lh);
-  f32x16 acc[MTWB][NT];
-#pragma unroll
-  for (int j = 0; j < MTWB; ++j)
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][t][r] = 0.f;
-
-  // zero plane (padded M rows) of every term
-  for (int e = tid; e < TERMS * (XPLANE / 4); e += WGB_TPB) {
-    const int t = e / (XPLANE / 4), o = e - t * (XPLANE / 4);
-    reinterpret_cast<unsigned*>(sXT + t * xt_bytes + CP * XPLANE)[o] = 0u;
-  }
-  // slabs never straddle samples (nslab_total = N * slabs per sample): the reduce kernel can then give per-sample sums
-  const int slabs_per_n = nslab_total / N, bricks_in_n = tiles_x * tiles_y * tiles_z;
-  const long long b_base = (long long)(slab / slabs_per_n) * bricks_in_n;
-  const long long b_beg = b_base + (long long)(slab % slabs_per_n) * bricks_per_slab;
-  long long b_end = b_beg + bricks_per_slab;
-  if (b_end > b_base + bricks_in_n) b_end = b_base + bricks_in_n;
-  const bool xvec = (CP >= 4) && ((Cin & 3) == 0) && (Cmem == Cin);
-  const bool dvec = (Cout & 3) == 0;
-  const int cq = CP >> 2;                 // channel quads per voxel (xvec)
-
-  // ---- software pipeline over bricks: the global loads of brick b+1 are issued into registers before the
-  //      MFMA phase of brick b and converted / transposed into LDS after it (1 workgroup per CU: nothing
-  //      else would hide the HBM latency).  Item = 2 voxels x (4 channels | 1 channel).
-  constexpr int XI = 2;                         // input-halo items per thread (24 rows x 9 pairs x <=4 quads = 864)
-  constexpr int DI = (WV / 2) * (CO / 4) / WGB_TPB;   // dz items per thread (vector path): 2 (NT=2) or 1
-  const int x_per_row = 9 * (xvec ? cq : CP);
-  const int x_items = XROWS * x_per_row;
-  float4 px[XI][2];
-  float4 pd[DI > 0 ? DI : 1][2], pm[DI > 0 ? DI : 1][2];
-  int pn = 0;                                   // sample index of the prefetched brick
-
-  // per-thread staging descriptors (identical for every brick): computed once.  Global addresses are
-  // (per-brick base pointer) + (precomputed 32-bit element offset relative to the brick origin).
-  int xi_dz[XI], xi_dy[XI], xi_dx[XI], xi_cb[XI], xi_lds[XI], xi_rel[XI];
-  bool xi_on[XI];
-  const int HWs = H * W;
-#pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const int e = tid + i * WGB_TPB;
-    const int rowh = e / x_per_row, rem = e - rowh * x_per_row;
-    const int cpart = rem / 9, pr = rem - cpart * 9;
-    const int lz = rowh / WHY, ly = rowh - lz * WHY;
-    xi_cb[i] = xvec ? 4 * cpart : cpart;
-    xi_on[i] = (e < x_items) && (ci0 + xi_cb[i] < Cin);
-    xi_dz[i] = lz - 1; xi_dy[i] = ly - 1; xi_dx[i] = 2 * pr - 1;
-    xi_lds[i] = xi_cb[i] * XPLANE + (rowh * XPITCH + 2 * pr) * 2;
-    xi_rel[i] = ((xi_dz[i] * H + xi_dy[i]) * W + xi_dx[i]) * Cmem + xi_cb[i];
-  }
-  constexpr int DIR = DI > 0 ? DI : 1;
-  int di_dz[DIR], di_dy[DIR], di_dx[DIR], di_lds[DIR], di_rel[DIR];
-  bool di_on[DIR];
-#pragma unroll
-  for (int i = 0; i < DI; ++i) {
-    const int e = tid + i * WGB_TPB;
-    // lanes: 4 consecutive cout quads (one 64-B global segment), then 64 voxel pairs, then quad groups
-    const int q = (e & 3) + 4 * (e >> 8), pv = (e >> 2) & 63;
-    const int lx = (pv % (WX / 2)) * 2, ly = (pv / (WX / 2)) % WY, lz = pv / ((WX / 2) * WY);
-    di_dz[i] = lz; di_dy[i] = ly; di_dx[i] = lx;
-    di_on[i] = co0 + 4 * q < Cout;
-    di_lds[i] = (4 * q) * DPLANE + ((lz * WY + ly) * WX + lx) * 2;
-    di_rel[i] = ((lz * H + ly) * W + lx) * Cout + 4 * q;
-  }
-  const float sX = xscale ? xscale[0] : 1.f, sD = dscale ? dscale[0] : 1.f;
-  // normalisation coefficients of this thread's channels, reloaded only when the sample index changes
-  float xsc[XI][4], xsh[XI][4];
-  int coef_n = -1;
-  auto load_coefs = [&](int n) {
-    if (n == coef_n) return;
-    coef_n = n;
-#pragma unroll
-    for (int i = 0; i < XI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = ci0 + xi_cb[i] + j;
-        const bool ok = scale && xi_on[i] && c < Cin && (xvec || j == 0);
-        xsc[i][j] = (ok ? scale[n * Cin + c] : 1.f) * sX;      // power-of-two range scale folded in (exact)
-        xsh[i][j] = (ok ? shift[n * Cin + c] : 0.f) * sX;
-      }
-  };
-  const int bricks_per_n = tiles_x * tiles_y * tiles_z, tiles_xy = tiles_x * tiles_y;
-  auto brick_coords = [&](long long bi64, int& n, int& x0, int& y0, int& z0) {
-    const int bi = (int)bi64;                    // < 2^31 bricks by construction
-    n = bi / bricks_per_n;
-    const int r = bi - n * bricks_per_n;
-    const int bz = r / tiles_xy, r2 = r - bz * tiles_xy;
-    const int by = r2 / tiles_x, bx = r2 - by * tiles_x;
-    x0 = bx * WX; y0 = by * WY; z0 = bz * WZ;
-  };
-  auto prefetch = [&](long long bi) {
-    int n, x0, y0, z0;
-    brick_coords(bi, n, x0, y0, z0);
-    pn = n;
-    const long long origin = (((long long)n * D + z0) * H + y0) * W + x0;     // wave-uniform
-    const float* xb = x + origin * Cmem + ci0;
-    const float* db = dz + origin * Cout + co0;
-    const float* mb = dzmask ? dzmask + origin * Cout + co0 : nullptr;
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      px[i][0] = px[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int gy = y0 + xi_dy[i], gz = z0 + xi_dz[i];
-      if (xi_on[i] && (unsigned)gy < (unsigned)H && (unsigned)gz < (unsigned)D) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int gx = x0 + xi_dx[i] + u;
-          if ((unsigned)gx < (unsigned)W) {
-            if (xvec) px[i][u] = *reinterpret_cast<const float4*>(xb + xi_rel[i] + u * Cin);
-            else px[i][u].x = (ci0 + xi_cb[i] == ones_ch) ? 1.f : xb[xi_rel[i] + u * Cmem];
-          }
-        }
-      }
-    }
-    if (dvec) {
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        const int gy = y0 + di_dy[i], gz = z0 + di_dz[i];
-        const bool rok = di_on[i] && (gy < H) && (gz < D);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int gx = x0 + di_dx[i] + u;
-          pd[i][u] = make_float4(0.f, 0.f, 0.f, 0.f);
-          pm[i][u] = make_float4(1.f, 1.f, 1.f, 1.f);
-          if (rok && gx < W) {
-            pd[i][u] = *reinterpret_cast<const float4*>(db + di_rel[i] + u * Cout);
-            if (mb) pm[i][u] = *reinterpret_cast<const float4*>(mb + di_rel[i] + u * Cout);
-          }
-        }
-      }
-    }
-  };
-  auto commit = [&](long long bi) {   // registers -> normalise / mask -> split -> transposed LDS images
-    int n, x0, y0, z0;
-    brick_coords(bi, n, x0, y0, z0);
-    load_coefs(n);
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      if (xi_on[i]) {
-        const int gy = y0 + xi_dy[i], gz = z0 + xi_dz[i];
-        const bool rowok = (unsigned)gy < (unsigned)H && (unsigned)gz < (unsigned)D;
-        const int nch = xvec ? 4 : 1;
-        float v[2][4] = {{px[i][0].x, px[i][0].y, px[i][0].z, px[i][0].w}, {px[i][1].x, px[i][1].y, px[i][1].z, px[i][1].w}};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const bool ok = rowok && (unsigned)(x0 + xi_dx[i] + u) < (unsigned)W;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (j < nch) {
-              float t = v[u][j] * xsc[i][j] + xsh[i][j];     // identity coefficients when scale == NULL
-              if (relu_in) t = fmaxf(t, 0.f);
-              v[u][j] = ok ? t : 0.f;                        // zero padding AFTER the normalisation
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < nch) {
-            float r0 = v[0][j], r1 = v[1][j];
-#pragma unroll
-            for (int t = 0; t < TERMS; ++t) {
-              float b0, b1;
-              const unsigned h0 = to16<TERMS>(r0, b0), h1 = to16<TERMS>(r1, b1);
-              *reinterpret_cast<unsigned*>(sXT + t * xt_bytes + xi_lds[i] + j * XPLANE) = h0 | (h1 << 16);
-              r0 -= b0; r1 -= b1;
-            }
-          }
-        }
-      }
-    }
-    if (dvec) {
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        float v[2][4] = {{pd[i][0].x, pd[i][0].y, pd[i][0].z, pd[i][0].w}, {pd[i][1].x, pd[i][1].y, pd[i][1].z, pd[i][1].w}};
-        const float m[2][4] = {{pm[i][0].x, pm[i][0].y, pm[i][0].z, pm[i][0].w}, {pm[i][1].x, pm[i][1].y, pm[i][1].z, pm[i][1].w}};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float r0 = (m[0][j] > 0.f) ? v[0][j] * sD : 0.f, r1 = (m[1][j] > 0.f) ? v[1][j] * sD : 0.f;
-#pragma unroll
-          for (int t = 0; t < TERMS; ++t) {
-            float b0, b1;
-            const unsigned h0 = to16<TERMS>(r0, b0), h1 = to16<TERMS>(r1, b1);
-            *reinterpret_cast<unsigned*>(sDT + t * CO * DPLANE + di_lds[i] + j * DPLANE) = h0 | (h1 << 16);
-            r0 -= b0; r1 -= b1;
-          }
-        }
-      }
-    } else {   // odd Cout: direct (unpipelined) scalar staging
-      for (int e = tid; e < (WV / 2) * CO; e += WGB_TPB) {
-        const int c = e % CO, pv = e / CO;
-        const int lx = (pv % (WX / 2)) * 2, ly = (pv / (WX / 2)) % WY, lz = pv / ((WX / 2) * WY);
-        const int gy = y0 + ly, gz = z0 + lz;
-        float r[2] = {0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int gx = x0 + lx + u;
-          if ((gx < W) & (gy < H) & (gz < D) & (co0 + c < Cout)) {
-            const long long off = ((((long long)n * D + gz) * H + gy) * W + gx) * Cout + co0 + c;
-            r[u] = (dzmask && !(dzmask[off] > 0.f)) ? 0.f : dz[off] * sD;
-          }
-        }
-        const int vox = (lz * WY + ly) * WX + lx;
-#pragma unroll
-        for (int t = 0; t < TERMS; ++t) {
-          float b0, b1;
-          const unsigned h0 = to16<TERMS>(r[0], b0), h1 = to16<TERMS>(r[1], b1);
-          *reinterpret_cast<unsigned*>(sDT + (t * CO + c) * DPLANE + vox * 2) = h0 | (h1 << 16);
-          r[0] -= b0; r[1] -= b1;
-        }
-      }
-    }
-  };
-
-  if (b_beg < b_end) prefetch(b_beg);
-  for (long long bi = b_beg; bi < b_end; ++bi) {
-    __syncthreads();            // previous brick's MFMA phase is done with the LDS images
-    commit(bi);
-    __syncthreads();
-    if (bi + 1 < b_end) prefetch(bi + 1);
-    wgrad_mfma_brick<NT, TERMS>(sXT, sDT, xt_bytes, wt, ks, KS, li, lh, acc);
-  }
-  wgrad_store_partial<NT>(partial + (((long long)slab * KS + ks) * 27) * Cin * Cout, wt, MT, CP, ci0, co0, Cin, Cout, li,
-                          lh, acc);
-}
-
-// =============================================================================================
-// Wave-specialised weight gradient (the vector path: Cin % 4 == 0, Cout % 4 == 0).  The kernel above needs ~235
-// registers per lane, i.e. ONE 512-thread workgroup per CU, so its staging (global -> normalise -> split -> transposed
-// LDS images) and its MFMA phase run back to back.  Here a 768-thread workgroup has 8 CONSUMER waves (the same tile
-// dealing and MFMA loop, no staging registers) and 4 PRODUCER waves (one per SIMD) that stage brick b+1 into the
-// other half of a double-buffered LDS image while the consumers multiply brick b: one raw s_barrier per brick, the
-// producers' global loads for brick b+2 stay in flight across it (only LDS traffic is drained at the barrier).
-constexpr int WS_CONS = 8;
-// PW producer waves: 4 (one per SIMD, 3 waves per SIMD in all: 168 registers) or 8 (two per SIMD, 128 registers: the
-// consumers of the unmasked N = 64 variant fit, and the producers -- the pole with 4 -- get twice the issue slots)
-
-__device__ __forceinline__ void ws_barrier() {
-  // LDS writes / reads of this wave are complete, outstanding GLOBAL loads are not waited for
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// DSPLIT (round 5): dz is the pre-split record tensor of kmh_maxpool3d_bwd_split -- (N, Cout/8, V + 1) records of 8 fp16 hi +
-// 8 fp16 lo terms of fmaf(dz, S, 0) -- so a producer item (4 channels of two x neighbours) is four 8-byte loads and eight
-// 16-bit packs instead of two 16-byte loads, eight multiplies and four split_pair sequences: the same words in the same
-// transposed image, bit-identical sums.
-template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false, bool AMP = false>
-__global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_wgrad_ws_kernel(
-    const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ dz, const float* __restrict__ dzmask, float* __restrict__ partial, int N, int D,
-    int H, int W, int Cin, int Cout, int relu_in, int CP, int MT, int TG, int KS, int ci_tiles, int tiles_x,
-    int tiles_y, int tiles_z, int bricks_per_slab, int nslab_total, const float* __restrict__ xscale,
-    const float* __restrict__ dscale, int dz_blocked /* dz is (N, Cout/8, D, H, W, 8) */) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smemb[];
-  constexpr int CO = 32 * NT;
-  // LDS: sXT[TERMS][CP+1][XPLANE_R] -- ONE ring image of RZ z planes (see XPLANE_R) -- then two stages of sDT[TERMS][CO][DPLANE]
-  const int xt_bytes = (CP + 1) * XPLANE_R;               // one term of sXT
-  constexpr int dt_bytes = TERMS * CO * DPLANE;           // one stage of sDT
-  unsigned char* const sXTr = smemb;
-  unsigned char* const sDT0 = smemb + TERMS * xt_bytes;
-  constexpr int WS_TPB = 64 * (WS_CONS + PW), WS_PT = 64 * PW;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int ntile = gridDim.x / nslab_total;
-  const int item = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = item % ntile, slab = item / ntile;
-  const int cit = tile % ci_tiles, cog = tile / ci_tiles;
-  const int ci0 = cit * CP, co0 = cog * CO;
-
-  // zero plane (padded M rows) of every term: all RZ ring planes of it
-  for (int e = tid; e < TERMS * (XPLANE_R / 4); e += WS_TPB) {
-    const int t = e / (XPLANE_R / 4), o = e - t * (XPLANE_R / 4);
-    reinterpret_cast<unsigned*>(sXTr + t * xt_bytes + CP * XPLANE_R)[o] = 0u;
-  }
-  // slabs never straddle samples (nslab_total = N * slabs per sample): the reduce kernel can then give per-sample sums
-  const int bricks_per_n = tiles_x * tiles_y * tiles_z;
-  const int slabs_per_n = nslab_total / N;
-  const long long b_base = (long long)(slab / slabs_per_n) * bricks_per_n;
-  const long long b_beg = b_base + (long long)(slab % slabs_per_n) * bricks_per_slab;
-  long long b_end = b_beg + bricks_per_slab;
-  if (b_end > b_base + bricks_per_n) b_end = b_base + bricks_per_n;
-  if (b_beg >= b_end) return;                             // uniform over the workgroup
-  auto brick_coords = [&](long long bi64, int& n, int& x0, int& y0, int& z0) {
-    const int bi = (int)bi64;
-    n = bi / bricks_per_n;
-    const int r = bi - n * bricks_per_n;                   // z fastest: consecutive bricks share two halo planes
-    const int col = r / tiles_z, bz = r - col * tiles_z;
-    const int by = col / tiles_x, bx = col - by * tiles_x;
-    x0 = bx * WX; y0 = by * WY; z0 = bz * WZ;
-  };
-  // ring base of a brick: + 2 planes per brick inside a z column, + 4 at the first brick of a column (which fills all four
-  // planes of its window); producers and consumers advance it by the same rule
-  const int cz_first = (int)((b_beg - b_base) % tiles_z);
-
-  // (Round 6, measured and removed -- profiles/r6e_wgrad_prio_order_ab.txt: s_setprio 2 on the consumer waves: flat; on the
-  // producer waves: 1-10 % slower (the consumers' stream is the critical path); term-major MFMA order over a row's
-  // accumulators instead of three products of one accumulator back to back: flat.)
-  if (wv >= WS_CONS) {
-    // ------------------------------------------------------------------------------ producers
-    const int pt = tid - 64 * WS_CONS;
-    const int cq = CP >> 2;                               // channel quads per voxel
-    const int x_per_row = 9 * cq;
-    // x items of HALF a halo window (2 planes = 12 rows): set 0 = planes 2, 3 (the NEW planes of every brick), set 1 = planes
-    // 0, 1 (fetched only by the first brick of a z column).  Same (ly, pair, channels) in both sets: lz differs by 2.
-    const int x_items = 2 * WHY * x_per_row;              // <= 432
-    constexpr int XH = (432 + WS_PT - 1) / WS_PT;         // items per thread and half: 1 (PW = 8) or 2
-    constexpr int XI = 2 * XH;                            // register sets: [0, XH) = set 0, [XH, 2 XH) = set 1
-    constexpr int DI = (WV / 2) * (CO / 4) / WS_PT;       // 4 (NT = 2) or 2
-    int xi_pk[XI], xi_lds[XI];                     // pk = lz | ly << 4 | (2 pr) << 8 | cb << 16 | on << 30 (halo coords)
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const int e = pt + (i % XH) * WS_PT;
-      const int rowh = e / x_per_row, rem = e - rowh * x_per_row;
-      const int cpart = rem / 9, pr = rem - cpart * 9;
-      const int lzh = rowh / WHY, ly = rowh - lzh * WHY;
-      const int lz = lzh + (i < XH ? 2 : 0);
-      const int cb = 4 * cpart;
-      const bool on = (e < x_items) && (ci0 + cb < Cin);
-      xi_pk[i] = on ? (lz | (ly << 4) | ((2 * pr) << 8) | (cb << 16) | (1 << 30)) : 0;   // off: loads a valid dummy
-      xi_lds[i] = cb * XPLANE_R + (ly * XPITCH_R + 2 * pr) * 2;                               // + the ring plane's ZSLOT, per brick
-    }
-    int di_pk[DI], di_lds[DI], di_q4[DI];
-#pragma unroll
-    for (int i = 0; i < DI; ++i) {
-      const int e = pt + i * WS_PT;
-      const int q = (e & 3) + 4 * (e >> 8), pv = (e >> 2) & 63;
-      const int lx = (pv % (WX / 2)) * 2, ly = (pv / (WX / 2)) % WY, lz = pv / ((WX / 2) * WY);
-      const bool on = co0 + 4 * q < Cout;
-      di_pk[i] = lz | (ly << 4) | (lx << 8) | (on ? (1 << 30) : 0);
-      di_lds[i] = (4 * q) * DPLANE + ((lz * WY + ly) * WX + lx) * 2;
-      di_q4[i] = on ? 4 * q : 0;                          // off: loads a valid dummy, writes zeros
-      // channel-blocked dz: element offset of the quad inside the sample = (chunk plane) + voxel * 8 + (quad in chunk)
-      if (dz_blocked) di_q4[i] = on ? ((co0 + 4 * q) >> 3) * (D * H * W * 8) + ((4 * q) & 7) : 0;
-      // pre-split records: planes of V + 1 records of 8 floats; the quad's four fp16 hi terms are floats (quad in chunk) / 2 ..
-      // + 1 of the record, its lo terms 4 floats further
-      if (DSPLIT) di_q4[i] = on ? ((co0 + 4 * q) >> 3) * ((D * H * W + 1) * 8) + (((4 * q) & 7) >> 1) : 0;
-    }
-    const int dstride = (dz_blocked || DSPLIT) ? 8 : Cout;      // floats between x neighbours of one dz quad
-    const float sX = xscale ? xscale[0] : 1.f, sD = dscale ? dscale[0] : 1.f;
-    float4 px[XI][2], pd[DI][2], pm[MASK ? DI : 1][2];
-
-    // Loads are unconditional: halo coordinates are clamped into the volume (the value is zeroed at conversion time
-    // when the true coordinate was outside), so a brick's 16 (+8 mask) 16-byte loads per thread go out back to back.
-    // Element offsets inside one sample are 24-bit multiply-adds (the launcher checks D*H*W*C < 2^31).
-    auto issue = [&](int n, int x0, int y0, int z0, bool col_start) {
-      const int xn_sets = col_start ? XI : XH;             // uniform: a column's first brick fetches all four planes
-      const float* xn = x + (long long)n * D * H * W * Cin + ci0;
-      const float* dn = DSPLIT ? dz + (long long)n * (Cout >> 3) * ((long long)D * H * W + 1) * 8
-                               : dz + (long long)n * D * H * W * Cout + (dz_blocked ? 0 : co0);
-      const float* mn = MASK ? dzmask + (long long)n * D * H * W * Cout + co0 : nullptr;
-      // all element offsets first, then the loads back to back
-      unsigned xo[XI][2], dO[DI][2];
-#pragma unroll
-      for (int i = 0; i < XI; ++i) {
-        if (i >= xn_sets) break;
-        const int gz = min(max(z0 + (xi_pk[i] & 15) - 1, 0), D - 1), gy = min(max(y0 + ((xi_pk[i] >> 4) & 15) - 1, 0), H - 1);
-        const int gx0 = x0 + ((xi_pk[i] >> 8) & 255) - 1, cb = (xi_pk[i] >> 16) & 255;
-        const unsigned row = __umul24(__umul24(gz, H) + gy, W);
-        xo[i][0] = __umul24(row + min(max(gx0, 0), W - 1), Cin) + cb;
-        xo[i][1] = __umul24(row + min(max(gx0 + 1, 0), W - 1), Cin) + cb;
-      }
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        const int gz = min(z0 + (di_pk[i] & 15), D - 1), gy = min(y0 + ((di_pk[i] >> 4) & 15), H - 1);
-        const int gx0 = x0 + ((di_pk[i] >> 8) & 255);
-        const unsigned row = __umul24(__umul24(gz, H) + gy, W);
-        dO[i][0] = __umul24(row + min(gx0, W - 1), dstride) + di_q4[i];
-        dO[i][1] = __umul24(row + min(gx0 + 1, W - 1), dstride) + di_q4[i];
-      }
-#pragma unroll
-      for (int i = 0; i < XI; ++i) {
-        if (i >= xn_sets) break;
-        px[i][0] = *reinterpret_cast<const float4*>(xn + xo[i][0]);
-        px[i][1] = *reinterpret_cast<const float4*>(xn + xo[i][1]);
-      }
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        if constexpr (DSPLIT) {        // (hi.x, hi.y, lo.x, lo.y): 4 + 4 fp16 terms of the voxel's channel quad
-          const float2 h0 = *reinterpret_cast<const float2*>(dn + dO[i][0]), l0 = *reinterpret_cast<const float2*>(dn + dO[i][0] + 4);
-          const float2 h1 = *reinterpret_cast<const float2*>(dn + dO[i][1]), l1 = *reinterpret_cast<const float2*>(dn + dO[i][1] + 4);
-          pd[i][0] = make_float4(h0.x, h0.y, l0.x, l0.y);
-          pd[i][1] = make_float4(h1.x, h1.y, l1.x, l1.y);
-          continue;
-        }
-        pd[i][0] = *reinterpret_cast<const float4*>(dn + dO[i][0]);
-        pd[i][1] = *reinterpret_cast<const float4*>(dn + dO[i][1]);
-        if (MASK) {
-          pm[i][0] = *reinterpret_cast<const float4*>(mn + dO[i][0]);
-          pm[i][1] = *reinterpret_cast<const float4*>(mn + dO[i][1]);
-        }
-      }
-    };
-    // (n, channel) normalisation coefficients of this workgroup's CP channels, pre-multiplied by the range scale:
-    // a small LDS table behind the two stages, rewritten (by every producer wave for itself: LDS operations of one
-    // wave are ordered, and the waves write identical values) when the sample index changes
-    float* ctab = reinterpret_cast<float*>(sDT0 + 2 * dt_bytes);
-    int tab_n = -1;
-    const float relu_lo = relu_in ? 0.f : -INFINITY;
-    // Keeps every use of the staged registers behind the barrier: register-only work may otherwise be hoisted above
-    // the (volatile, but not register-clobbering) barrier statement, and the wait for the loads with it.
-    auto pin = [](float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); };
-    auto convert = [&](int n, int x0, int y0, int z0, unsigned char* sXT, unsigned char* sDT, int ring_base, bool col_start) {
-      const int xn_sets = col_start ? XI : XH;
-      if (n != tab_n) {
-        tab_n = n;
-        if (lane < 2 * CP) {
-          const int c = ci0 + (lane % CP);
-          float v = lane < CP ? sX : 0.f;
-          if (scale && c < Cin) v = (lane < CP ? scale[(long long)n * Cin + c] : shift[(long long)n * Cin + c]) * sX;
-          ctab[lane] = v;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < XI; ++i) {
-        if (i >= xn_sets) break;
-        const int zdst = ((ring_base + (xi_pk[i] & 15)) & (RZ - 1)) * ZSLOT;      // this halo plane's place in the ring
-        const int gz = z0 + (xi_pk[i] & 15) - 1, gy = y0 + ((xi_pk[i] >> 4) & 15) - 1;
-        const int gx0 = x0 + ((xi_pk[i] >> 8) & 255) - 1, cb = (xi_pk[i] >> 16) & 255;
-        const bool rowok = (unsigned)gy < (unsigned)H && (unsigned)gz < (unsigned)D;
-        const float4 sc4 = *reinterpret_cast<const float4*>(ctab + cb);
-        const float4 sh4 = *reinterpret_cast<const float4*>(ctab + CP + cb);
-        const float sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
-        float v[2][4] = {{px[i][0].x, px[i][0].y, px[i][0].z, px[i][0].w}, {px[i][1].x, px[i][1].y, px[i][1].z, px[i][1].w}};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const bool ok = rowok && (unsigned)(gx0 + u) < (unsigned)W;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float t = fmaxf(v[u][j] * sc[j] + sh[j], relu_lo);
-            v[u][j] = ok ? t : 0.f;                        // zero padding AFTER the normalisation
-          }
-        }
-        if (xi_pk[i] >> 30) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            unsigned w[TERMS];
-            split_pair<TERMS>(v[0][j], v[1][j], w);
-#pragma unroll
-            for (int t = 0; t < TERMS; ++t)
-              *reinterpret_cast<unsigned*>(sXT + t * xt_bytes + xi_lds[i] + zdst + j * XPLANE_R) = w[t];
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        const int gz = z0 + (di_pk[i] & 15), gy = y0 + ((di_pk[i] >> 4) & 15), gx0 = x0 + ((di_pk[i] >> 8) & 255);
-        const bool rok = (di_pk[i] >> 30) && gy < H && gz < D;
-        if constexpr (DSPLIT) {
-          // words of the transposed image: (voxel 0 | voxel 1 << 16) per channel and term
-          static_assert(TERMS == 2 && !MASK, "pre-split records are fp16 hi / lo, already masked");
-          const bool k0 = rok && gx0 < W, k1 = rok && gx0 + 1 < W;
-          unsigned a[4] = {__float_as_uint(pd[i][0].x), __float_as_uint(pd[i][0].y), __float_as_uint(pd[i][0].z), __float_as_uint(pd[i][0].w)};
-          unsigned b[4] = {__float_as_uint(pd[i][1].x), __float_as_uint(pd[i][1].y), __float_as_uint(pd[i][1].z), __float_as_uint(pd[i][1].w)};
-#pragma unroll
-          for (int u = 0; u < 4; ++u) { a[u] = k0 ? a[u] : 0u; b[u] = k1 ? b[u] : 0u; }
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const unsigned av = a[2 * t + (j >> 1)], bv = b[2 * t + (j >> 1)];
-              const unsigned wd = (j & 1) ? ((av >> 16) | (bv & 0xffff0000u)) : ((av & 0xffffu) | (bv << 16));
-              *reinterpret_cast<unsigned*>(sDT + t * CO * DPLANE + di_lds[i] + j * DPLANE) = wd;
-            }
-          continue;
-        }
-        float v[2][4] = {{pd[i][0].x, pd[i][0].y, pd[i][0].z, pd[i][0].w}, {pd[i][1].x, pd[i][1].y, pd[i][1].z, pd[i][1].w}};
-        float m[2][4] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}};
-        if (MASK) {
-          m[0][0] = pm[i][0].x; m[0][1] = pm[i][0].y; m[0][2] = pm[i][0].z; m[0][3] = pm[i][0].w;
-          m[1][0] = pm[i][1].x; m[1][1] = pm[i][1].y; m[1][2] = pm[i][1].z; m[1][3] = pm[i][1].w;
-        }
-        const bool ok0 = rok && gx0 < W, ok1 = rok && gx0 + 1 < W;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float r0 = (ok0 && m[0][j] > 0.f) ? v[0][j] * sD : 0.f, r1 = (ok1 && m[1][j] > 0.f) ? v[1][j] * sD : 0.f;
-          unsigned w[TERMS];
-          split_pair<TERMS>(r0, r1, w);
-#pragma unroll
-          for (int t = 0; t < TERMS; ++t)
-            *reinterpret_cast<unsigned*>(sDT + t * CO * DPLANE + di_lds[i] + j * DPLANE) = w[t];
-        }
-      }
-    };
-
-    // brick coordinates advance incrementally (z fastest, then x, y; a slab stays inside one sample): no divisions in the loop
-    int cn, cx, cy, cz;
-    {
-      int x0, y0, z0;
-      brick_coords(b_beg, cn, x0, y0, z0);
-      cx = x0 / WX; cy = y0 / WY; cz = z0 / WZ;
-    }
-    int rbase = 0;                                        // ring base of the brick whose loads are in flight
-    bool cstart = true;                                   // ... and whether it is the first of its column (here: of the slab)
-    issue(cn, cx * WX, cy * WY, cz * WZ, true);
-    for (long long bi = b_beg; bi < b_end; ++bi) {
-      unsigned char* sDTs = sDT0 + ((bi - b_beg) & 1) * dt_bytes;
-      const int pn = cn, px0 = cx * WX, py0 = cy * WY, pz0 = cz * WZ;      // the brick whose loads are in flight
-      const int pbase = rbase;
-      const bool pstart = cstart;
-      cstart = false;
-      if (++cz == tiles_z) { cz = 0; cstart = true; if (++cx == tiles_x) { cx = 0; if (++cy == tiles_y) { cy = 0; ++cn; } } }
-      rbase = (rbase + (cstart ? 4 : 2)) & (RZ - 1);
-#pragma unroll
-      for (int i = 0; i < XI; ++i) { pin(px[i][0]); pin(px[i][1]); }
-#pragma unroll
-      for (int i = 0; i < DI; ++i) {
-        pin(pd[i][0]); pin(pd[i][1]);
-        if (MASK) { pin(pm[i][0]); pin(pm[i][1]); }
-      }
-      convert(pn, px0, py0, pz0, sXTr, sDTs, pbase, pstart);                 // waits for the loads of brick bi only
-      if (bi + 1 < b_end) issue(cn, cx * WX, cy * WY, cz * WZ, cstart);      // in flight across the barrier
-      ws_barrier();
-    }
-    return;
-  }
-
-  // -------------------------------------------------------------------------------- consumers
-  const int tg = wv % TG, ks = wv / TG;
-  const WgradTiles wt = wgrad_deal_tiles(CP, MT, TG, tg, li, lh, true);
-  f32x16 acc[MTWB][NT];
-#pragma unroll
-  for (int j = 0; j < MTWB; ++j)
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][t][r] = 0.f;
-
-  ws_barrier();                                            // brick b_beg is staged (and the zero planes written)
-  auto bricks = [&](auto mode) {
-    int rbase = 0, cz = cz_first;                           // as the producers count them
-    for (long long bi = b_beg; bi < b_end; ++bi) {
-      const unsigned char* sDT = sDT0 + ((bi - b_beg) & 1) * dt_bytes;
-      wgrad_mfma_brick<NT, TERMS, decltype(mode)::value, AMP, true>(sXTr, sDT, xt_bytes, wt, ks, KS, li, lh, acc, rbase);
-      const bool nstart = ++cz == tiles_z;
-      if (nstart) cz = 0;
-      rbase = (rbase + (nstart ? 4 : 2)) & (RZ - 1);
-      if (bi + 1 < b_end) ws_barrier();                    // brick bi+1 is staged: its ring planes and the other sDT stage
-    }
-  };
-  // the paired dealing (CP = 16) fixes every wave's tap x offsets: waves 0-4 hold (kx 0, kx 1) of one slot, waves
-  // 5-7 two kx = 2 tiles (an absent sixth one reads the zero plane, whatever its shift)
-  if (TG == 8 && MT == 15) {
-    if (tg < 5) bricks(std::integral_constant<int, 1>{});
-    else bricks(std::integral_constant<int, 2>{});
-  } else {
-    bricks(std::integral_constant<int, 0>{});
-  }
-  wgrad_store_partial<NT>(partial + (((long long)slab * KS + ks) * 27) * Cin * Cout, wt, MT, CP, ci0, co0, Cin, Cout, li,
-                          lh, acc);
-}
-
-__global__ __launch_bounds__(256) void wgrad_bf_reduce_kernel(const float* __restrict__ partial, int nslab, int Cin,
-                                                              int Cout, float* __restrict__ dw, int accumulate,
-                                                              const float* __restrict__ xscale,
-                                                              const float* __restrict__ dscale) {
-  const double desc = (double)(xscale ? xscale[1] : 1.f) * (double)(dscale ? dscale[1] : 1.f);
-  const long long total = (long long)27 * Cin * Cout;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    double s = 0;
-    for (int k = 0; k < nslab; ++k) s += partial[(long long)k * total + e];
-    const int co = (int)(e % Cout), ci = (int)((e / Cout) % Cin), tap = (int)(e / ((long long)Cout * Cin));
-    const long long o = ((long long)co * Cin + ci) * 27 + tap;
-    dw[o] = accumulate ? dw[o] + (float)(s * desc) : (float)(s * desc);
-  }
-}
-
-// Reduce + fold: dw as above, and, from the PER-SAMPLE sums the slab order allows,
-//   bhat[n][ci] = sum_{tap, co} w[co][ci][tap] * dWn[n][tap][ci][co]  =  sum_v dxn[n][v][ci] * xhat[n][v][ci]
-// (dxn = the data gradient of the same dz, xhat = the convolution's input): GroupNorm's second backward statistic
-// without a pass over dxn and x.  Block = (ci, tap triple); bhat must be zero on entry.
-// 1024 threads = LP columns (the next power of two >= 3 Cout, capped at 1024) x S = 1024 / LP slices of the slabs: the
-// slab sums are strided reads 27 Cin Cout floats apart, and one thread walking all of them ran at 1.1 TB/s.
-__global__ __launch_bounds__(1024) void wgrad_bf_reduce_fold_kernel(const float* __restrict__ partial, int N, int per_n,
-                                                                    int Cin, int Cout, float* __restrict__ dw,
-                                                                    int accumulate, const float* __restrict__ xscale,
-                                                                    const float* __restrict__ dscale,
-                                                                    const float* __restrict__ w,
-                                                                    double* __restrict__ bhat, int LP) {
-  const double desc = (double)(xscale ? xscale[1] : 1.f) * (double)(dscale ? dscale[1] : 1.f);
-  const long long total = (long long)27 * Cin * Cout;
-  const int ci = blockIdx.x, t3 = blockIdx.y;
-  __shared__ double red[1024];
-  __shared__ double wred[1024 / kWave];
-  const int S = 1024 / LP, lcol = threadIdx.x % LP, sl = threadIdx.x / LP;
-  const int L = 3 * Cout;
-  for (int l0 = 0; l0 < L; l0 += LP) {                      // (one pass unless 3 Cout > 1024)
-    const int l = l0 + lcol;
-    const bool act = l < L;
-    const int tap = 3 * t3 + (act ? l / Cout : 0), co = act ? l % Cout : 0;
-    const long long e = ((long long)tap * Cin + ci) * Cout + co;
-    const long long o = ((long long)co * Cin + ci) * 27 + tap;
-    const double wv = act ? (double)w[o] : 0.0;
-    double tot = 0;
-    for (int n = 0; n < N; ++n) {
-      double sn = 0;
-      if (act)
-        for (int k = sl; k < per_n; k += S) sn += partial[((long long)n * per_n + k) * total + e];
-      __syncthreads();
-      red[threadIdx.x] = sn;
-      __syncthreads();
-      double bn = 0;
-      if (sl == 0 && act) {
-        sn = 0;
-        for (int q = 0; q < S; ++q) sn += red[q * LP + lcol];      // fixed order
-        tot += sn;
-        bn = wv * sn * desc;
-      }
-      const double r = block_sum<double>(bn, wred);
-      if (threadIdx.x == 0) atomicAdd(bhat + (long long)n * Cin + ci, r);
-    }
-    if (sl == 0 && act) dw[o] = accumulate ? dw[o] + (float)(tot * desc) : (float)(tot * desc);
-  }
-}
-
-struct WgradBfPlan {
-  int CP, MT, TG, KS, ci_tiles, co_groups, NT, tiles_x, tiles_y, tiles_z, nslab, bricks_per_slab;
-  long long nbricks;
-  size_t lds;        // one stage of conv3_wgrad_bf_kernel
-  size_t lds_ws;     // conv3_wgrad_ws_kernel: the ring x image + two dz stages + the coefficient table
-};
-
-static WgradBfPlan wgrad_bf_plan(int N, int D, int H, int W, int Cin, int Cout, int terms) {
-  WgradBfPlan p;
-  p.CP = 1;
-  while (p.CP < Cin && p.CP < 16) p.CP <<= 1;
-  p.ci_tiles = (Cin + p.CP - 1) / p.CP;
-  {
-    const int tpt = 32 / p.CP;
-    p.MT = 3 * ((9 + tpt - 1) / tpt);            // uniform-kx tiles: 15 (CP=16), 9, 6, 3, 3
-  }
-  p.TG = 1;
-  while (p.TG < 8 && p.TG < p.MT) p.TG <<= 1;
-  p.KS = 8 / p.TG;
-  p.NT = Cout > 32 ? 2 : 1;
-  p.co_groups = (Cout + 32 * p.NT - 1) / (32 * p.NT);
-  p.tiles_x = (W + WX - 1) / WX; p.tiles_y = (H + WY - 1) / WY; p.tiles_z = (D + WZ - 1) / WZ;
-  p.nbricks = (long long)N * p.tiles_x * p.tiles_y * p.tiles_z;
-  // ~768 workgroups in all; a slab is a run of bricks of ONE sample
-  const long long bricks_per_n = (long long)p.tiles_x * p.tiles_y * p.tiles_z;
-  long long want = 768 / ((long long)p.ci_tiles * p.co_groups * N);
-  if (want < 1) want = 1;
-  if (want > bricks_per_n) want = bricks_per_n;
-  p.bricks_per_slab = (int)((bricks_per_n + want - 1) / want);
-  p.nslab = N * (int)((bricks_per_n + p.bricks_per_slab - 1) / p.bricks_per_slab);
-  p.lds = (size_t)terms * ((size_t)(p.CP + 1) * XPLANE + (size_t)32 * p.NT * DPLANE);
-  p.lds_ws = (size_t)terms * ((size_t)(p.CP + 1) * XPLANE_R + 2 * (size_t)32 * p.NT * DPLANE) + 256;
-  return p;
-}
-
-template <int NT, int TERMS>
-static int launch_wgrad_bf(const WgradBfPlan& p, const float* x, const float* scale, const float* shift,
-                           const float* dz, const float* dzmask, float* ws, int N, int D, int H, int W, int Cin,
-                           int Cout, int relu_in, int Cmem, int ones_ch, const float* xscale, const float* dscale,
-                           hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_bf_kernel<NT, TERMS>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-  if (e != hipSuccess) return (int)e;
-  dim3 g(p.ci_tiles * p.co_groups * p.nslab);
-  conv3_wgrad_bf_kernel<NT, TERMS><<<g, WGB_TPB, p.lds, s>>>(x, scale, shift, dz, dzmask, ws, N, D, H, W, Cin, Cout,
-                                                            relu_in, p.CP, p.MT, p.TG, p.KS, p.ci_tiles, p.tiles_x,
-                                                            p.tiles_y, p.tiles_z, p.bricks_per_slab, p.nslab, Cmem,
-                                                            ones_ch, xscale, dscale);
-  return KMH_LAUNCH_CHECK();
-}
-
-template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false>
-static int launch_wgrad_ws(const WgradBfPlan& p, const float* x, const float* scale, const float* shift,
-                           const float* dz, const float* dzmask, float* ws, int N, int D, int H, int W, int Cin,
-                           int Cout, int relu_in, const float* xscale, const float* dscale, int dz_blocked, hipStream_t s) {
-  const size_t lds = p.lds_ws;                             // ring x image, two dz stages, the coefficient table
-  hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  dim3 g(p.ci_tiles * p.co_groups * p.nslab);
-  if constexpr (!MASK && PW == 8) {
-    if (kmh_amp_enabled()) {
-      e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, true><<<g, 64 * (WS_CONS + PW), lds, s>>>(
-          x, scale, shift, dz, dzmask, ws, N, D, H, W, Cin, Cout, relu_in, p.CP, p.MT, p.TG, p.KS, p.ci_tiles, p.tiles_x, p.tiles_y,
-          p.tiles_z, p.bricks_per_slab, p.nslab, xscale, dscale, dz_blocked);
-      return KMH_LAUNCH_CHECK();
-    }
-  }
-  conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT><<<g, 64 * (WS_CONS + PW), lds, s>>>(x, scale, shift, dz, dzmask, ws, N, D, H, W, Cin, Cout,
-                                                               relu_in, p.CP, p.MT, p.TG, p.KS, p.ci_tiles, p.tiles_x,
-                                                               p.tiles_y, p.tiles_z, p.bricks_per_slab, p.nslab, xscale,
-                                                               dscale, dz_blocked);
-  return KMH_LAUNCH_CHECK();
-}
-
-}  // namespace
-
-// the wave-specialised kernel's preconditions (vector path of the f16x3 mode)
-static bool wgrad_ws_ok(const WgradBfPlan& p, int D, int H, int W, int Cin, int Cout, int terms) {
-  static const bool no_ws = getenv("KEYMORPH_WGRAD_NO_WS") != nullptr;     // A/B measurements only
-  return !no_ws && terms == 2 && p.CP >= 4 && (Cin & 3) == 0 && (Cout & 3) == 0 && p.lds_ws <= 160 * 1024 &&
-         (long long)D * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31) &&
-         (long long)D * H * W <= (1ll << 24);   // 24-bit multiply-adds index the voxels of one sample
-}
-
-/* 1 when kmh_conv3d_wgrad_bf accepts a channel-blocked dz, (N, Cout/8, D, H, W, 8), for this shape */
-KMH_API int kmh_conv3d_wgrad_bf_blocked_ok(int N, int D, int H, int W, int Cin, int Cout, int terms) {
-  const WgradBfPlan p = wgrad_bf_plan(N, D, H, W, Cin, Cout, terms);
-  return (Cout & 7) == 0 && wgrad_ws_ok(p, D, H, W, Cin, Cout, terms) ? 1 : 0;
-}
-
-KMH_API size_t kmh_conv3d_wgrad_bf_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int terms) {
-  const WgradBfPlan p = wgrad_bf_plan(N, D, H, W, Cin, Cout, terms);
-  return (size_t)p.nslab * p.KS * 27 * Cin * Cout * sizeof(float);
-}
-
-/* append_ones != 0: x has Cin-1 real channels in memory and a virtual last channel that reads 1 inside the volume
- * (0 in the zero padding); dw then has Cin logical input channels.  With scale == NULL this yields, per output
- * channel and tap, R = sum_v x[v+tap] dz[v] and S = sum_v [v+tap inside] dz[v] in ONE pass. */
-KMH_API int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float* shift, const float* dz,
-                                const float* dzmask, float* dw, int N, int D, int H, int W, int Cin, int Cout,
-                                int relu_in, int accumulate, int terms, int append_ones, const float* xscale,
-                                const float* dscale, int dz_blocked, const float* w_fold, double* bhat, void* ws,
-                                void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
-  hipStream_t s = (hipStream_t)stream;
-  if ((w_fold == nullptr) != (bhat == nullptr)) return -22;
-  const WgradBfPlan p = wgrad_bf_plan(N, D, H, W, Cin, Cout, terms);
-  if (dz_blocked && (dzmask || !kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, terms))) return -22;
-  if (dz_blocked == 2 && (terms != 2 || ((long long)D * H * W + 1) * (Cout > Cin ? Cout : Cin) >= (1ll << 31))) return -22;
-  if (p.MT > p.TG * MTWB || (terms != 2 && terms != 3)) return -22;
-  const int Cmem = append_ones ? Cin - 1 : Cin, ones_ch = append_ones ? Cin - 1 : -1;
-  if (append_ones && (scale || Cin > 4)) return -22;
-  int rc;
-  if (terms == 2 && (!xscale || !dscale)) return -22;      // fp16 split without range scaling is not accurate
-#define KMH_WG_CALL(NT_, T_) launch_wgrad_bf<NT_, T_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, Cmem, ones_ch, xscale, dscale, s)
-  // wave-specialised kernel (producer / consumer waves, double-buffered LDS): vector path of the f16x3 mode
-  const bool ws_ok = wgrad_ws_ok(p, D, H, W, Cin, Cout, terms) && !append_ones;
-#define KMH_WS_CALL(NT_, M_, PW_) launch_wgrad_ws<NT_, 2, M_, PW_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, dz_blocked, s)
-  static const int pw = getenv("KEYMORPH_WGRAD_PRODUCERS") ? atoi(getenv("KEYMORPH_WGRAD_PRODUCERS")) : 8;
-  if (ws_ok && dz_blocked == 2) {      // pre-split dz records (kmh_maxpool3d_bwd_split)
-    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s)
-                   : launch_wgrad_ws<1, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s);
-  } else if (ws_ok) {
-    if (p.NT == 2) rc = dzmask ? KMH_WS_CALL(2, true, 4) : (pw == 8 ? KMH_WS_CALL(2, false, 8) : KMH_WS_CALL(2, false, 4));
-    else rc = dzmask ? KMH_WS_CALL(1, true, 4) : (pw == 8 ? KMH_WS_CALL(1, false, 8) : KMH_WS_CALL(1, false, 4));
-  } else if (p.NT == 2) rc = terms == 2 ? KMH_WG_CALL(2, 2) : KMH_WG_CALL(2, 3);
-  else rc = terms == 2 ? KMH_WG_CALL(1, 2) : KMH_WG_CALL(1, 3);
-#undef KMH_WS_CALL
-#undef KMH_WG_CALL
-  if (rc) return rc;
-  const long long total = (long long)27 * Cin * Cout;
-  int nb = ceil_div(total, 256);
-  if (nb > 2048) nb = 2048;
-  if (bhat)
-  {
-    int LP = 64;
-    while (LP < 3 * Cout && LP < 1024) LP <<= 1;
-    wgrad_bf_reduce_fold_kernel<<<dim3(Cin, 9), 1024, 0, s>>>((const float*)ws, N, (p.nslab / N) * p.KS, Cin, Cout, dw,
-                                                              accumulate, xscale, dscale, w_fold, bhat, LP);
-  }
-  else
-    wgrad_bf_reduce_kernel<<<nb, 256, 0, s>>>((const float*)ws, p.nslab * p.KS, Cin, Cout, dw, accumulate, xscale, dscale);
-  return KMH_LAUNCH_CHECK();
-}
-
-#endif   // KMH_TU_WGRAD
-#if !KMH_TU_WGRAD
-// First-layer fold (Cin = 1, GroupNorm over the single input channel): from the raw correlations of ONE sample
-//   rs (Cout, 2, 27): rs[co][0][tap] = R = sum_v x[v+tap] dz[v][co],  rs[co][1][tap] = S = sum_v [inside] dz[v][co]
-// produce  dw (+)= scale*R + shift*S   (the gradient wrt the filter applied to the NORMALISED input) and
-//          ab = (A, B) = (sum dxn, sum dxn*x) = (sum_{co,tap} W S, sum_{co,tap} W R)  without ever forming dxn.
-namespace {
-template <typename RS>
-__global__ __launch_bounds__(256) void first_layer_fold_kernel(const RS* __restrict__ rs, const float* __restrict__ w,
-                                                               const float* __restrict__ scale,
-                                                               const float* __restrict__ shift, int Cout,
-                                                               float* __restrict__ dw, double* __restrict__ ab,
-                                                               int accumulate) {
-  const float sc = scale[0], sh = shift[0];
-  double a = 0, b = 0;
-  for (int e = threadIdx.x; e < Cout * 27; e += 256) {
-    const int co = e / 27, tap = e % 27;
-    const RS R = rs[(co * 2 + 0) * 27 + tap], S = rs[(co * 2 + 1) * 27 + tap];      // (fp64 from the dedicated kernel)
-    const float g = (float)((RS)sc * R + (RS)sh * S);
-    dw[e] = accumulate ? dw[e] + g : g;
-    a += (double)w[e] * (double)S;
-    b += (double)w[e] * (double)R;
-  }
-  __shared__ double red[4];
-  a = block_sum<double>(a, red);
-  b = block_sum<double>(b, red);
-  if (threadIdx.x == 0) { ab[0] = a; ab[1] = b; }
-}
-}  // namespace
-
-/* rs_f64 != 0: rs holds doubles (what kmh_conv3d_first_layer_wgrad writes: GroupNorm's sums over the whole volume cancel to
- * ~1e-3 of their terms, so the correlations are kept in fp64 until they are folded); 0: floats (the split-operand weight
- * gradient over the virtual 2-channel input, Cout > 16) */
-KMH_API int kmh_conv3d_first_layer_fold(const void* rs, int rs_f64, const float* w, const float* scale_n, const float* shift_n,
-                                        int Cout, float* dw, double* ab_n, int accumulate, void* stream) {
-  if (rs_f64)
-    first_layer_fold_kernel<double><<<1, 256, 0, (hipStream_t)stream>>>((const double*)rs, w, scale_n, shift_n, Cout, dw, ab_n, accumulate);
-  else
-    first_layer_fold_kernel<float><<<1, 256, 0, (hipStream_t)stream>>>((const float*)rs, w, scale_n, shift_n, Cout, dw, ab_n, accumulate);
-  return KMH_LAUNCH_CHECK();
-}
-
-#endif   // !KMH_TU_WGRAD

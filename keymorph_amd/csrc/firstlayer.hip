@@ -617,3 +617,43 @@ KMH_API int kmh_conv3d_first_layer_wgrad(const float* x, const float* dz, const 
   first_wgrad_reduce_kernel<<<dim3(ceil_div(per, 4), N), 256, 0, s>>>((const float*)ws, D * yt * FL_XS, per, rs);
   return KMH_LAUNCH_CHECK();
 }
+
+// First-layer fold (Cin = 1, GroupNorm over the single input channel): from the raw correlations of ONE sample
+//   rs (Cout, 2, 27): rs[co][0][tap] = R = sum_v x[v+tap] dz[v][co],  rs[co][1][tap] = S = sum_v [inside] dz[v][co]
+// produce  dw (+)= scale*R + shift*S   (the gradient wrt the filter applied to the NORMALISED input) and
+//          ab = (A, B) = (sum dxn, sum dxn*x) = (sum_{co,tap} W S, sum_{co,tap} W R)  without ever forming dxn.
+namespace {
+template <typename RS>
+__global__ __launch_bounds__(256) void first_layer_fold_kernel(const RS* __restrict__ rs, const float* __restrict__ w,
+                                                               const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, int Cout,
+                                                               float* __restrict__ dw, double* __restrict__ ab,
+                                                               int accumulate) {
+  const float sc = scale[0], sh = shift[0];
+  double a = 0, b = 0;
+  for (int e = threadIdx.x; e < Cout * 27; e += 256) {
+    const int co = e / 27, tap = e % 27;
+    const RS R = rs[(co * 2 + 0) * 27 + tap], S = rs[(co * 2 + 1) * 27 + tap];      // (fp64 from the dedicated kernel)
+    const float g = (float)((RS)sc * R + (RS)sh * S);
+    dw[e] = accumulate ? dw[e] + g : g;
+    a += (double)w[e] * (double)S;
+    b += (double)w[e] * (double)R;
+  }
+  __shared__ double red[4];
+  a = block_sum<double>(a, red);
+  b = block_sum<double>(b, red);
+  if (threadIdx.x == 0) { ab[0] = a; ab[1] = b; }
+}
+}  // namespace
+
+/* rs_f64 != 0: rs holds doubles (what kmh_conv3d_first_layer_wgrad writes: GroupNorm's sums over the whole volume cancel to
+ * ~1e-3 of their terms, so the correlations are kept in fp64 until they are folded); 0: floats (the split-operand weight
+ * gradient over the virtual 2-channel input, Cout > 16) */
+KMH_API int kmh_conv3d_first_layer_fold(const void* rs, int rs_f64, const float* w, const float* scale_n, const float* shift_n,
+                                        int Cout, float* dw, double* ab_n, int accumulate, void* stream) {
+  if (rs_f64)
+    first_layer_fold_kernel<double><<<1, 256, 0, (hipStream_t)stream>>>((const double*)rs, w, scale_n, shift_n, Cout, dw, ab_n, accumulate);
+  else
+    first_layer_fold_kernel<float><<<1, 256, 0, (hipStream_t)stream>>>((const float*)rs, w, scale_n, shift_n, Cout, dw, ab_n, accumulate);
+  return KMH_LAUNCH_CHECK();
+}

@@ -1,5 +1,7 @@
 """Audit of the hand-waited inline-asm loads of csrc/conv_bf.hip (run by keymorph_amd.build on the assembly of the very
 compilation that makes the library, by tools/scan_asm_inflight.py from the command line, and by tests/test_asm_audit_cpu.py).
+That file holds the 3x3x3 forward / data-gradient family only, so its assembly is the conv3_fwd_[sg]_kernel instances scanned here
+plus conv3_fwd_bf_kernel and pack_weight_bf_kernel, which have no inline-asm loads.
 
 An `asm volatile("global_load_dwordx4 %0, ...")` destination is "defined", for the compiler, the moment the statement ends -- long
 before the data lands.  Under register pressure the compiler has been seen to COPY such a register (v_accvgpr_write / v_mov /

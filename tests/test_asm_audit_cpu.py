@@ -1,4 +1,6 @@
 """ISA audit of the hand-counted inline-asm loads of csrc/conv_bf.hip (no GPU needed: hipcc cross-compiles gfx950).
+That file holds the forward / data-gradient family only: the conv3_fwd_[sg]_kernel instances audited here plus conv3_fwd_bf_kernel
+and pack_weight_bf_kernel.
 
 An `asm volatile("global_load_dwordx4 %0, ...")` destination is defined, for the compiler, when the statement ends -- long before
 the data lands.  Under register pressure the compiler has been seen to copy such a register (v_accvgpr_write) while the load was

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy (waves per SIMD) of every kernel, as the compiler reports them
 (`hipcc -S --cuda-device-only`): the authoritative source for occupancy -- the register column of a rocprofv3 trace is
-not the allocation on gfx950.  Usage: tools/kernel_resources.py [file.hip ...] > profiles/rNx_kernel_resources.md"""
+not the allocation on gfx950.  Compiled with the library's flags (keymorph_amd.build: FLAGS + FILE_FLAGS).  Usage: tools/kernel_resources.py [file.hip ...] > profiles/rNx_kernel_resources.md"""
 import glob
 import os
 import re
@@ -9,7 +9,10 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "keymorph_amd", "csrc")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from keymorph_amd import build  # noqa: E402
+
+ROOT = build.CSRC
 
 
 def main():
@@ -18,7 +21,8 @@ def main():
     for f in files:
         with tempfile.TemporaryDirectory() as td:
             out = os.path.join(td, "k.s")
-            subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast",
+            # the library's own command (per-file flags included: conv_wgrad.hip and norm.hip are built with max-ILP scheduling)
+            subprocess.run([build._hipcc(), *build.FLAGS, *build.FILE_FLAGS.get(os.path.basename(f), []),
                             "--cuda-device-only", "-S", "-o", out, f, "-I", ROOT], check=True, stderr=subprocess.DEVNULL)
             txt = open(out).read()
         for m in re.finditer(r"; Kernel info:.*?\n(.*?); Occupancy: (\d+)", txt, re.S):

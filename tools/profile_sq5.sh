@@ -41,7 +41,7 @@ done
 echo "== KEYMORPH_FWD_S=3 KMH_TIME=1 python tools/prof_layer.py 256 16 32 f16x3 nomask" >> $out
 KEYMORPH_FWD_S=3 KMH_TIME=1 python tools/prof_layer.py 256 16 32 f16x3 nomask >> $out 2>&1
 python tools/prof_pool.py >> $out 2>&1
-# cycle stamps of workgroup 0, wave 0 (differences between consecutive stamps; see the stamp() calls in conv_bf.hip)
+# cycle stamps of workgroup 0, wave 0 (differences between consecutive stamps; see the stamp() calls of conv3_fwd_g_kernel / conv3_fwd_s_kernel in conv_bf.hip)
 st=gpurun_out/${tag}_cycle_stamps.txt
 : > $st
 for shape in "128 64 64" "128 32 32" "256 16 32"; do
