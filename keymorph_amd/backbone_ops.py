@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._handoff import attach, expect, peek
 from ._lib import check
 from .ops import _p, _prep, _stream, workspace
 
@@ -35,6 +36,32 @@ def set_conv_mode(mode: str):
     global CONV_MODE
     assert mode in ("f32", "f16x3", "bf16x6"), mode
     CONV_MODE = mode
+
+
+# Switches read at CALL time (environment, all default off; for A/B runs, tests and debugging -- README.md)
+_SWITCHES = {
+    "KEYMORPH_NO_EPILOGUE_STATS": "a separate statistics pass per layer instead of the convolution epilogue's",
+    "KEYMORPH_NO_UPCONV": "materialise upsample+concat instead of the fused decoder operator, forward",
+    "KEYMORPH_NO_UPCONV_BWD": "materialise upsample+concat instead of the fused decoder operator, backward",
+    "KEYMORPH_NO_UPCONV_WGRAD": "the fused decoder operator rebuilds the upsampled half for the 27-tap weight gradient",
+    "KEYMORPH_NO_UP2_FOLD": "the upsampled channels' weight gradient by the box-sum tensor + matrix product route",
+    "KEYMORPH_NO_STATS_FOLD": "GroupNorm's backward statistics by a pass over the tensors",
+    "KEYMORPH_NO_BLOCKED_GRADS": "every gradient in (N,D,H,W,C)",
+    "KEYMORPH_NO_BLOCKED_UPCAT": "only the fused decoder operator's gradient in (N,D,H,W,C)",
+    "KEYMORPH_NO_SPLIT_POOLGRAD": "the 256^3-level pooled gradient scattered as fp32 instead of pre-split records",
+    "KEYMORPH_NO_CONV_POOL": "separate pooling pass instead of the conv epilogue's",
+    "KEYMORPH_NO_LAZY_FIRST": "GroupNorm backward of the first block as its own pass",
+    "KEYMORPH_NO_LAZY_SKIP": "GroupNorm's backward of a decoder skip applied in the decoder",
+    "KEYMORPH_NO_LAZY_IN": "ConvNet block by block: separate norm / ReLU / pooling passes",
+    "KEYMORPH_RANGE_AUDIT": "debug (ON = audit): per-sample dynamic range of every gradient operand, RANGE_AUDIT_LOG",
+}
+
+
+def _off(name: str) -> bool:
+    """Is the switch set?  Read now, not at import (tests flip them between calls); KeyError for a name not in the table."""
+    if name not in _SWITCHES:
+        raise KeyError(name)
+    return bool(os.environ.get(name))
 
 
 # ---- use_amp: a per-call argument of the library, a per-thread scope here ------------------------------------------
@@ -170,17 +197,16 @@ def absmax_scale(x: Tensor, min_abs: float = 0.0) -> Tensor:
 # the statistics of its sources (upsample + concat), tagged on the tensor object and guarded by its version counter.
 def conv_emits_stats() -> bool:
     """KEYMORPH_NO_EPILOGUE_STATS=1 (A/B measurements only) falls back to a separate statistics pass per layer."""
-    return CONV_MODE != "f32" and not os.environ.get("KEYMORPH_NO_EPILOGUE_STATS")
+    return CONV_MODE != "f32" and not _off("KEYMORPH_NO_EPILOGUE_STATS")
 
 
 def _tag_stats(t: Tensor, stats: Optional[Tensor]) -> None:
     if stats is not None:
-        t._kmh_stats = (stats, t._version)
+        attach(t, "stats", stats)
 
 
 def _peek_stats(t: Tensor) -> Optional[Tensor]:
-    tag = getattr(t, "_kmh_stats", None)
-    return tag[0] if (tag is not None and tag[1] == t._version) else None
+    return peek(t, "stats")
 
 
 STATS_STATS = {"carried": 0, "measured": 0}
@@ -198,7 +224,7 @@ def input_stats(x: Tensor, N: int, V: int, C: int) -> Tensor:
 # ---- range scales that travel with gradients -------------------------------------------------------------------
 # A backward kernel that produces a gradient tensor can emit its f16x3 range scale in the same pass (gn_bwd_apply),
 # and pooling / upsample+concat backward only move or add values, so a bound follows from the incoming scale.  The
-# scale rides on the tensor object as an attribute, guarded by the tensor's version counter; whenever it is missing
+# scale rides on the tensor object (_handoff.py), guarded by the tensor's version counter; whenever it is missing
 # (autograd summed two gradients, a hook replaced the tensor, ...) the consumer measures max|dy| itself.
 def _tag_grad_scale(t: Optional[Tensor], scale2: Optional[Tensor], loosen: float = 1.0) -> None:
     """loosen >= 1 (a power of two): |t| <= loosen * (the bound scale2 was made for)."""
@@ -206,12 +232,7 @@ def _tag_grad_scale(t: Optional[Tensor], scale2: Optional[Tensor], loosen: float
         return
     if loosen != 1.0:
         scale2 = torch.stack([scale2[0] * (1.0 / loosen), scale2[1] * loosen])
-    t._kmh_dscale = (scale2, t._version)
-
-
-def _peek_grad_scale(t: Tensor) -> Optional[Tensor]:
-    tag = getattr(t, "_kmh_dscale", None)
-    return tag[0] if (tag is not None and tag[1] == t._version) else None
+    attach(t, "grad_scale", scale2)
 
 
 def _sum_bound(a: Optional[Tensor], b: Optional[Tensor]) -> Optional[Tensor]:
@@ -248,9 +269,9 @@ def range_audit(t: Tensor) -> dict:
 
 
 def grad_scale(dy: Tensor) -> Tensor:
-    if os.environ.get("KEYMORPH_RANGE_AUDIT") and not _is_blocked(dy):
+    if _off("KEYMORPH_RANGE_AUDIT") and not _blocked_kind(dy):
         RANGE_AUDIT_LOG.append(dict(range_audit(dy), shape=tuple(dy.shape)))
-    s = _peek_grad_scale(dy)
+    s = peek(dy, "grad_scale")
     if s is not None:
         GRAD_SCALE_STATS["carried"] += 1
         return s
@@ -280,14 +301,25 @@ def pack_weight(w: Tensor, transposed: bool, wscale: Optional[Tensor] = None, te
         terms = terms or _TERMS[CONV_MODE]
         out = torch.empty(int(lib.kmh_conv3d_pack_bf_bytes(Cout, Cin, int(transposed), terms)), dtype=torch.uint8,
                           device=w.device)
-        out._kmh_terms = terms
-        out._kmh_wscale = (wscale if wscale is not None else absmax_scale(w)) if terms == 2 else None
-        check(lib.kmh_conv3d_pack_weight_bf(_p(w), _p(out), Cout, Cin, int(transposed), terms, _p(out._kmh_wscale),
-                                            _stream()), "kmh_conv3d_pack_weight_bf")
+        wscale = (wscale if wscale is not None else absmax_scale(w)) if terms == 2 else None
+        attach(out, "packed", (terms, wscale))
+        check(lib.kmh_conv3d_pack_weight_bf(_p(w), _p(out), Cout, Cin, int(transposed), terms, _p(wscale), _stream()),
+              "kmh_conv3d_pack_weight_bf")
         return out
     out = _f32((27, Cout, Cin) if transposed else (27, Cin, Cout), w.device)
     check(lib.kmh_conv3d_pack_weight(_p(w), _p(out), Cout, Cin, int(transposed), _stream()), "kmh_conv3d_pack_weight")
     return out
+
+
+def _packed(pk: Tensor):
+    """(terms, wscale) of a split-operand packing; (0, None) for the fp32 kernels' plain one"""
+    return peek(pk, "packed") or (0, None)
+
+
+def _conv_meta(N, D, H, W, Cin, Cout, taps=27) -> None:
+    """the profiler's record of the next launch: algorithmic work, 2 * taps * Cin * Cout flops per output voxel"""
+    if _lib.profiler.enabled:
+        _lib.profiler.meta = {"flops": 2.0 * taps * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
 
 
 def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, relu_out, mask=None,
@@ -298,12 +330,9 @@ def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, rel
     kernels' epilogue (the caller checks `conv_emits_stats()` first)."""
     lib = _lib.load()
     y = _f32((N, D, H, W, Cout), x.device)
-    if _lib.profiler.enabled:  # algorithmic work: 2*27*Cin*Cout flops per output voxel (SURVEY 8d)
-        _lib.profiler.meta = {"flops": 2.0 * 27 * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
-    terms = getattr(packed, "_kmh_terms", 0)
+    _conv_meta(N, D, H, W, Cin, Cout)
+    terms, wscale = _packed(packed)
     if terms:
-        if _lib.profiler.enabled:
-            _lib.profiler.meta = {"flops": 2.0 * 27 * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
         if terms == 2 and ascale is None:
             assert scale is None, "a normalised input needs the range scale of the NORMALISED tensor (norm_coeffs)"
             ascale = absmax_scale(x)
@@ -313,7 +342,7 @@ def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, rel
                             "convstats")
         check(lib.kmh_conv3d_fwd_bf(_p(x), _p(scale), _p(shift), _p(mask), _p(packed), _p(bias), _p(y), N, D, H, W,
                                     Cin, Cout, int(relu_in), int(relu_out), _t(terms), BF_ROWS_PER_WAVE,
-                                    _p(ascale if terms == 2 else None), _p(packed._kmh_wscale), _p(sws), _p(stats_out),
+                                    _p(ascale if terms == 2 else None), _p(wscale), _p(sws), _p(stats_out),
                                     int(in_blocked), _p(addend), _stream()), "kmh_conv3d_fwd_bf")
         return y
     assert stats_out is None and addend is None, "only the split-operand kernels emit output statistics / take an addend"
@@ -326,12 +355,11 @@ def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, rel
 def conv3_wgrad(x, scale, shift, dz, N, D, H, W, Cin, Cout, relu_in, dzmask=None, xscale=None, dscale=None,
                 dz_blocked: bool = False, fold: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
     """fold = (weight (Cout,Cin,3,3,3), bhat (N,Cin) float64 zeros): bhat[n,c] += sum_{tap,co} W dW_n, which equals
-    sum_v dxn[n,v,c] * xhat[n,v,c] for the data gradient dxn of the same dz (split-operand kernels only)."""
-    """xscale / dscale: range scales of the (normalised) input and of dz for the f16x3 mode (measured if absent)."""
+    sum_v dxn[n,v,c] * xhat[n,v,c] for the data gradient dxn of the same dz (split-operand kernels only).
+    xscale / dscale: range scales of the (normalised) input and of dz for the f16x3 mode (measured if absent)."""
     lib = _lib.load()
     dw = _f32((Cout, Cin, 3, 3, 3), x.device)
-    if _lib.profiler.enabled:
-        _lib.profiler.meta = {"flops": 2.0 * 27 * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
+    _conv_meta(N, D, H, W, Cin, Cout)
     if CONV_MODE != "f32":
         terms = _TERMS[CONV_MODE]
         ws = workspace(int(lib.kmh_conv3d_wgrad_bf_ws_bytes(N, D, H, W, Cin, Cout, terms)), x.device, "wgrad")
@@ -394,10 +422,7 @@ def first_layer_grads(x, scale, shift, mr, gamma, weight, dy, ymask, N, D, H, W,
                                           _p(ws), _stream()), "kmh_conv3d_wgrad_bf")
             check(lib.kmh_conv3d_first_layer_fold(_p(rs), 0, _p(weight), _p(scale[n]), _p(shift[n]), Cout, _p(dw),
                                                   _p(ab[n]), int(n > 0), _stream()), "kmh_conv3d_first_layer_fold")
-    c123 = _f32((N, 1, 3), x.device)
-    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
-    check(lib.kmh_gn_bwd_coeffs(_p(ab), _p(gamma), _p(mr), N, 1, G, float(V), _p(c123), _p(dgamma), _p(dbeta),
-                                None, _stream()), "kmh_gn_bwd_coeffs")
+    _, dgamma, dbeta = _gn_bwd_coeffs(ab, gamma, mr, N, 1, G, V)
     return dw, dgamma, dbeta
 
 
@@ -418,8 +443,7 @@ def conv3_up2_dgrad(dz: Tensor, weight: Tensor, Cs: int, Cl: int, dscale: Option
     check(lib.kmh_conv3d_up2_dgrad_pack_weight(_p(weight), _p(pk), Cout, Cs + Cl, Cs, Cl, terms, _p(wsu), _stream()),
           "kmh_conv3d_up2_dgrad_pack_weight")
     ds = _f32((N, D // 2, H // 2, W // 2, Cl), dz.device)
-    if _lib.profiler.enabled:
-        _lib.profiler.meta = {"flops": 2.0 * 8 * Cl * Cout * N * D * H * W, "shape": (N, D, H, W, Cout, Cl)}
+    _conv_meta(N, D, H, W, Cout, Cl, taps=8)
     sws = None
     if stats_out is not None:        # (N, Cl, 2) float64: per-channel (sum, sum of squares) of ds, from the epilogue
         sws = workspace(int(lib.kmh_conv3d_up2_dgrad_stats_ws_bytes(N, D // 2, H // 2, W // 2, Cl)), dz.device, "convstats")
@@ -434,17 +458,15 @@ UPCONV_STATS = {"calls": 0}          # decoder convolutions computed without the
 
 def _up_sources(x):
     """(skip, low) when x is the untouched output of upcat() with exact 2x upsampling, else None."""
-    tag = getattr(x, "_kmh_upsrc", None)
-    if tag is None or tag[2] != x._version or tag[0]._version != tag[3] or tag[1]._version != tag[4]:
-        return None
-    return tag[0], tag[1]
+    tag = peek(x, "up_sources")
+    return tag[:2] if (tag is not None and tag[0]._version == tag[2] and tag[1]._version == tag[3]) else None
 
 
 def grad_blocked_ok(N, D, H, W, Cin, Cout) -> bool:
     """May the gradient of a (Cin -> Cout) SingleConv's OUTPUT be handed to it channel-blocked, (N, Cout/8, D, H, W, 8)?
     (f16x3 mode, the wave-specialised weight gradient takes this shape, whole 8-channel chunks.)  The data-gradient
     loader then uses whole cache lines: 8-13 % on those launches, bit-identical results."""
-    if CONV_MODE != "f16x3" or os.environ.get("KEYMORPH_NO_BLOCKED_GRADS"):
+    if CONV_MODE != "f16x3" or _off("KEYMORPH_NO_BLOCKED_GRADS"):
         return False
     return bool(_lib.load().kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, 2))
 
@@ -459,7 +481,7 @@ UP2_STATS = {"fold": 0, "boxsum": 0}      # which weight-gradient route the fuse
 def up2_wgrad_fold_ok(Cl, Cout, terms):
     """The upsampled channels' weight gradient with the box sums formed inside the product (kmh_up2_wgrad_fold);
     KEYMORPH_NO_UP2_FOLD=1: the box-sum tensor + matrix product route (the A/B arm)."""
-    if os.environ.get("KEYMORPH_NO_UP2_FOLD"):
+    if _off("KEYMORPH_NO_UP2_FOLD"):
         return False
     return bool(_lib.load().kmh_up2_wgrad_fold_ok(int(Cl), int(Cout), int(terms)))
 
@@ -469,29 +491,53 @@ def pool_grad_split_ok(N, D, H, W, Cin, Cout) -> bool:
     records (`kmh_maxpool3d_bwd_split`)?  Both consumers must take them: the data gradient (Cout -> Cin, the z-paired tile of
     the one-wave kernel: `kmh_conv3d_fwd_bf_split_ok`) and the wave-specialised weight gradient.  KEYMORPH_NO_SPLIT_POOLGRAD=1
     keeps the fp32 scatter (A/B runs, tests)."""
-    if CONV_MODE != "f16x3" or os.environ.get("KEYMORPH_NO_SPLIT_POOLGRAD") or Cout % 8:
+    if CONV_MODE != "f16x3" or _off("KEYMORPH_NO_SPLIT_POOLGRAD") or Cout % 8:
         return False
     lib = _lib.load()
     return bool(lib.kmh_conv3d_fwd_bf_split_ok(N, D, H, W, Cout, Cin, 2)) and \
         bool(lib.kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, 2))
 
 
-# Layout of a gradient tensor handed from one operator's backward to the next (an attribute on the tensor object, guarded by its
-# version counter): kind 1 = fp32 channel-blocked (N, C/8, D, H, W, 8); kind 2 = PRE-SPLIT records (N, C/8, V + 1, 8 floats =
-# 8 fp16 hi + 8 fp16 lo), what kmh_maxpool3d_bwd_split writes.  Both are "blocked"; a consumer must know which.
-def _tag_blocked(t, kind: int = 1) -> None:
-    t._kmh_blocked = t._version
-    t._kmh_blocked_kind = int(kind)
-
-
-def _is_blocked(t) -> bool:
-    tag = getattr(t, "_kmh_blocked", None)
-    return tag is not None and tag == t._version
-
-
 def _blocked_kind(t) -> int:
-    """0 = (N,D,H,W,C); 1 = fp32 channel-blocked; 2 = pre-split records"""
-    return int(getattr(t, "_kmh_blocked_kind", 1)) if _is_blocked(t) else 0
+    """Layout of a gradient tensor handed from one operator's backward to the next (_handoff.py: "layout"): 0 = (N,D,H,W,C);
+    1 = fp32 channel-blocked; 2 = pre-split records.  1 and 2 are both "blocked"; a consumer must know which."""
+    return peek(t, "layout") or 0
+
+
+def _gn_bwd_coeffs(ab, gamma, mr, N, C, G, V, fold=None):
+    """GroupNorm's backward coefficients -> c123 (N,C,3), dgamma, dbeta (None without an affine).  ab (N,C,2) float64 = (sum dxn,
+    sum dxn * x) per channel, or a function of the device flag that computes it.  fold = (dstats, bhat, beta): the sums come
+    without a pass over dxn and x -- sum dxn from the data-gradient launch's epilogue, sum dxn * xhat from the per-sample weight
+    gradient contracted with the weights; a gamma that is exactly 0 flips the flag that un-gates `ab(flag)` (only_if=flag)."""
+    lib = _lib.load()
+    c123 = _f32((N, C, 3), mr.device)
+    dgamma = dbeta = flag = None
+    if gamma is not None:
+        dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    if fold is not None:
+        dstats, bhat, beta = fold
+        flag = torch.empty(1, dtype=torch.int32, device=mr.device)
+        check(lib.kmh_gn_bwd_coeffs_fold(_p(dstats), _p(bhat), _p(gamma), _p(beta), _p(mr), N, C, G, float(V), _p(c123),
+                                         _p(dgamma), _p(dbeta), _p(flag), _stream()), "kmh_gn_bwd_coeffs_fold")
+        STATS_STATS["folded"] = STATS_STATS.get("folded", 0) + 1
+    if callable(ab):
+        ab = ab(flag)
+    check(lib.kmh_gn_bwd_coeffs(_p(ab), _p(gamma), _p(mr), N, C, G, float(V), _p(c123), _p(dgamma), _p(dbeta), _p(flag),
+                                _stream()), "kmh_gn_bwd_coeffs")
+    return c123, dgamma, dbeta
+
+
+def _gn_bwd_apply(dxn, x, c123, N, V, C, sc2, from_relu=True, out=None, blocked=False):
+    """dx = [x > 0] (c1 dxn + c2 x + c3), in place on dxn unless `out` is given (a channel-blocked dx cannot be written in
+    place); sc2: zeroed float[2] that receives dx's range scale (f16x3), tagged on dx."""
+    out = dxn if out is None else out
+    check(_lib.load().kmh_gn_bwd_apply(_p(dxn), _p(x), _p(c123), N, V, C, int(from_relu), 0, _p(out), _p(sc2), int(blocked),
+                                       _stream()), "kmh_gn_bwd_apply")
+    _tag_grad_scale(out, sc2)
+    if blocked:
+        attach(out, "layout", 1)
+        BLOCKED_STATS["handoffs"] += 1
+    return out
 
 
 @_binds_amp
@@ -519,18 +565,17 @@ class _SingleConvGCR(torch.autograd.Function):
         V = D * H * W
         if upsrc is not None and not (CONV_MODE in _TERMS and _TERMS[CONV_MODE] in (2, 3) and Cout > 16
                                        and upsrc[1].shape[-1] % 8 == 0 and upsrc[0].shape[-1] % 8 == 0
-                                       and not os.environ.get("KEYMORPH_NO_UPCONV")):
+                                       and not _off("KEYMORPH_NO_UPCONV")):
             upsrc = None
         stats = input_stats(x, N, V, Cin)
         scale, shift, mr, ascale = norm_coeffs(stats, gamma, beta, N, Cin, num_groups, V, want_ascale=True)
         ystats = (torch.empty((N, Cout, 2), dtype=torch.float64, device=x.device) if conv_emits_stats() else None)
+        lib = _lib.load()
         if Cin == 1 and Cout <= 16:
             # the first U-Net convolution has its own exact-fp32 kernels, forward and backward (csrc/firstlayer.hip)
-            lib = _lib.load()
             y = _f32((N, D, H, W, Cout), x.device)
             ws = workspace(int(lib.kmh_conv3d_first_layer_fwd_ws_bytes(N, D, H, W, Cout)), x.device, "convstats")
-            if _lib.profiler.enabled:
-                _lib.profiler.meta = {"flops": 2.0 * 27 * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
+            _conv_meta(N, D, H, W, Cin, Cout)
             check(lib.kmh_conv3d_first_layer_fwd(_p(x), _p(scale), _p(shift), _p(weight), _p(y), N, D, H, W, Cout, _p(ws),
                                                  _p(ystats), _stream()), "kmh_conv3d_first_layer_fwd")
         elif upsrc is not None:
@@ -542,23 +587,21 @@ class _SingleConvGCR(torch.autograd.Function):
                              ystats)
         elif pool:
             assert dy_premasked and ystats is not None and conv_pool_ok(N, D, H, W, Cin, Cout)
-            lib = _lib.load()
             pk = pack_weight(weight, False)
-            ctx.wscale = getattr(pk, "_kmh_wscale", None)
+            ctx.wscale = _packed(pk)[1]
             y = _f32((N, D // 2, H // 2, W // 2, Cout), x.device)
             arg = torch.empty((N, D // 2, H // 2, W // 2, Cout), dtype=torch.uint8, device=x.device)
             sws = workspace(int(lib.kmh_conv3d_fwd_bf_stats_ws_bytes(N, D, H, W, Cout, BF_ROWS_PER_WAVE)), x.device,
                             "convstats")
-            if _lib.profiler.enabled:
-                _lib.profiler.meta = {"flops": 2.0 * 27 * Cin * Cout * N * D * H * W, "shape": (N, D, H, W, Cin, Cout)}
+            _conv_meta(N, D, H, W, Cin, Cout)
             check(lib.kmh_conv3d_fwd_bf_pool(_p(x), _p(scale), _p(shift), _p(pk), _p(y), _p(arg), N, D, H, W, Cin, Cout, 0,
-                                             _t(2), _p(ascale), _p(pk._kmh_wscale), _p(sws), _p(ystats), 0, _stream()),
+                                             _t(2), _p(ascale), _p(ctx.wscale), _p(sws), _p(ystats), 0, _stream()),
                   "kmh_conv3d_fwd_bf_pool")
             ctx.pool_arg = arg
             POOL_STATS["fused"] += 1
         else:
             pk = pack_weight(weight, False)
-            ctx.wscale = getattr(pk, "_kmh_wscale", None)   # the data-gradient packing of the backward re-uses it
+            ctx.wscale = _packed(pk)[1]   # the data-gradient packing of the backward re-uses it
             y = conv3_raw(x, scale, shift, pk, None, N, D, H, W, Cin, Cout, False, True, ascale=ascale,
                           stats_out=ystats)
         ctx.pool = bool(pool)
@@ -584,17 +627,12 @@ class _SingleConvGCR(torch.autograd.Function):
         Cout = weight.shape[0]
         V = D * H * W
         dy_blocked, dx_blocked = ctx.blocked
-        if _is_blocked(dy) != (dy_blocked and not ctx.pool):   # a lost or unexpected layout tag would silently scramble channels
-            raise RuntimeError("keymorph_amd: gradient layout mismatch (channel-blocked tag %s, expected %s); something "
-                               "between two SingleConvs replaced the gradient tensor (a hook?) -- set "
-                               "KEYMORPH_NO_BLOCKED_GRADS=1 to keep every gradient in (N,D,H,W,C)"
-                               % (_is_blocked(dy), dy_blocked))
-        sd_in = _peek_grad_scale(dy)
+        # a lost or unexpected layout tag would silently scramble channels
+        expect(dy, "layout", dy_blocked and not ctx.pool, "gradient between two SingleConvs", "KEYMORPH_NO_BLOCKED_GRADS")
+        sd_in = peek(dy, "grad_scale")
         dy_lazy, dx_lazy = ctx.lazy
-        lazy_tag = getattr(dy, "_kmh_lazy_gn", None)
-        if (lazy_tag is not None and lazy_tag[2] == dy._version) != dy_lazy:
-            raise RuntimeError("keymorph_amd: the first encoder block's lazy GroupNorm-backward hand-off lost its tag (a "
-                               "hook replaced the gradient?) -- set KEYMORPH_NO_LAZY_FIRST=1")
+        expect(dy, "lazy_gn", dy_lazy, "the first encoder block's pending GroupNorm backward", "KEYMORPH_NO_LAZY_FIRST")
+        lazy_tag = peek(dy, "lazy_gn")
         dy = _prep(dy)
         dy_split = False
         if ctx.pool:
@@ -622,36 +660,32 @@ class _SingleConvGCR(torch.autograd.Function):
             _tag_grad_scale(full, sd_in)       # scattering moves values: the bound of the pooled gradient holds
             dy = full
             if dy_blocked:
-                _tag_blocked(dy, 2 if dy_split else 1)
+                attach(dy, "layout", 2 if dy_split else 1)
                 BLOCKED_STATS["handoffs"] += 1
         # ReLU backward (dz = dy * [y > 0]) is fused into the loaders of both gradient kernels -- and is
         # skipped altogether when every consumer of y already returned a gradient masked by (y > 0)
         # (a downstream SingleConv with x_from_relu, possibly through max-pool / upsample+concat).
-        if _blocked_kind(dy) != (2 if dy_split else (1 if (dy_blocked) else 0)):
-            raise RuntimeError("keymorph_amd: gradient layout kind %d where %d was expected (1 = fp32 channel-blocked, 2 = pre-split "
-                               "records); a hook or an in-place op between two operators changed the tensor"
-                               % (_blocked_kind(dy), 2 if dy_split else (1 if dy_blocked else 0)))
+        kind = 2 if dy_split else int(dy_blocked)
+        if _blocked_kind(dy) != kind:
+            raise RuntimeError("keymorph_amd: gradient layout kind %d where %d was expected (1 = fp32 channel-blocked, 2 = pre-split"
+                               " records); a hook or an in-place op between two operators changed the tensor" % (_blocked_kind(dy), kind))
         ymask = None if dy_premasked else y
         first = Cin == 1 and not ctx.needs_input_grad[0] and (Cout <= 16 or CONV_MODE != "f32")
         dscale = (grad_scale(dy) if (_needs_range_scales() and not (first and Cout <= 16)) else None)
         if first:
-            if dy_lazy:      # dy = dxn of the next layer, to be combined with that layer's input (= y) on the fly
-                dw, dgamma, dbeta = first_layer_grads(x, scale, shift, mr, gamma, weight, dy, lazy_tag[1], N, D, H, W, Cout,
-                                                      G, dscale=dscale, lazy_c123=lazy_tag[0])
-            else:
-                dw, dgamma, dbeta = first_layer_grads(x, scale, shift, mr, gamma, weight, dy, ymask, N, D, H, W, Cout, G,
-                                                      dscale=dscale)
-            return None, dgamma, dbeta, dw, None, None, None, None, None, None, None, None, None
+            # dy_lazy: dy = dxn of the next layer, to be combined with that layer's input (= y) on the fly
+            lazy_c123, ymask = lazy_tag if dy_lazy else (None, ymask)
+            dw, dgamma, dbeta = first_layer_grads(x, scale, shift, mr, gamma, weight, dy, ymask, N, D, H, W, Cout, G,
+                                                  dscale=dscale, lazy_c123=lazy_c123)
+            return (None, dgamma, dbeta, dw) + (None,) * 9
         assert not dy_lazy, "only the first layer's correlation kernel applies a pending GroupNorm backward"
         need_affine = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         need_dxn = ctx.needs_input_grad[0] or need_affine
-        # GroupNorm's backward statistics without a pass over dxn and x: sum dxn from the data-gradient launch's
-        # epilogue, sum dxn * xhat from the per-sample weight gradient contracted with the weights (the same trick as
-        # the first layer's fold); a gamma that is exactly 0 flips a device flag that un-gates the direct path
-        fold = need_dxn and ctx.needs_input_grad[3] and conv_emits_stats() and not os.environ.get("KEYMORPH_NO_STATS_FOLD")
+        # GroupNorm's backward statistics without a pass over dxn and x (_gn_bwd_coeffs; the same trick as the first layer's fold)
+        fold = need_dxn and ctx.needs_input_grad[3] and conv_emits_stats() and not _off("KEYMORPH_NO_STATS_FOLD")
         bhat = torch.zeros((N, Cin), dtype=torch.float64, device=x.device) if fold else None
         dw = (conv3_wgrad(x, scale, shift, dy, N, D, H, W, Cin, Cout, False, dzmask=ymask, xscale=ctx.ascale,
-                          dscale=dscale, dz_blocked=2 if dy_split else dy_blocked, fold=(weight, bhat) if fold else None)
+                          dscale=dscale, dz_blocked=kind, fold=(weight, bhat) if fold else None)
               if ctx.needs_input_grad[3] else None)
         dx = dgamma = dbeta = None
         if need_dxn:
@@ -661,38 +695,21 @@ class _SingleConvGCR(torch.autograd.Function):
             dxn = conv3_raw(dy, None, None,
                             pack_weight(weight, True, None if ctx.dgrad_terms else getattr(ctx, "wscale", None), terms=ctx.dgrad_terms),
                             None, N, D, H, W, Cout, Cin, False, False,
-                            mask=ymask, ascale=dscale, in_blocked=2 if dy_split else dy_blocked, stats_out=dstats)
-            c123 = _f32((N, Cin, 3), x.device)
-            sc2 = (torch.zeros(2, dtype=torch.float32, device=x.device)
-                   if (_needs_range_scales() and ctx.needs_input_grad[0]) else None)
-            dgamma = torch.zeros_like(gamma)
-            dbeta = torch.zeros_like(gamma)
-            flag = None
-            if fold:
-                flag = torch.empty(1, dtype=torch.int32, device=x.device)
-                check(lib.kmh_gn_bwd_coeffs_fold(_p(dstats), _p(bhat), _p(gamma), _p(beta), _p(mr), N, Cin, G, float(V),
-                                                 _p(c123), _p(dgamma), _p(dbeta), _p(flag), _stream()),
-                      "kmh_gn_bwd_coeffs_fold")
-                STATS_STATS["folded"] = STATS_STATS.get("folded", 0) + 1
-            ab = channel_stats(dxn, x, N, V, Cin, only_if=flag)
-            check(lib.kmh_gn_bwd_coeffs(_p(ab), _p(gamma), _p(mr), N, Cin, G, float(V), _p(c123), _p(dgamma),
-                                        _p(dbeta), _p(flag), _stream()), "kmh_gn_bwd_coeffs")
+                            mask=ymask, ascale=dscale, in_blocked=kind, stats_out=dstats)
+            sc2 = torch.zeros(2, dtype=torch.float32, device=x.device) if (_needs_range_scales() and ctx.needs_input_grad[0]) else None
+            c123, dgamma, dbeta = _gn_bwd_coeffs(lambda flag: channel_stats(dxn, x, N, V, Cin, only_if=flag), gamma, mr,
+                                                 N, Cin, G, V, fold=(dstats, bhat, beta) if fold else None)
             if ctx.needs_input_grad[0] and dx_lazy:
                 assert x_from_relu and not dx_blocked
                 dx = dxn
-                dx._kmh_lazy_gn = (c123, x, dx._version)      # applied by the first layer's correlation kernel
+                attach(dx, "lazy_gn", (c123, x))      # applied by the first layer's correlation kernel
                 LAZY_STATS["handoffs"] += 1
             elif ctx.needs_input_grad[0]:
-                # in place on dxn; the (x > 0) mask is the upstream ReLU's backward (x is a ReLU output,
-                # possibly pooled / upsampled / concatenated -- all of which commute with the mask)
-                dx = torch.empty_like(dxn) if dx_blocked else dxn    # another layout cannot be written in place
-                check(lib.kmh_gn_bwd_apply(_p(dxn), _p(x), _p(c123), N, V, Cin, int(x_from_relu), 0, _p(dx), _p(sc2),
-                                           int(dx_blocked), _stream()), "kmh_gn_bwd_apply")
-                _tag_grad_scale(dx, sc2)
-                if dx_blocked:
-                    _tag_blocked(dx, 1)
-                    BLOCKED_STATS["handoffs"] += 1
-        return dx, dgamma, dbeta, dw, None, None, None, None, None, None, None, None, None
+                # the (x > 0) mask is the upstream ReLU's backward (x is a ReLU output, possibly pooled / upsampled /
+                # concatenated -- all of which commute with the mask)
+                dx = _gn_bwd_apply(dxn, x, c123, N, V, Cin, sc2, from_relu=x_from_relu,
+                                   out=torch.empty_like(dxn) if dx_blocked else None, blocked=dx_blocked)
+        return (dx, dgamma, dbeta, dw) + (None,) * 9
 
 
 def _up2_forward(skip, low, scale, shift, ascale, weight, N, D, H, W, Cs, Cl, Cout, ystats):
@@ -708,8 +725,7 @@ def _up2_forward(skip, low, scale, shift, ascale, weight, N, D, H, W, Cs, Cl, Co
     check(lib.kmh_conv3d_up2_pack_weight(_p(weight), _p(pku), Cout, Cs + Cl, Cs, Cl, terms, _p(wsu), _stream()),
           "kmh_conv3d_up2_pack_weight")
     part = _f32((N, D, H, W, Cout), dev)
-    if _lib.profiler.enabled:   # the work actually done: 8 taps per upsampled channel
-        _lib.profiler.meta = {"flops": 2.0 * 8 * Cl * Cout * N * D * H * W, "shape": (N, D, H, W, Cl, Cout)}
+    _conv_meta(N, D, H, W, Cl, Cout, taps=8)   # the work actually done: 8 taps per upsampled channel
     check(lib.kmh_conv3d_up2_fwd(_p(low), _p(scale), _p(shift), Cs + Cl, Cs, _p(pku), _p(part), N, D // 2, H // 2,
                                  W // 2, Cl, Cout, _t(terms), _p(ascale if terms == 2 else None), _p(wsu), _stream()),
           "kmh_conv3d_up2_fwd")
@@ -725,8 +741,7 @@ def upcat_conv_ok(skip, low, Cout) -> bool:
     (scripts/register.py, pairwise_register_eval.py:116-171) run the same forward."""
     return (CONV_MODE in _TERMS and conv_emits_stats() and Cout > 16 and Cout % 4 == 0 and skip.shape[-1] % 8 == 0
             and low.shape[-1] % 8 == 0 and all(a == 2 * b for a, b in zip(skip.shape[1:4], low.shape[1:4]))
-            and not os.environ.get("KEYMORPH_NO_UPCONV")
-            and not os.environ.get("KEYMORPH_NO_UPCONV_BWD"))
+            and not _off("KEYMORPH_NO_UPCONV") and not _off("KEYMORPH_NO_UPCONV_BWD"))
 
 
 @_binds_amp
@@ -770,10 +785,7 @@ class _UpCatConvGCR(torch.autograd.Function):
         Cl, Cout = low.shape[-1], weight.shape[0]
         C, V = Cs + Cl, D * H * W
         blk = ctx.dy_blocked
-        if _is_blocked(dy) != blk:      # a lost or unexpected layout tag would silently scramble channels
-            raise RuntimeError("keymorph_amd: gradient layout mismatch at the fused upsample+concat convolution (channel-"
-                               "blocked tag %s, expected %s); something replaced the gradient tensor (a hook?) -- set "
-                               "KEYMORPH_NO_BLOCKED_GRADS=1 to keep every gradient in (N,D,H,W,C)" % (_is_blocked(dy), blk))
+        expect(dy, "layout", blk, "gradient of the fused upsample+concat convolution's output", "KEYMORPH_NO_BLOCKED_GRADS")
         dy = _prep(dy)
         if not dy_premasked:     # fold the ReLU mask once (this operator's gradient kernels take no mask operand)
             dzm = torch.empty_like(dy)
@@ -786,7 +798,7 @@ class _UpCatConvGCR(torch.autograd.Function):
         bhat_s = torch.zeros((N, Cs), dtype=torch.float64, device=dy.device)
         dw_s = conv3_wgrad(skip, scale[:, :Cs].contiguous(), shift[:, :Cs].contiguous(), dy, N, D, H, W, Cs, Cout, False,
                            xscale=ctx.ascale, dscale=dscale, dz_blocked=blk, fold=(weight[:, :Cs].contiguous(), bhat_s))
-        if Cout % 4 == 0 and not os.environ.get("KEYMORPH_NO_UPCONV_WGRAD"):
+        if Cout % 4 == 0 and not _off("KEYMORPH_NO_UPCONV_WGRAD"):
             Vl = V // 8
             sc_l, sh_l = scale[:, Cs:].contiguous(), shift[:, Cs:].contiguous()   # named: they must outlive the launch
             terms = _TERMS[CONV_MODE]
@@ -831,48 +843,34 @@ class _UpCatConvGCR(torch.autograd.Function):
         dst_l = torch.empty((N, Cl, 2), dtype=torch.float64, device=dy.device)
         dsum_l = conv3_up2_dgrad(dy, weight, Cs, Cl, dscale, stats_out=dst_l, dz_blocked=blk)
         dstats = torch.cat([dst_s, dst_l], dim=1)
-        c123 = _f32((N, C, 3), dy.device)
-        dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
-        flag = torch.empty(1, dtype=torch.int32, device=dy.device)
-        check(lib.kmh_gn_bwd_coeffs_fold(_p(dstats), _p(bhat), _p(gamma), _p(beta), _p(mr), N, C, G, float(V), _p(c123),
-                                         _p(dgamma), _p(dbeta), _p(flag), _stream()), "kmh_gn_bwd_coeffs_fold")
-        STATS_STATS["folded"] = STATS_STATS.get("folded", 0) + 1
         # gamma == 0 somewhere: the direct statistics, gated on the device (sum dxn x over the upsampled channels is
         # sum over low voxels of (children's sum) * x_low)
-        ab = torch.cat([channel_stats(dxn_s, skip, N, V, Cs, only_if=flag),
-                        channel_stats(dsum_l, low, N, V // 8, Cl, only_if=flag)], dim=1)
-        check(lib.kmh_gn_bwd_coeffs(_p(ab), _p(gamma), _p(mr), N, C, G, float(V), _p(c123), _p(dgamma), _p(dbeta),
-                                    _p(flag), _stream()), "kmh_gn_bwd_coeffs")
+        ab = lambda flag: torch.cat([channel_stats(dxn_s, skip, N, V, Cs, only_if=flag),             # noqa: E731
+                                     channel_stats(dsum_l, low, N, V // 8, Cl, only_if=flag)], dim=1)
+        c123, dgamma, dbeta = _gn_bwd_coeffs(ab, gamma, mr, N, C, G, V, fold=(dstats, bhat, beta))
         # dx = mask * (c1 dxn + c2 x + c3); summed over 8 children for the upsampled half: c1 S + 8 c2 x_low + 8 c3
         c_s = c123[:, :Cs].contiguous()
         c_l = (c123[:, Cs:] * _const(dy.device, 1.0, 8.0, 8.0)).contiguous()
-        want = _needs_range_scales()
-        sc_s = torch.zeros(2, dtype=torch.float32, device=dy.device) if want else None
-        sc_l = torch.zeros(2, dtype=torch.float32, device=dy.device) if want else None
+        sc_s = torch.zeros(2, dtype=torch.float32, device=dy.device) if _needs_range_scales() else None
+        sc_l = torch.zeros(2, dtype=torch.float32, device=dy.device) if _needs_range_scales() else None
         dskip = dlow = None
         if ctx.needs_input_grad[0] and ctx.dskip_lazy:
             dskip = dxn_s
-            dskip._kmh_lazy_gn = (c_s, skip, dskip._version)       # applied by _PoolFork.backward
+            attach(dskip, "lazy_gn", (c_s, skip))       # applied by _PoolFork.backward
             LAZY_STATS["handoffs"] += 1
         elif ctx.needs_input_grad[0]:
-            check(lib.kmh_gn_bwd_apply(_p(dxn_s), _p(skip), _p(c_s), N, V, Cs, 1, 0, _p(dxn_s), _p(sc_s), 0, _stream()),
-                  "kmh_gn_bwd_apply")
-            dskip = dxn_s
-            _tag_grad_scale(dskip, sc_s)
+            dskip = _gn_bwd_apply(dxn_s, skip, c_s, N, V, Cs, sc_s)
         if ctx.needs_input_grad[1]:
-            check(lib.kmh_gn_bwd_apply(_p(dsum_l), _p(low), _p(c_l), N, V // 8, Cl, 1, 0, _p(dsum_l), _p(sc_l), 0,
-                                       _stream()), "kmh_gn_bwd_apply")
-            dlow = dsum_l
-            _tag_grad_scale(dlow, sc_l)
-        return dskip, dlow, dgamma, dbeta, dw, None, None, None, None
+            dlow = _gn_bwd_apply(dsum_l, low, c_l, N, V // 8, Cl, sc_l)
+        return (dskip, dlow, dgamma, dbeta, dw) + (None,) * 4
 
 
 def upcat_blocked_ok(skip, low, Cout) -> bool:
     """May the fused operator's OUTPUT gradient arrive channel-blocked?  (the skip half's 27-tap weight gradient must take
     that layout -- grad_blocked_ok -- and the upsampled half goes through the box sums, Cout % 8 == 0.)"""
     N, D, H, W, Cs = skip.shape
-    return (torch.is_grad_enabled() and Cout % 8 == 0 and not os.environ.get("KEYMORPH_NO_UPCONV_WGRAD")
-            and not os.environ.get("KEYMORPH_NO_BLOCKED_UPCAT") and grad_blocked_ok(N, D, H, W, Cs, Cout))
+    return (torch.is_grad_enabled() and Cout % 8 == 0 and not _off("KEYMORPH_NO_UPCONV_WGRAD")
+            and not _off("KEYMORPH_NO_BLOCKED_UPCAT") and grad_blocked_ok(N, D, H, W, Cs, Cout))
 
 
 def upcat_conv_gcr(skip, low, gamma, beta, weight, num_groups: int, dy_premasked: bool = False,
@@ -912,7 +910,7 @@ def lazy_skip_ok(skip) -> bool:
     """May the fused decoder operator hand the skip half's gradient to pool_fork's backward with GroupNorm's backward
     pending?  (dense fp32 skip tensor with even D, H, W and whole channel quads)"""
     return (torch.is_grad_enabled() and skip.shape[1] % 2 == 0 and skip.shape[2] % 2 == 0 and skip.shape[3] % 2 == 0
-            and skip.shape[4] % 4 == 0 and not os.environ.get("KEYMORPH_NO_LAZY_SKIP"))
+            and skip.shape[4] % 4 == 0 and not _off("KEYMORPH_NO_LAZY_SKIP"))
 
 
 def lazy_first_layer_ok(x, cout1: int) -> bool:
@@ -920,13 +918,13 @@ def lazy_first_layer_ok(x, cout1: int) -> bool:
     GroupNorm's backward still pending?  The first layer must be the 1 -> Cout <= 16 layer with the dedicated kernels
     and its input must need no gradient (the image)."""
     return (x.shape[-1] == 1 and cout1 <= 16 and not x.requires_grad and torch.is_grad_enabled()
-            and not os.environ.get("KEYMORPH_NO_LAZY_FIRST"))
+            and not _off("KEYMORPH_NO_LAZY_FIRST"))
 
 
 def conv_pool_ok(N, D, H, W, Cin, Cout) -> bool:
     """May relu(conv3(group_norm(x))) be followed by MaxPool3d(2) inside the convolution's epilogue (the output feeds
     ONLY that pooling and its gradient arrives masked)?  f16x3 mode, 16 < Cout <= 32, the LDS-DMA kernel selected."""
-    if CONV_MODE != "f16x3" or not conv_emits_stats() or os.environ.get("KEYMORPH_NO_CONV_POOL"):
+    if CONV_MODE != "f16x3" or not conv_emits_stats() or _off("KEYMORPH_NO_CONV_POOL"):
         return False
     return bool(_lib.load().kmh_conv3d_fwd_bf_pool_ok(N, D, H, W, Cin, Cout, 2))
 
@@ -957,7 +955,7 @@ def _maxpool_bwd(ctx, dy, add, out_blocked=False):
     N, D, H, W, C = ctx.xshape
     odd = (D % 2) or (H % 2) or (W % 2)
     acs = 0
-    add_tag = _NO_ADD if add is None else _peek_grad_scale(add)
+    add_tag = _NO_ADD if add is None else peek(add, "grad_scale")
     if add is not None:
         acs = add.stride(3)
         dense_voxels = add.stride() == (D * H * W * acs, H * W * acs, W * acs, acs, 1)
@@ -971,10 +969,10 @@ def _maxpool_bwd(ctx, dy, add, out_blocked=False):
     check(lib.kmh_maxpool3d_bwd(None, _p(arg), _p(dy_c), _p(add), acs, _p(dx), N, D, H, W, C, int(out_blocked),
                                 _stream()), "kmh_maxpool3d_bwd")
     if out_blocked:
-        _tag_blocked(dx, 1)
+        attach(dx, "layout", 1)
         BLOCKED_STATS["handoffs"] += 1
     # scattering moves values: the bound of dy holds for dx (plus the skip gradient's bound when that is added)
-    sd = _peek_grad_scale(dy)
+    sd = peek(dy, "grad_scale")
     _tag_grad_scale(dx, sd if add_tag is _NO_ADD else _sum_bound(sd, add_tag))
     return dx
 
@@ -1008,28 +1006,19 @@ class _PoolFork(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dskip):
-        lazy = getattr(dskip, "_kmh_lazy_gn", None) if dskip is not None else None
-        if lazy is not None and lazy[2] != dskip._version:
-            raise RuntimeError("keymorph_amd: the skip gradient's pending GroupNorm backward lost its tag (a hook modified "
-                               "the gradient?) -- set KEYMORPH_NO_LAZY_SKIP=1")
-        if lazy is None and dskip is not None and getattr(ctx, "_kmh_expect_lazy", False):
-            # the decoder handed over dxn with GroupNorm's backward PENDING, but what arrived is not that tensor (a hook or
-            # retain_grad on the skip tensor, or a second consumer whose gradient autograd added): summing it as a finished
-            # gradient would be silently wrong
-            raise RuntimeError("keymorph_amd: pool_fork expected the skip gradient with its GroupNorm backward pending, but the "
-                               "tensor that arrived carries no such tag (hook / retain_grad / second consumer of the skip "
-                               "tensor?) -- set KEYMORPH_NO_LAZY_SKIP=1 to apply GroupNorm's backward in the decoder")
+        if dskip is not None and getattr(ctx, "_kmh_expect_lazy", False):
+            # the decoder handed over dxn with GroupNorm's backward PENDING: if what arrived is not that tensor (a hook, retain_grad
+            # or a second consumer of the skip tensor) or it was modified since, summing it as finished would be silently wrong
+            expect(dskip, "lazy_gn", True, "pool_fork's skip gradient with its GroupNorm backward pending", "KEYMORPH_NO_LAZY_SKIP")
+        lazy = peek(dskip, "lazy_gn") if dskip is not None else None
         if lazy is not None:
             lib = _lib.load()
-            c123, x, _ = lazy
+            c123, x = lazy
             N, D, H, W, C = ctx.xshape
             dxn = _prep(dskip)
             sc2 = torch.zeros(2, dtype=torch.float32, device=dxn.device) if _needs_range_scales() else None
             if dy is None:                       # no pooled gradient: just the pending apply
-                check(lib.kmh_gn_bwd_apply(_p(dxn), _p(x), _p(c123), N, D * H * W, C, 1, 0, _p(dxn), _p(sc2), 0, _stream()),
-                      "kmh_gn_bwd_apply")
-                _tag_grad_scale(dxn, sc2)
-                return dxn
+                return _gn_bwd_apply(dxn, x, c123, N, D * H * W, C, sc2)
             (arg,) = ctx.saved_tensors
             dx = torch.empty((N, D, H, W, C), dtype=torch.float32, device=dxn.device)
             check(lib.kmh_maxpool3d_bwd_lazy(_p(arg), _p(_prep(dy)), _p(dxn), _p(x), _p(c123), _p(dx), N, D, H, W, C, _p(sc2),
@@ -1073,7 +1062,7 @@ class _UpCat(torch.autograd.Function):
               "kmh_upcat_bwd")
         if ctx.lazy:
             dskip = dout[..., :Cs]
-        sd = _peek_grad_scale(dout)
+        sd = peek(dout, "grad_scale")
         _tag_grad_scale(dskip, sd)                      # a subset of dout's values
         if (D, H, W) == (2 * Dl, 2 * Hl, 2 * Wl):
             _tag_grad_scale(dlow, sd, loosen=8.0)       # each coarse voxel sums exactly 8 fine ones
@@ -1089,7 +1078,7 @@ def upcat(skip: Tensor, low: Tensor, lazy_skip_grad: bool = False) -> Tensor:
         _tag_stats(out, torch.cat([ss, sl * 8.0], dim=1))
     if all(a == 2 * b for a, b in zip(skip.shape[1:4], low.shape[1:4])) and skip.is_contiguous() and low.is_contiguous():
         # the consumer (a SingleConv) can compute the upsampled half from `low` itself (8 taps instead of 27)
-        out._kmh_upsrc = (skip.detach(), low.detach(), out._version, skip._version, low._version)
+        attach(out, "up_sources", (skip.detach(), low.detach(), skip._version, low._version))
     return out
 
 
@@ -1226,12 +1215,14 @@ class _ConvBlock(torch.autograd.Function):
         lib = _lib.load()
         (groups,) = ctx.cfg
         dy = _prep(dy)
+        saved = ctx.saved_tensors
+        x, weight = saved[:2]
+        N, D, H, W, Cin = x.shape
+        Cout = weight.shape[0]
+        V = D * H * W
         dgamma = dbeta = None
         if ctx.bn == 2:
-            x, weight, z, y, scale, gamma, rmean, rstd = ctx.saved_tensors
-            N, D, H, W, Cin = x.shape
-            Cout = weight.shape[0]
-            V = D * H * W
+            z, y, scale, gamma, rmean, rstd = saved[2:]
             dym = torch.empty_like(dy)
             check(lib.kmh_relu_mask(_p(dy), _p(y), dy.numel(), _p(dym), _stream()), "kmh_relu_mask")
             ab = channel_stats(dym, z, N, V, Cout).sum(0)                 # (Cout, 2): sum dym, sum dym * z
@@ -1239,46 +1230,28 @@ class _ConvBlock(torch.autograd.Function):
             dgamma = ((ab[:, 1] - rmean.double() * ab[:, 0]) * rstd.double()).float()
             c123 = torch.zeros((N, Cout, 3), dtype=torch.float32, device=x.device)
             c123[:, :, 0] = scale
-            check(lib.kmh_gn_bwd_apply(_p(dym), _p(z), _p(c123), N, V, Cout, 0, 0, _p(dym), None, 0, _stream()),
-                  "kmh_gn_bwd_apply")
-            dz, dzmask = dym, None
+            dz, dzmask = _gn_bwd_apply(dym, z, c123, N, V, Cout, None, from_relu=False), None
         elif groups == 0:
-            x, weight, y = ctx.saved_tensors
-            N, D, H, W, Cin = x.shape
-            Cout = weight.shape[0]
-            V = D * H * W
-            dz, dzmask = dy, y
+            dz, dzmask = dy, saved[2]
         else:
-            saved = ctx.saved_tensors
-            x, weight, z, y, mr = saved[:5]
-            gamma = saved[5] if len(saved) > 5 else None
-            N, D, H, W, Cin = x.shape
-            Cout = weight.shape[0]
-            V = D * H * W
+            z, y, mr, *affine = saved[2:]
+            gamma = affine[0] if affine else None
             Nn, Vn = (1, N * V) if ctx.bn == 1 else (N, V)
             dym = torch.empty_like(dy)
             check(lib.kmh_relu_mask(_p(dy), _p(y), dy.numel(), _p(dym), _stream()), "kmh_relu_mask")
-            ab = channel_stats(dym, z, Nn, Vn, Cout)
-            c123 = _f32((Nn, Cout, 3), x.device)
-            if gamma is not None:
-                dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
-            check(lib.kmh_gn_bwd_coeffs(_p(ab), _p(gamma), _p(mr), Nn, Cout, groups, float(Vn), _p(c123), _p(dgamma),
-                                        _p(dbeta), None, _stream()), "kmh_gn_bwd_coeffs")
-            check(lib.kmh_gn_bwd_apply(_p(dym), _p(z), _p(c123), Nn, Vn, Cout, 0, 0, _p(dym), None, 0, _stream()),
-                  "kmh_gn_bwd_apply")
-            dz, dzmask = dym, None
+            c123, dgamma, dbeta = _gn_bwd_coeffs(channel_stats(dym, z, Nn, Vn, Cout), gamma, mr, Nn, Cout, groups, Vn)
+            dz, dzmask = _gn_bwd_apply(dym, z, c123, Nn, Vn, Cout, None, from_relu=False), None
         dw = conv3_wgrad(x, None, None, dz, N, D, H, W, Cin, Cout, False, dzmask=dzmask)
+        dzm = dz
         if dzmask is not None:
             dzm = torch.empty_like(dz)
             check(lib.kmh_relu_mask(_p(dz), _p(dzmask), dz.numel(), _p(dzm), _stream()), "kmh_relu_mask")
-            db = channel_stats(dzm, None, N, V, Cout)[:, :, 0].sum(0).float()
-        else:
-            db = channel_stats(dz, None, N, V, Cout)[:, :, 0].sum(0).float()
+        db = channel_stats(dzm, None, N, V, Cout)[:, :, 0].sum(0).float()
         dx = None
         if ctx.needs_input_grad[0]:
             dx = conv3_raw(dz, None, None, pack_weight(weight, True), None, N, D, H, W, Cout, Cin, False, False,
                            mask=dzmask)
-        return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+        return (dx, dw, db, dgamma, dbeta) + (None,) * 5
 
 
 def conv_block(x, weight, bias, gamma=None, beta=None, groups: int = 0) -> Tensor:
@@ -1327,9 +1300,32 @@ def convnet_lazy_ok(x: Tensor, norm_type: str) -> bool:
     The fused units never form the gradient w.r.t. the image (their first unit returns None for it), so an input that
     requires one -- saliency maps, adversarial inputs, augmentation differentiated through the image -- takes the
     block-by-block route, whose first block does compute it."""
-    return (norm_type == "instance" and conv_emits_stats() and not os.environ.get("KEYMORPH_NO_LAZY_IN")
+    return (norm_type == "instance" and conv_emits_stats() and not _off("KEYMORPH_NO_LAZY_IN")
             and not (x.requires_grad and torch.is_grad_enabled())
             and all(int(d) % 16 == 0 for d in x.shape[1:4]))
+
+
+def _in_bwd(g, u, zprev, scale, shift, mr, arg=None, in_place=False):
+    """Backward of u = [MaxPool3d(2)](ReLU(InstanceNorm(zprev))) for the gradient g of u -> the gradient of zprev, tagged with
+    its range scale.  Both sums of InstanceNorm's backward are taken at u's resolution (kmh_in_bwd_stats: g [zhat > 0] against
+    u); arg: the pooling's winners, u the pooled RAW tensor -- the apply pass then scatters through them."""
+    lib = _lib.load()
+    N, Dp, Hp, Wp, C = zprev.shape
+    ab = torch.empty((N, C, 2), dtype=torch.float64, device=g.device)
+    ws = workspace(int(lib.kmh_channel_stats_ws_bytes(N, C)), g.device, "stats")
+    check(lib.kmh_in_bwd_stats(_p(g), _p(u), _p(scale), _p(shift), N, u.shape[1] * u.shape[2] * u.shape[3], C, _p(ab), _p(ws),
+                               _stream()), "kmh_in_bwd_stats")
+    c123, _, _ = _gn_bwd_coeffs(ab, None, mr, N, C, C, Dp * Hp * Wp)
+    out = g if in_place else torch.empty_like(zprev)
+    sc2 = torch.zeros(2, dtype=torch.float32, device=g.device) if _needs_range_scales() else None
+    if arg is not None:
+        check(lib.kmh_in_bwd_apply_pool(_p(arg), _p(g), _p(zprev), _p(scale), _p(shift), _p(c123), N, Dp, Hp, Wp, C, _p(out),
+                                        _p(sc2), _stream()), "kmh_in_bwd_apply_pool")
+    else:
+        check(lib.kmh_in_bwd_apply(_p(g), _p(zprev), _p(scale), _p(shift), _p(c123), N, Dp * Hp * Wp, C, _p(out), _p(sc2),
+                                   _stream()), "kmh_in_bwd_apply")
+    _tag_grad_scale(out, sc2)
+    return out
 
 
 @_binds_amp
@@ -1355,7 +1351,7 @@ class _ConvINUnit(torch.autograd.Function):
                 check(lib.kmh_maxpool3d_fwd(_p(zprev), _p(u), _p(arg), N, Dp, Hp, Wp, Cin, _stream()), "kmh_maxpool3d_fwd")
         D, H, W = u.shape[1:4]
         pk = pack_weight(weight, False)
-        ctx.wscale = getattr(pk, "_kmh_wscale", None)
+        ctx.wscale = _packed(pk)[1]
         zst = torch.empty((N, Cout, 2), dtype=torch.float64, device=zprev.device)
         z = conv3_raw(u, scale, shift, pk, bias, N, D, H, W, Cin, Cout, not first, False, ascale=ascale, stats_out=zst)
         ctx.ascale = ascale
@@ -1368,11 +1364,10 @@ class _ConvINUnit(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _dst):
-        lib = _lib.load()
         N, Dp, Hp, Wp, D, H, W, Cin, Cout = ctx.dims
         saved = ctx.saved_tensors
         zprev, weight = saved[0], saved[1]
-        dscale = _peek_grad_scale(dz)
+        dscale = peek(dz, "grad_scale")
         dz = _prep(dz)
         if _needs_range_scales() and dscale is None:
             dscale = absmax_scale(dz)
@@ -1381,31 +1376,14 @@ class _ConvINUnit(torch.autograd.Function):
         if ctx.first:
             xs = absmax_scale(zprev) if _needs_range_scales() else None
             dw = conv3_wgrad(zprev, None, None, dz, N, D, H, W, Cin, Cout, False, xscale=xs, dscale=dscale)
-            return None, None, dw, db, None, None
+            return (None, None, dw, db) + (None,) * 2
         scale, shift, mr = saved[2:5]
         u, arg = (saved[5], saved[6]) if ctx.pool else (zprev, None)
         dw = conv3_wgrad(u, scale, shift, dz, N, D, H, W, Cin, Cout, True, xscale=ctx.ascale, dscale=dscale)
         du = conv3_raw(dz, None, None, pack_weight(weight, True, wscale=ctx.wscale), None, N, D, H, W, Cout, Cin, False, False,
                        ascale=dscale)
-        # g = scatter(du) [zhat > 0] lives at u's resolution: both sums of InstanceNorm's backward are taken there
-        ab = torch.empty((N, Cin, 2), dtype=torch.float64, device=dz.device)
-        ws = workspace(int(lib.kmh_channel_stats_ws_bytes(N, Cin)), dz.device, "stats")
-        check(lib.kmh_in_bwd_stats(_p(du), _p(u), _p(scale), _p(shift), N, D * H * W, Cin, _p(ab), _p(ws), _stream()),
-              "kmh_in_bwd_stats")
-        c123 = _f32((N, Cin, 3), dz.device)
-        check(lib.kmh_gn_bwd_coeffs(_p(ab), None, _p(mr), N, Cin, Cin, float(Dp * Hp * Wp), _p(c123), None, None, None,
-                                    _stream()), "kmh_gn_bwd_coeffs")
-        sc2 = torch.zeros(2, dtype=torch.float32, device=dz.device) if _needs_range_scales() else None
-        if ctx.pool:
-            dzp = _f32((N, Dp, Hp, Wp, Cin), dz.device)
-            check(lib.kmh_in_bwd_apply_pool(_p(arg), _p(du), _p(zprev), _p(scale), _p(shift), _p(c123), N, Dp, Hp, Wp, Cin,
-                                            _p(dzp), _p(sc2), _stream()), "kmh_in_bwd_apply_pool")
-        else:
-            dzp = du
-            check(lib.kmh_in_bwd_apply(_p(du), _p(zprev), _p(scale), _p(shift), _p(c123), N, Dp * Hp * Wp, Cin, _p(dzp),
-                                       _p(sc2), _stream()), "kmh_in_bwd_apply")
-        _tag_grad_scale(dzp, sc2)
-        return dzp, None, dw, db, None, None
+        dzp = _in_bwd(du, u, zprev, scale, shift, mr, arg=arg, in_place=not ctx.pool)
+        return (dzp, None, dw, db) + (None,) * 2
 
 
 class _INReluOut(torch.autograd.Function):
@@ -1425,23 +1403,8 @@ class _INReluOut(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         z, scale, shift, mr = ctx.saved_tensors
-        N, D, H, W, C = z.shape
-        V = D * H * W
-        dy = _prep(dy)
-        ab = torch.empty((N, C, 2), dtype=torch.float64, device=z.device)
-        ws = workspace(int(lib.kmh_channel_stats_ws_bytes(N, C)), z.device, "stats")
-        check(lib.kmh_in_bwd_stats(_p(dy), _p(z), _p(scale), _p(shift), N, V, C, _p(ab), _p(ws), _stream()), "kmh_in_bwd_stats")
-        c123 = _f32((N, C, 3), z.device)
-        check(lib.kmh_gn_bwd_coeffs(_p(ab), None, _p(mr), N, C, C, float(V), _p(c123), None, None, None, _stream()),
-              "kmh_gn_bwd_coeffs")
-        dz = torch.empty_like(z)
-        sc2 = torch.zeros(2, dtype=torch.float32, device=z.device) if _needs_range_scales() else None
-        check(lib.kmh_in_bwd_apply(_p(dy), _p(z), _p(scale), _p(shift), _p(c123), N, V, C, _p(dz), _p(sc2), _stream()),
-              "kmh_in_bwd_apply")
-        _tag_grad_scale(dz, sc2)
-        return dz, None
+        return _in_bwd(_prep(dy), z, z, scale, shift, mr), None
 
 
 def convnet_instance_lazy(x: Tensor, blocks) -> Tensor:
@@ -1465,6 +1428,32 @@ HEAD_MASK = os.environ.get("KEYMORPH_HEAD_MASK", "1") != "0"
 HEAD_STATS = {"mask": 0, "recompute": 0}
 
 
+def _headcom_fwd(feat, w, b, sq=None, scales=False, mask=False):
+    """One launch of the fused head, split-operand arm (kmh_headcom_fwd_bf) or fp32 -> pts (N,K,3), sums (N,K,4), and from the
+    split-operand arm when asked: hsc, the feat / filter range scales (f16x3), and hmask, the [h > 0] bits.  sq (N,K): filled
+    with sum relu(h)^2."""
+    lib = _lib.load()
+    N, D, H, W, Cin = feat.shape
+    Cout = w.shape[0]
+    pts, sums = _f32((N, Cout, 3), feat.device), _f32((N, Cout, 4), feat.device)
+    hsc = hmask = None
+    if CONV_MODE != "f32" and Cin % 4 == 0:
+        terms = _HEAD_TERMS[CONV_MODE]
+        ws = workspace(int(lib.kmh_headcom_fwd_bf_ws_bytes(N, D * H * W, Cout, terms)), feat.device, "head")
+        if scales and terms == 2:
+            hsc = _f32((4,), feat.device)
+        nmask = int(lib.kmh_headcom_mask_words(N, D, H, W, Cout)) if mask else 0
+        if nmask:
+            hmask = torch.empty(nmask, dtype=torch.int32, device=feat.device)
+        check(lib.kmh_headcom_fwd_bf(_p(feat), _p(w), _p(b), _p(pts), _p(sums), _p(sq), _p(hsc), N, D, H, W, Cin, Cout,
+                                     _t(terms), _p(hmask), _p(ws), _stream()), "kmh_headcom_fwd_bf")
+    else:
+        ws = workspace(int(lib.kmh_headcom_fwd_ws_bytes(N, D * H * W, Cout)), feat.device, "head")
+        check(lib.kmh_headcom_fwd(_p(feat), _p(w), _p(b), _p(pts), _p(sums), _p(sq), N, D, H, W, Cin, Cout, _p(ws),
+                                  _stream()), "kmh_headcom_fwd")
+    return pts, sums, hsc, hmask
+
+
 @_binds_amp
 class _HeadCoM(torch.autograd.Function):
     """pts = CenterOfMass3d('ij')(conv1x1(feat) + b) without the heat-map (csrc/headcom.hip); the second output is
@@ -1472,31 +1461,14 @@ class _HeadCoM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, w, b, feat_from_relu=False):
-        lib = _lib.load()
         ctx.set_materialize_grads(False)
         ctx.mask_dfeat = int(bool(feat_from_relu))
         feat, w = _prep(feat), _prep(w)
         b = None if b is None else _prep(b)
-        N, D, H, W, Cin = feat.shape
-        Cout = w.shape[0]
-        pts = _f32((N, Cout, 3), feat.device)
-        sums = _f32((N, Cout, 4), feat.device)
-        if CONV_MODE != "f32" and Cin % 4 == 0:
-            terms = _HEAD_TERMS[CONV_MODE]
-            ws = workspace(int(lib.kmh_headcom_fwd_bf_ws_bytes(N, D * H * W, Cout, terms)), feat.device, "head")
-            hsc = _f32((4,), feat.device) if terms == 2 else None    # feat / filter range scales, re-used by the backward
-            # [h > 0] bits for the backward (it then skips recomputing the logits): only when a backward can follow
-            nmask = int(lib.kmh_headcom_mask_words(N, D, H, W, Cout)) if (HEAD_MASK and any(ctx.needs_input_grad[:3])) else 0
-            hmask = torch.empty(nmask, dtype=torch.int32, device=feat.device) if nmask else None
-            check(lib.kmh_headcom_fwd_bf(_p(feat), _p(w), _p(b), _p(pts), _p(sums), None, _p(hsc), N, D, H, W, Cin, Cout,
-                                         _t(terms), _p(hmask), _p(ws), _stream()), "kmh_headcom_fwd_bf")
-            ctx.hsc = hsc
-            ctx.hmask = hmask
-            HEAD_STATS["mask" if nmask else "recompute"] += 1
-        else:
-            ws = workspace(int(lib.kmh_headcom_fwd_ws_bytes(N, D * H * W, Cout)), feat.device, "head")
-            check(lib.kmh_headcom_fwd(_p(feat), _p(w), _p(b), _p(pts), _p(sums), None, N, D, H, W, Cin, Cout, _p(ws),
-                                      _stream()), "kmh_headcom_fwd")
+        # the range scales are re-used by the backward; the [h > 0] bits let it skip recomputing the logits: only when one can follow
+        pts, sums, ctx.hsc, ctx.hmask = _headcom_fwd(feat, w, b, scales=True, mask=HEAD_MASK and any(ctx.needs_input_grad[:3]))
+        if CONV_MODE != "f32" and feat.shape[-1] % 4 == 0:
+            HEAD_STATS["mask" if ctx.hmask is not None else "recompute"] += 1
         ctx.save_for_backward(feat, w, sums) if b is None else ctx.save_for_backward(feat, w, sums, b)
         return pts, sums[:, :, 0].contiguous()
 
@@ -1520,8 +1492,8 @@ class _HeadCoM(torch.autograd.Function):
             dsc = (torch.zeros(2, dtype=torch.float32, device=feat.device)
                    if (terms == 2 and dfeat is not None) else None)
             check(lib.kmh_headcom_bwd_bf(_p(dpts), _p(dpower), _p(feat), _p(w), _p(b), _p(sums), _p(dfeat), _p(dw), _p(db), N, D, H,
-                                         W, Cin, Cout, _t(terms), ctx.mask_dfeat, _p(getattr(ctx, "hsc", None)), _p(dsc),
-                                         _p(getattr(ctx, "hmask", None)), _p(ws), _stream()), "kmh_headcom_bwd_bf")
+                                         W, Cin, Cout, _t(terms), ctx.mask_dfeat, _p(ctx.hsc), _p(dsc), _p(ctx.hmask), _p(ws), _stream()),
+                  "kmh_headcom_bwd_bf")
             _tag_grad_scale(dfeat, dsc)
         else:
             ws = workspace(int(lib.kmh_headcom_bwd_ws_bytes(N, D * H * W, Cin, Cout)), feat.device, "head")
@@ -1537,22 +1509,11 @@ def head_moments(feat: Tensor, w: Tensor, b: Optional[Tensor]):
     """Inference-only companion of head_com for keypoint weighting (keymorph/model.py:75-109): keypoints plus the
     per-channel moments of relu(heat-map), still without materialising it.
     -> pts (N,K,3), power (N,K) = sum relu(h), sq (N,K) = sum relu(h)^2.  No autograd graph is recorded."""
-    lib = _lib.load()
     with torch.no_grad():
         feat, w = _prep(feat), _prep(w)
         b = None if b is None else _prep(b)
-        N, D, H, W, Cin = feat.shape
-        Cout = w.shape[0]
-        pts, sums, sq = _f32((N, Cout, 3), feat.device), _f32((N, Cout, 4), feat.device), _f32((N, Cout), feat.device)
-        if CONV_MODE != "f32" and Cin % 4 == 0:
-            terms = _HEAD_TERMS[CONV_MODE]
-            ws = workspace(int(lib.kmh_headcom_fwd_bf_ws_bytes(N, D * H * W, Cout, terms)), feat.device, "head")
-            check(lib.kmh_headcom_fwd_bf(_p(feat), _p(w), _p(b), _p(pts), _p(sums), _p(sq), None, N, D, H, W, Cin, Cout,
-                                         _t(terms), None, _p(ws), _stream()), "kmh_headcom_fwd_bf")
-        else:
-            ws = workspace(int(lib.kmh_headcom_fwd_ws_bytes(N, D * H * W, Cout)), feat.device, "head")
-            check(lib.kmh_headcom_fwd(_p(feat), _p(w), _p(b), _p(pts), _p(sums), _p(sq), N, D, H, W, Cin, Cout, _p(ws),
-                                      _stream()), "kmh_headcom_fwd")
+        sq = _f32((feat.shape[0], w.shape[0]), feat.device)
+        pts, sums, _, _ = _headcom_fwd(feat, w, b, sq=sq)
         return pts, sums[:, :, 0].contiguous(), sq
 
 

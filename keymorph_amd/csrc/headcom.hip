@@ -391,8 +391,8 @@ __device__ __forceinline__ void split4(const float4 v, uint2 out[TERMS]) {
     out[t].y = h[2] | (h[3] << 16);
   }
 }
-// AMP (KeyMorph(use_amp=True), kmh_conv_set_amp; TERMS == 2 only): the hi x hi product alone, as the reference's autocast
-// runs this convolution in fp16 (keymorph/model.py:176-191)
+// AMP (KeyMorph(use_amp=True): the entry point was called with terms == 1, common.h: KmhAmpCall; TERMS == 2 only): the
+// hi x hi product alone, as the reference's autocast runs this convolution in fp16 (keymorph/model.py:176-191)
 template <int TERMS, bool AMP = false>
 __device__ __forceinline__ f32x16 mfma_split(const bf16x8 a[TERMS], const bf16x8 b[TERMS], f32x16 acc) {
   if constexpr (TERMS == 3) {

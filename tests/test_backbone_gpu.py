@@ -1233,6 +1233,66 @@ def test_lost_lazy_skip_tag_raises(monkeypatch):
         assert torch.equal(p.grad, g_hook[k]), k
 
 
+def _gcr_params(Cin, Cout, seed):
+    g = gen(seed)
+    gamma, beta = 1 + 0.2 * torch.randn(Cin, generator=g), 0.2 * torch.randn(Cin, generator=g)
+    w = torch.randn(Cout, Cin, 3, 3, 3, generator=g) / np.sqrt(27 * Cin)
+    return [t.to(DEV).requires_grad_(True) for t in (gamma, beta, w)]
+
+
+def test_dense_gradient_where_a_blocked_one_was_promised_raises():
+    """A SingleConv told `dy_blocked` (its only consumer returns the gradient channel-blocked) that receives a plain dense
+    gradient -- the layout hand-off was lost, e.g. to a hook -- must refuse: reading it as blocked would scramble channels.
+    The check is the first thing the backward does, before any launch."""
+    from keymorph_amd import backbone_ops as B
+    old = B.CONV_MODE
+    try:
+        B.set_conv_mode("f16x3")
+        x = torch.randn(1, 8, 8, 32, 8, generator=gen(71)).abs().to(DEV).requires_grad_(True)
+        gamma, beta, w = _gcr_params(8, 16, 72)
+        y = B.single_conv_gcr(x, gamma, beta, w, 8, dy_premasked=True, dy_blocked=True)
+        with pytest.raises(RuntimeError, match="KEYMORPH_NO_BLOCKED_GRADS"):
+            y.backward(torch.ones_like(y))
+    finally:
+        B.set_conv_mode(old)
+
+
+def test_dense_gradient_at_the_fused_decoder_operator_raises():
+    """The same at upcat_conv_gcr(dy_blocked=True), at the smallest shape of test_decoder_block_fused_upsample_concat_conv."""
+    from keymorph_amd import backbone_ops as B
+    N, Cs, Cl, Cout, ld = 2, 16, 24, 32, (3, 5, 18)
+    old = B.CONV_MODE
+    try:
+        B.set_conv_mode("f16x3")
+        g = gen(73)
+        skip = torch.randn(N, *(2 * d for d in ld), Cs, generator=g).abs().to(DEV).requires_grad_(True)
+        low = torch.randn(N, *ld, Cl, generator=g).abs().to(DEV).requires_grad_(True)
+        gamma, beta, w = _gcr_params(Cs + Cl, Cout, 74)
+        assert B.upcat_conv_ok(skip, low, Cout)
+        y = B.upcat_conv_gcr(skip, low, gamma, beta, w, 8, dy_premasked=True, dy_blocked=True)
+        with pytest.raises(RuntimeError, match="KEYMORPH_NO_BLOCKED_GRADS"):
+            y.backward(torch.ones_like(y))
+    finally:
+        B.set_conv_mode(old)
+
+
+def test_lost_lazy_first_layer_tag_raises():
+    """The first convolution told `dy_lazy` (the second one hands over its normalised-input gradient with GroupNorm's backward
+    pending) that receives a gradient without that hand-off must refuse: taking it as finished would skip a GroupNorm
+    backward."""
+    from keymorph_amd import backbone_ops as B
+    old = B.CONV_MODE
+    try:
+        B.set_conv_mode("f16x3")
+        img = torch.rand(1, 8, 8, 32, 1, generator=gen(75)).to(DEV)
+        gamma, beta, w = _gcr_params(1, 8, 76)
+        y = B.single_conv_gcr(img, gamma, beta, w, 1, x_from_relu=False, dy_premasked=True, dy_lazy=True)
+        with pytest.raises(RuntimeError, match="KEYMORPH_NO_LAZY_FIRST"):
+            y.backward(torch.ones_like(y))
+    finally:
+        B.set_conv_mode(old)
+
+
 def test_pool_fork_backward_with_a_misaligned_skip_gradient_view():
     """kmh_maxpool3d_bwd's 16-byte kernel reads the second gradient as float4: a channel-slice view whose storage offset is
     not a multiple of 4 floats must take the scalar kernel (round-2 advisor finding) -- same result either way"""

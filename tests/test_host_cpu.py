@@ -499,6 +499,79 @@ def test_amp_scope_is_per_thread_and_travels_with_the_autograd_node():
     assert torch.equal(x.grad, torch.full((3,), 2.0)) and B.amp_enabled() is B._AMP_DEFAULT
 
 
+def test_handoff_round_trip_and_version_guard():
+    """keymorph_amd/_handoff.py: a payload rides on the tensor OBJECT under its key, two keys are independent, and an in-place
+    change of the tensor voids every key; attaching again afterwards is valid."""
+    from keymorph_amd._handoff import attach, peek
+    t, a, b = torch.zeros(4), torch.ones(2), torch.full((2,), 3.0)
+    assert peek(t, "stats") is None and peek(t, "grad_scale") is None
+    attach(t, "stats", a)
+    assert peek(t, "stats") is a and peek(t, "grad_scale") is None
+    attach(t, "grad_scale", b)
+    assert peek(t, "stats") is a and peek(t, "grad_scale") is b
+    attach(t, "stats", b)                                   # replacing one key leaves the other
+    assert peek(t, "stats") is b and peek(t, "grad_scale") is b
+    t.add_(1)
+    assert peek(t, "stats") is None and peek(t, "grad_scale") is None
+    attach(t, "stats", a)
+    assert peek(t, "stats") is a and peek(t, "grad_scale") is None      # the stale key stays void
+    for other in (t.clone(), t.detach(), t.view_as(t)):     # another tensor object carries nothing
+        assert all(peek(other, k) is None for k in ("stats", "grad_scale", "layout", "lazy_gn", "up_sources", "packed"))
+    assert peek(t, "stats") is a
+
+
+def test_handoff_layout_and_up_sources():
+    """The gradient layout is ONE guarded value (absent = dense, 1 = channel-blocked, 2 = pre-split records); the sources of an
+    upsample + concat are void when the output OR either source was modified in place."""
+    from keymorph_amd import backbone_ops as B
+    from keymorph_amd._handoff import attach
+    dense, t1, t2 = torch.zeros(4), torch.zeros(4), torch.zeros(4)
+    attach(t1, "layout", 1)
+    attach(t2, "layout", 2)
+    assert (B._blocked_kind(dense), B._blocked_kind(t1), B._blocked_kind(t2)) == (0, 1, 2)
+    t2.mul_(2)
+    assert B._blocked_kind(t2) == 0
+
+    for touched in ("none", "out", "skip", "low"):
+        skip, low, out = torch.zeros(4), torch.zeros(4), torch.zeros(4)
+        assert B._up_sources(out) is None
+        attach(out, "up_sources", (skip, low, skip._version, low._version))
+        {"none": out.clone(), "out": out, "skip": skip, "low": low}[touched].add_(1)
+        got = B._up_sources(out)
+        if touched == "none":
+            assert got is not None and got[0] is skip and got[1] is low
+        else:
+            assert got is None, touched
+
+
+def test_handoff_expect_raises_both_ways():
+    from keymorph_amd._handoff import attach, expect
+    t = torch.zeros(4)
+    expect(t, "lazy_gn", False, "a test", "KEYMORPH_NO_LAZY_FIRST")
+    with pytest.raises(RuntimeError, match="KEYMORPH_NO_BLOCKED_GRADS"):
+        expect(t, "layout", True, "a test", "KEYMORPH_NO_BLOCKED_GRADS")          # expected, absent
+    attach(t, "layout", 1)
+    expect(t, "layout", True, "a test", "KEYMORPH_NO_BLOCKED_GRADS")
+    with pytest.raises(RuntimeError, match="KEYMORPH_NO_LAZY_SKIP"):
+        expect(t, "layout", False, "a test", "KEYMORPH_NO_LAZY_SKIP")             # present, not expected
+    t.add_(1)
+    with pytest.raises(RuntimeError, match="a test.*KEYMORPH_NO_LAZY_FIRST"):
+        expect(t, "layout", True, "a test", "KEYMORPH_NO_LAZY_FIRST")             # expected, stale
+
+
+def test_switch_reader_follows_the_environment(monkeypatch):
+    from keymorph_amd import backbone_ops as B
+    monkeypatch.delenv("KEYMORPH_NO_UPCONV", raising=False)
+    assert B._off("KEYMORPH_NO_UPCONV") is False
+    monkeypatch.setenv("KEYMORPH_NO_UPCONV", "1")
+    assert B._off("KEYMORPH_NO_UPCONV") is True
+    monkeypatch.delenv("KEYMORPH_NO_UPCONV")
+    assert B._off("KEYMORPH_NO_UPCONV") is False
+    with pytest.raises(KeyError):
+        B._off("KEYMORPH_NO_SUCH_THING")
+    assert all(isinstance(v, str) and v for v in B._SWITCHES.values())
+
+
 def test_bench_plain_run_options_and_output_dump(tmp_path):
     """A plain bench.py run times the headline alone: every side leg's size is 0 unless given, --full turns them all on at
     their sizes, an explicit size wins either way.  dump_outputs writes float32 (float64 stays float64) and replaces an array
