@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "conv_split.h"
+#include "stats_final.h"
 #include <type_traits>
 
 namespace {

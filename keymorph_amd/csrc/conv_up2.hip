@@ -18,6 +18,7 @@
 // Chunks are double-buffered in LDS: the loads of chunk c+1 are in flight during the MFMAs of chunk c.
 #include <cstdlib>
 #include "conv_split.h"
+#include "stats_final.h"
 
 namespace {
 

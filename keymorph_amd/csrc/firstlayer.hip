@@ -11,6 +11,7 @@
 // row sum of dz and two end corrections.  Exact fp32, independent of the convolution arithmetic mode.
 #include <cstdlib>
 #include "common.h"
+#include "stats_final.h"
 
 namespace {
 

@@ -12,6 +12,7 @@
 // registers are directly the A operand of the dW product (k-pair = voxels rho, rho+4).
 #include <type_traits>
 #include "common.h"
+#include "absmax.h"
 
 namespace {
 

@@ -7,6 +7,8 @@
 //   MaxPool3d   : keymorph/unet3d/buildingblocks.py:363, keymorph/layers.py:176
 //   upsample+cat: keymorph/unet3d/buildingblocks.py:471-475, 568-582
 #include "common.h"
+#include "absmax.h"
+#include "stats_final.h"
 
 namespace {
 

@@ -7,59 +7,12 @@
 // owns VPT=4 consecutive output voxels so the grid is read as 3 x 16-B loads and the output
 // written as one 16-B store per channel.
 //
-// Source coordinate (unnorm_clip): ((g + 1) * size - 1) / 2 in fp32 with every operation rounded on its own, as ATen's CPU
-// grid_sampler_3d computes it -- the product is kept out of -ffp-contract=fast's fused multiply-add, because one ulp of the
-// coordinate moves floor() to the neighbouring cell at lattice points (the grid gradient then takes that cell's difference)
-// and flips the clamp mask at the first and last voxel centre.  Then ATen's clip_coordinates_set_grad: <= 0 -> 0 and
-// >= size - 1 -> size - 1, both with a zero derivative.
-// NaN coordinates: clamped to the far border (size - 1) of their axis, as ATen's forward does; a voxel with a NaN
-// coordinate passes no gradient to the grid (all three components 0) nor to the volume, as ATen's backward.  So every
-// coordinate that reaches floor() lies in [0, size - 1] and every corner address derived from it is inside the volume.
-#include "common.h"
-#include <cstdlib>
+// The source coordinate, the NaN rule, the blend and the chunk helpers are shared with warp_dice.hip: sampler_taps.h.
+#include "sampler_taps.h"
 
 namespace {
 
-constexpr int VPT = 4;      // voxels per thread
-constexpr int TPB = 256;    // threads per block
-
-struct Tap {
-  int x0, y0, z0;        // floor corner
-  float fx, fy, fz;      // fractional offsets
-  float mx, my, mz;      // d(ix)/d(gx) incl. clamp mask (W/2 or 0)
-};
-
-__device__ __forceinline__ float unnorm_clip(float g, int size, float& mult) {
-  // ((g+1)*size-1)/2 then clip_coordinates_set_grad: borders count as out of bounds for the grad.  The product is rounded
-  // on its own, as ATen's CPU kernel rounds it: under -ffp-contract=fast it would be fused into the subtraction (one
-  // v_fma_f32, one rounding), and one ulp of the coordinate moves floor() to the neighbouring cell at lattice points and
-  // flips the clamp mask at the first and last voxel centre.  The empty asm makes the product opaque, so it stays a
-  // v_mul_f32 followed by a v_add_f32 (__fmul_rn and `#pragma clang fp contract(off)` are both contracted anyway).
-  float p = (g + 1.f) * (float)size;
-  asm volatile("" : "+v"(p));
-  const float v = (p - 1.f) * 0.5f;
-  const float hi = (float)(size - 1);
-  if (v <= 0.f) { mult = 0.f; return 0.f; }
-  if (!(v < hi)) { mult = 0.f; return hi; }      // v >= hi, and NaN: the far border (ATen's clip_coordinates)
-  mult = 0.5f * (float)size;
-  return v;
-}
-
-// a voxel with a NaN coordinate passes no gradient at all (ATen's backward finds none of its corners inside the volume).
-// Tested where the gradient is written, on the coordinates still in registers or LDS there (not in make_tap: keeping the
-// flag live across the channel loop costs the fused warp + MSE + gradient kernel 6 VGPRs and a wave per SIMD).
-__device__ __forceinline__ bool any_nan(float gx, float gy, float gz) { return gx != gx || gy != gy || gz != gz; }
-
-__device__ __forceinline__ Tap make_tap(float gx, float gy, float gz, int D, int H, int W) {
-  Tap t;
-  float ix = unnorm_clip(gx, W, t.mx);
-  float iy = unnorm_clip(gy, H, t.my);
-  float iz = unnorm_clip(gz, D, t.mz);
-  float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-  t.x0 = (int)fx0; t.y0 = (int)fy0; t.z0 = (int)fz0;
-  t.fx = ix - fx0; t.fy = iy - fy0; t.fz = iz - fz0;
-  return t;
-}
+constexpr int VPT = 4;      // voxels per thread of the plain kernels
 
 // 8 corner values of one channel plane; corners past the far border contribute 0 (weight is 0 there)
 __device__ __forceinline__ void gather8(const float* __restrict__ p, const Tap& t, int D, int H, int W,
@@ -78,22 +31,6 @@ __device__ __forceinline__ void gather8(const float* __restrict__ p, const Tap& 
   v[5] = p[r10 + x1] * (ox * oz);
   v[6] = p[r11 + t.x0] * (oy * oz);
   v[7] = p[r11 + x1] * (ox * oy * oz);
-}
-
-__device__ __forceinline__ float blend8(const float v[8], const Tap& t) {
-  const float ax = 1.f - t.fx, ay = 1.f - t.fy, az = 1.f - t.fz;
-  // same association as ATen: value * (wx*wy*wz) summed corner by corner -- as ONE explicit fma chain, so that every
-  // instantiation of every sampler kernel rounds identically (left to -ffp-contract=fast the fused and the plain warp
-  // differed by 1 ulp in 13 % of the voxels)
-  float o = v[0] * (ax * ay * az);
-  o = fmaf(v[1], t.fx * ay * az, o);
-  o = fmaf(v[2], ax * t.fy * az, o);
-  o = fmaf(v[3], t.fx * t.fy * az, o);
-  o = fmaf(v[4], ax * ay * t.fz, o);
-  o = fmaf(v[5], t.fx * ay * t.fz, o);
-  o = fmaf(v[6], ax * t.fy * t.fz, o);
-  o = fmaf(v[7], t.fx * t.fy * t.fz, o);
-  return o;
 }
 
 __device__ __forceinline__ void load_grid4(const float* __restrict__ grid, long long v0, long long nvox,
@@ -139,7 +76,7 @@ __global__ __launch_bounds__(TPB) void sample_fwd_kernel(
         if (MODE == 0) {
           float v[8];
           gather8(p, t[i], D, H, W, v);
-          o[i] = blend8(v, t[i]);
+          o[i] = blend8(v, t[i].fx, t[i].fy, t[i].fz);
         } else {
           // nearest: nearbyint (half to even) of the clipped coordinate
           int xn = (int)rintf((float)t[i].x0 + t[i].fx);
@@ -209,15 +146,8 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_kernel(
     for (int i = 0; i < VPT; ++i) {
       float v[8];
       gather8(p, t[i], D, H, W, v);
-      const float fx = t[i].fx, fy = t[i].fy, fz = t[i].fz;
-      const float ax = 1.f - fx, ay = 1.f - fy, az = 1.f - fz;
-      // d/dix, d/diy, d/diz of the trilinear blend (ATen grid_sampler_3d_backward)
-      float dx = -v[0] * (ay * az) + v[1] * (ay * az) - v[2] * (fy * az) + v[3] * (fy * az)
-                 - v[4] * (ay * fz) + v[5] * (ay * fz) - v[6] * (fy * fz) + v[7] * (fy * fz);
-      float dy = -v[0] * (ax * az) - v[1] * (fx * az) + v[2] * (ax * az) + v[3] * (fx * az)
-                 - v[4] * (ax * fz) - v[5] * (fx * fz) + v[6] * (ax * fz) + v[7] * (fx * fz);
-      float dz = -v[0] * (ax * ay) - v[1] * (fx * ay) - v[2] * (ax * fy) - v[3] * (fx * fy)
-                 + v[4] * (ax * ay) + v[5] * (fx * ay) + v[6] * (ax * fy) + v[7] * (fx * fy);
+      float dx, dy, dz;
+      blend_grads(v, t[i].fx, t[i].fy, t[i].fz, dx, dy, dz);
       gx[i] += dx * go[i];
       gy[i] += dy * go[i];
       gz[i] += dz * go[i];
@@ -244,30 +174,19 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_kernel(
 }
 
 // ----------------------------------------------------------------------------------------------
-// Lane-contiguous variants (the ones the launchers use whenever W >= 2 and a channel plane has < 2^31 voxels).
-// One voxel per lane per pass, so one gather instruction covers 64 NEIGHBOURING voxels (2-4 cache lines for a
-// smooth grid instead of 8+), the two x-corners of a row come from ONE 8-byte load, all in-plane offsets are
-// 32-bit, and the AoS grid / grid-gradient rows go through LDS so their global accesses are 16-byte coalesced.
-constexpr int PASSES = 4;   // 256-voxel passes per workgroup
-
-struct Tap32 {
-  int r00, r01, r10, r11;   // row offsets (z, y) inside one channel plane, + the pair base xb
-  bool sel;                 // x0 is the last column: the pair was loaded one to the left
+// Lane-contiguous variants (sampler_taps.h: PASSES), with the corner rows as element offsets for flat 8-byte loads.
+struct Tap32 : CornerRows {
   float oy, oz;             // 0 when the +1 corner is past the far border
-  float fx, fy, fz;
 };
 
 __device__ __forceinline__ Tap32 make_tap32(const Tap& t, int D, int H, int W) {
   Tap32 q;
-  const int y1 = t.y0 + 1 < H ? t.y0 + 1 : t.y0, z1 = t.z0 + 1 < D ? t.z0 + 1 : t.z0;
-  q.sel = t.x0 > W - 2;
-  const int xb = q.sel ? W - 2 : t.x0;
-  q.r00 = (t.z0 * H + t.y0) * W + xb; q.r01 = (t.z0 * H + y1) * W + xb;
-  q.r10 = (z1 * H + t.y0) * W + xb;   q.r11 = (z1 * H + y1) * W + xb;
+  static_cast<CornerRows&>(q) = corner_rows(t, D, H, W);
   q.oy = t.y0 + 1 < H ? 1.f : 0.f; q.oz = t.z0 + 1 < D ? 1.f : 0.f;
-  q.fx = t.fx; q.fy = t.fy; q.fz = t.fz;
   return q;
 }
+// a lane past the end of its chunk: any valid address (nothing of it is used)
+__device__ __forceinline__ void park(Tap32& q) { q.r00 = q.r01 = q.r10 = q.r11 = 0; q.sel = false; }
 
 __device__ __forceinline__ void load_pair(const float* __restrict__ p, bool sel, float& lo, float& hi) {
   float2 r;
@@ -285,26 +204,6 @@ __device__ __forceinline__ void gather8_pairs(const float* __restrict__ p, const
   v[6] *= q.oy * q.oz; v[7] *= q.oy * q.oz;
 }
 
-// the workgroup's PASSES*256 grid rows (x, y, z) -> LDS, 16-byte coalesced
-__device__ __forceinline__ void stage_rows(const float* __restrict__ src, int cnt, float* sg, int tid) {
-  if (cnt == TPB * PASSES && ((reinterpret_cast<unsigned long long>(src) & 15) == 0)) {
-#pragma unroll
-    for (int k = 0; k < PASSES * 3 / 4; ++k)
-      reinterpret_cast<float4*>(sg)[tid + k * TPB] = reinterpret_cast<const float4*>(src)[tid + k * TPB];
-  } else {
-    for (int e = tid; e < cnt * 3; e += TPB) sg[e] = src[e];
-  }
-}
-__device__ __forceinline__ void unstage_rows(float* __restrict__ dst, int cnt, const float* sg, int tid) {
-  if (cnt == TPB * PASSES && ((reinterpret_cast<unsigned long long>(dst) & 15) == 0)) {
-#pragma unroll
-    for (int k = 0; k < PASSES * 3 / 4; ++k)
-      reinterpret_cast<float4*>(dst)[tid + k * TPB] = reinterpret_cast<const float4*>(sg)[tid + k * TPB];
-  } else {
-    for (int e = tid; e < cnt * 3; e += TPB) dst[e] = sg[e];
-  }
-}
-
 // FUSE_GRAD (with FUSE_MSE): the loss is mean((out - fixed)^2), whose cotangent 2 (out - fixed) / count is known right
 // here, so the same pass also produces d(loss)/d(grid) -- the rows of the staged grid are overwritten with it and written
 // out like the grid came in.  One launch and 36 B per voxel instead of three (warp, MSE backward, grid backward) and 68.
@@ -317,7 +216,7 @@ __global__ __launch_bounds__(TPB) void sample_fwd_lc_kernel(
   const int n = blockIdx.y, tid = threadIdx.x;
   // (one contiguous chunk range per XCD -- xcd_remap of the block index -- measured slower: DESIGN.md section 8, round 4)
   const long long vb = (long long)blockIdx.x * (TPB * PASSES);
-  const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
+  const int cnt = chunk_count(ovox, vb);
   stage_rows(grid + ((long long)n * ovox + vb) * 3, cnt, sg, tid);
   __syncthreads();
   const long long plane = (long long)D * H * W;
@@ -333,7 +232,7 @@ __global__ __launch_bounds__(TPB) void sample_fwd_lc_kernel(
       const int l = tid + (j0 + u) * TPB;             // lane-contiguous: voxel vb + l
       t[u] = make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W);
       q[u] = make_tap32(t[u], D, H, W);
-      if (l >= cnt) { q[u].r00 = q[u].r01 = q[u].r10 = q[u].r11 = 0; q[u].sel = false; }   // any valid address
+      if (l >= cnt) park(q[u]);
       near[u] = 0;
       if (MODE != 0 && l < cnt) {
         const int xn = (int)rintf((float)t[u].x0 + t[u].fx), yn = (int)rintf((float)t[u].y0 + t[u].fy),
@@ -357,20 +256,12 @@ __global__ __launch_bounds__(TPB) void sample_fwd_lc_kernel(
 #pragma unroll
         for (int u = 0; u < ILP; ++u) gather8_pairs(p, q[u], v[u]);
 #pragma unroll
-        for (int u = 0; u < ILP; ++u) o[u] = blend8(v[u], t[u]);
+        for (int u = 0; u < ILP; ++u) o[u] = blend8(v[u], t[u].fx, t[u].fy, t[u].fz);
         if (FUSE_GRAD) {
 #pragma unroll
           for (int u = 0; u < ILP; ++u) {
-            const float fx = t[u].fx, fy = t[u].fy, fz = t[u].fz;
-            const float ax = 1.f - fx, ay = 1.f - fy, az = 1.f - fz;
-            const float* w = v[u];
-            // d/dix, d/diy, d/diz of the trilinear blend (ATen grid_sampler_3d_backward), as sample_bwd_grid_lc_kernel
-            const float dx = -w[0] * (ay * az) + w[1] * (ay * az) - w[2] * (fy * az) + w[3] * (fy * az)
-                             - w[4] * (ay * fz) + w[5] * (ay * fz) - w[6] * (fy * fz) + w[7] * (fy * fz);
-            const float dy = -w[0] * (ax * az) - w[1] * (fx * az) + w[2] * (ax * az) + w[3] * (fx * az)
-                             - w[4] * (ax * fz) - w[5] * (fx * fz) + w[6] * (ax * fz) + w[7] * (fx * fz);
-            const float dz = -w[0] * (ax * ay) - w[1] * (fx * ay) - w[2] * (ax * fy) - w[3] * (fx * fy)
-                             + w[4] * (ax * ay) + w[5] * (fx * ay) + w[6] * (ax * fy) + w[7] * (fx * fy);
+            float dx, dy, dz;
+            blend_grads(v[u], t[u].fx, t[u].fy, t[u].fz, dx, dy, dz);
             const float go = (tid + (j0 + u) * TPB < cnt) ? (o[u] - fv[u]) * gcoef : 0.f;
             ggx[u] += dx * go; ggy[u] += dy * go; ggz[u] += dz * go;
           }
@@ -388,13 +279,10 @@ __global__ __launch_bounds__(TPB) void sample_fwd_lc_kernel(
         }
       }
     }
-    if (FUSE_GRAD) {      // each lane owns its rows of sg: coordinates in, gradient out
+    if (FUSE_GRAD) {
 #pragma unroll
-      for (int u = 0; u < ILP; ++u) {
-        const int l = tid + (j0 + u) * TPB;
-        const float k = any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2]) ? 0.f : 1.f;
-        sg[l * 3] = ggx[u] * t[u].mx * k; sg[l * 3 + 1] = ggy[u] * t[u].my * k; sg[l * 3 + 2] = ggz[u] * t[u].mz * k;
-      }
+      for (int u = 0; u < ILP; ++u)
+        grad_row_out(sg, tid + (j0 + u) * TPB, ggx[u], ggy[u], ggz[u], t[u].mx, t[u].my, t[u].mz);
     }
   }
   if (FUSE_GRAD) {
@@ -415,7 +303,7 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_lc_kernel(
   constexpr int ILP = 2;                   // voxels whose 4 pair-gathers are in flight together (ILP = 1: 151 us, 2: 138 us)
   const int n = blockIdx.y, tid = threadIdx.x;
   const long long vb = (long long)blockIdx.x * (TPB * PASSES);
-  const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
+  const int cnt = chunk_count(ovox, vb);
   stage_rows(grid + ((long long)n * ovox + vb) * 3, cnt, sg, tid);
   __syncthreads();
   const long long plane = (long long)D * H * W;
@@ -430,7 +318,7 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_lc_kernel(
       const int l = tid + (j0 + u) * TPB;
       t[u] = make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W);
       q[u] = make_tap32(t[u], D, H, W);
-      if (l >= cnt) { q[u].r00 = q[u].r01 = q[u].r10 = q[u].r11 = 0; q[u].sel = false; }
+      if (l >= cnt) park(q[u]);
       gx[u] = gy[u] = gz[u] = 0.f;
     }
     for (int c = 0; c < C; ++c) {
@@ -445,268 +333,16 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_lc_kernel(
       }
 #pragma unroll
       for (int u = 0; u < ILP; ++u) {
-        const float fx = t[u].fx, fy = t[u].fy, fz = t[u].fz;
-        const float ax = 1.f - fx, ay = 1.f - fy, az = 1.f - fz;
-        const float* w = v[u];
-        // d/dix, d/diy, d/diz of the trilinear blend (ATen grid_sampler_3d_backward)
-        const float dx = -w[0] * (ay * az) + w[1] * (ay * az) - w[2] * (fy * az) + w[3] * (fy * az)
-                         - w[4] * (ay * fz) + w[5] * (ay * fz) - w[6] * (fy * fz) + w[7] * (fy * fz);
-        const float dy = -w[0] * (ax * az) - w[1] * (fx * az) + w[2] * (ax * az) + w[3] * (fx * az)
-                         - w[4] * (ax * fz) - w[5] * (fx * fz) + w[6] * (ax * fz) + w[7] * (fx * fz);
-        const float dz = -w[0] * (ax * ay) - w[1] * (fx * ay) - w[2] * (ax * fy) - w[3] * (fx * fy)
-                         + w[4] * (ax * ay) + w[5] * (fx * ay) + w[6] * (ax * fy) + w[7] * (fx * fy);
+        float dx, dy, dz;
+        blend_grads(v[u], t[u].fx, t[u].fy, t[u].fz, dx, dy, dz);
         gx[u] += dx * go[u]; gy[u] += dy * go[u]; gz[u] += dz * go[u];
       }
     }
 #pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-      const int l = tid + (j0 + u) * TPB;
-      const float k = any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2]) ? 0.f : 1.f;
-      sg[l * 3] = gx[u] * t[u].mx * k; sg[l * 3 + 1] = gy[u] * t[u].my * k; sg[l * 3 + 2] = gz[u] * t[u].mz * k;
-    }
+    for (int u = 0; u < ILP; ++u) grad_row_out(sg, tid + (j0 + u) * TPB, gx[u], gy[u], gz[u], t[u].mx, t[u].my, t[u].mz);
   }
   __syncthreads();
   unstage_rows(dgrid + ((long long)n * ovox + vb) * 3, cnt, sg, tid);
-}
-
-// ----------------------------------------------------------------------------------------------
-// Fused align_img + soft DiceLoss (scripts/train.py:146-164 with loss_fn == "dice"; keymorph/utils.py:14-21,
-// keymorph/loss_ops.py:16-63) WITHOUT the warped segmentation ever being stored.  Dice couples every voxel of a
-// (sample, channel) row through its three sums, so the cotangent of the warp is only known after a full pass:
-//   pass A (warp_dice_sums_kernel)  per (n, c): sum t p, sum p^2, sum t^2 with p = warp(x)[n, c] recomputed on the fly;
-//   host: loss rows 1 - (2 I + 1) / (P + T + 1), and for the backward ca = -2 g / den, cb = 2 g num / den^2;
-//   pass B (warp_dice_grad_kernel)  d(loss)/d(grid) = sum_c (ca[n,c] t + cb[n,c] p) * d p / d grid, p recomputed again.
-// Per output voxel: A reads 12 + 8 C bytes, B reads 12 + 8 C and writes 12 -- the three-launch route (warp, Dice sums,
-// axpby, grid backward) moves 24 + 32 C.  Both kernels are persistent over 1024-voxel chunks (lane-contiguous like
-// sample_fwd_lc_kernel) and fetch the NEXT chunk's grid rows into registers before the current chunk's gathers.
-// ILP = voxels of a lane whose gathers are in flight together (PASSES / ILP sub-passes per chunk)
-constexpr int WD_MAXC = 128;
-
-struct GridRows { float4 a, b, c; };      // PASSES * 3 / 4 = 3 float4 per thread (named members: an array went to scratch)
-static_assert(PASSES * 3 / 4 == 3, "GridRows holds three float4 per thread");
-
-__device__ __forceinline__ bool rows_fast(const float* src, int cnt) {
-  return cnt == TPB * PASSES && ((reinterpret_cast<unsigned long long>(src) & 15) == 0);
-}
-__device__ __forceinline__ void fetch_rows(const float* __restrict__ src, bool fast, GridRows& g, int tid) {
-  if (fast) {
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    g.a = s4[tid]; g.b = s4[tid + TPB]; g.c = s4[tid + 2 * TPB];
-  }
-}
-__device__ __forceinline__ void commit_rows(const float* __restrict__ src, int cnt, bool fast, const GridRows& g, float* sg,
-                                            int tid) {
-  if (fast) {
-    float4* d4 = reinterpret_cast<float4*>(sg);
-    d4[tid] = g.a; d4[tid + TPB] = g.b; d4[tid + 2 * TPB] = g.c;
-  } else {
-    for (int e = tid; e < cnt * 3; e += TPB) sg[e] = src[e];
-  }
-}
-
-__device__ __forceinline__ void blend_grads(const float w[8], const Tap& t, float& dx, float& dy, float& dz) {
-  const float fx = t.fx, fy = t.fy, fz = t.fz;
-  const float ax = 1.f - fx, ay = 1.f - fy, az = 1.f - fz;
-  // d/dix, d/diy, d/diz of the trilinear blend (ATen grid_sampler_3d_backward), as sample_bwd_grid_lc_kernel
-  dx = -w[0] * (ay * az) + w[1] * (ay * az) - w[2] * (fy * az) + w[3] * (fy * az)
-       - w[4] * (ay * fz) + w[5] * (ay * fz) - w[6] * (fy * fz) + w[7] * (fy * fz);
-  dy = -w[0] * (ax * az) - w[1] * (fx * az) + w[2] * (ax * az) + w[3] * (fx * az)
-       - w[4] * (ax * fz) - w[5] * (fx * fz) + w[6] * (ax * fz) + w[7] * (fx * fz);
-  dz = -w[0] * (ax * ay) - w[1] * (fx * ay) - w[2] * (ax * fy) - w[3] * (fx * fy)
-       + w[4] * (ax * ay) + w[5] * (fx * ay) + w[6] * (ax * fy) + w[7] * (fx * fy);
-}
-
-// Gathers go through BUFFER loads: the channel plane's base lives in a scalar descriptor that the channel loop advances
-// with two scalar adds, the per-voxel part is a 32-bit byte offset computed once per chunk -- no 64-bit VALU address
-// arithmetic and no address registers per load (flat loads cost this loop 2 VALU + 2 VGPRs per gather), and lanes past
-// the end of a chunk read zeros from the range check instead of needing clamped addresses.
-typedef unsigned kmh_u2 __attribute__((vector_size(8)));      // the builtin's own return type (an ext_vector_type
-                                                              // of the same size converts by SPLATTING element 0)
-struct TapB {
-  unsigned o00, o01, o10, o11;   // byte offsets of the four x-pairs inside one channel plane
-  bool sel;                      // x0 is the last column: the pair was loaded one to the left
-  float fx, fy, fz;
-};
-__device__ __forceinline__ TapB make_tapb(const Tap& t, int D, int H, int W) {
-  TapB q;
-  const int y1 = t.y0 + 1 < H ? t.y0 + 1 : t.y0, z1 = t.z0 + 1 < D ? t.z0 + 1 : t.z0;   // (fy = 0 / fz = 0 there)
-  q.sel = t.x0 > W - 2;
-  const int xb = q.sel ? W - 2 : t.x0;
-  q.o00 = 4u * (unsigned)((t.z0 * H + t.y0) * W + xb); q.o01 = 4u * (unsigned)((t.z0 * H + y1) * W + xb);
-  q.o10 = 4u * (unsigned)((z1 * H + t.y0) * W + xb);   q.o11 = 4u * (unsigned)((z1 * H + y1) * W + xb);
-  q.fx = t.fx; q.fy = t.fy; q.fz = t.fz;
-  return q;
-}
-__device__ __forceinline__ void pair_b(__amdgpu_buffer_rsrc_t r, unsigned off, bool sel, float& lo, float& hi) {
-  const kmh_u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
-  // (scalars first: __builtin_bit_cast applied directly to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
-  const unsigned ua = v[0], ub = v[1];
-  const float a = __uint_as_float(ua), b = __uint_as_float(ub);
-  lo = sel ? b : a;
-  hi = sel ? 0.f : b;
-}
-__device__ __forceinline__ void gather8_b(__amdgpu_buffer_rsrc_t r, const TapB& q, float v[8]) {
-  pair_b(r, q.o00, q.sel, v[0], v[1]);
-  pair_b(r, q.o01, q.sel, v[2], v[3]);
-  pair_b(r, q.o10, q.sel, v[4], v[5]);
-  pair_b(r, q.o11, q.sel, v[6], v[7]);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float blend8f(const float v[8], float fx, float fy, float fz) {
-  Tap t;
-  t.fx = fx; t.fy = fy; t.fz = fz;
-  return blend8(v, t);
-}
-
-// Walk over a sample's chunks for a PERSISTENT launch (gridDim.x a multiple of 8): XCD k (= blockIdx.x % 8: observed
-// dispatch order, used for locality only -- any placement is correct) owns ONE contiguous range of chunks and its resident
-// blocks sweep it side by side, so that chunks next to each other (a rotated grid makes a 4-row chunk touch ~50 source rows
-// that its neighbours touch too) meet in one L2.  Measured: the same speed and the same FETCH_SIZE as the plain strided
-// walk at 2 x 14 x 256^3 (the duplicate fetches are not cross-XCD duplicates: DESIGN.md section 8); kept because it is no
-// slower and the kernels need a chunk loop for the prefetch of the next chunk's grid rows anyway.
-struct ChunkWalk { int cur, end, step; };
-__device__ __forceinline__ ChunkWalk chunk_walk(int b, int nb, int nchunk) {
-  const int NX = nb < 8 ? nb : 8;            // fewer than 8 blocks: as many ranges as blocks (every range needs an owner)
-  const int xcd = b % NX, idx = b / NX;
-  const int q = nchunk / NX, r = nchunk % NX;
-  ChunkWalk w;
-  const int lo = xcd * q + (xcd < r ? xcd : r);
-  w.end = lo + q + (xcd < r ? 1 : 0);
-  w.step = (nb - xcd + NX - 1) / NX;          // blocks of this launch row that sit on this XCD
-  w.cur = lo + idx;
-  return w;
-}
-
-// LAB variants: both segmentations are exactly one-hot (what scripts/train.py:54-79 builds: one_hot of a label map,
-// augmented with NEAREST sampling), so a voxel's C channel values are determined by ONE byte.  kmh_onehot_to_labels checks
-// that on the device and writes the label maps; the kernels then gather 8 corner LABELS per voxel once instead of 8 corner
-// values per channel (56 B of gathers and 56 B of fixed-segmentation reads per voxel become 8 + 1), and feed
-// v_k = [label_k == c] into the SAME blend / derivative arithmetic: bit-identical results.  `gate` (device int): the LAB
-// kernels return at once when it reads 0, the dense ones when it reads non-zero -- no host synchronisation decides.
-struct LabTaps { unsigned c[8]; unsigned t; };      // 8 corner labels (255 = none) and the fixed label
-__device__ __forceinline__ unsigned ld_lab(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, (int)off, 0, 0) & 255u;
-}
-// q's byte offsets are 4 * voxel index: the label map has one byte per voxel
-__device__ __forceinline__ void gather_labels(__amdgpu_buffer_rsrc_t r, const TapB& q, bool live, LabTaps& L) {
-  const unsigned o[4] = {q.o00 >> 2, q.o01 >> 2, q.o10 >> 2, q.o11 >> 2};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned a = ld_lab(r, o[k]), b = ld_lab(r, o[k] + 1u);
-    L.c[2 * k] = live ? (q.sel ? b : a) : 255u;             // as pair_b: the last column's pair sits one to the left
-    L.c[2 * k + 1] = (live && !q.sel) ? b : 255u;
-  }
-}
-
-// partial: (N, gridDim.x, C, 3) doubles
-template <int WD_ILP, bool LAB = false>
-__global__ __launch_bounds__(TPB) void warp_dice_sums_kernel(
-    const float* __restrict__ x, const float* __restrict__ grid, const float* __restrict__ fixed,
-    double* __restrict__ partial, int C, int D, int H, int W, long long ovox, int nchunk,
-    const unsigned char* __restrict__ labx = nullptr, const unsigned char* __restrict__ labf = nullptr,
-    const int* __restrict__ gate = nullptr) {
-  if (gate && ((*gate != 0) != LAB)) return;           // uniform: the other variant of this launch pair does the work
-  __shared__ __attribute__((aligned(16))) float sg[TPB * PASSES * 3];
-  __shared__ double racc[TPB / kWave][WD_MAXC][3];
-  const int n = blockIdx.y, tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
-  for (int e = tid; e < (TPB / kWave) * WD_MAXC * 3; e += TPB) (&racc[0][0][0])[e] = 0.0;
-  const long long plane = (long long)D * H * W;
-  const unsigned plane_bytes = (unsigned)(plane * 4);
-  const float* gbase = grid + (long long)n * ovox * 3;
-  const ChunkWalk cw = chunk_walk(blockIdx.x, gridDim.x, nchunk);
-  int chunk = cw.cur;
-  GridRows nxt = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-  bool nfast = false;
-  if (chunk < cw.end) {
-    const long long vb = (long long)chunk * (TPB * PASSES);
-    const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
-    nfast = rows_fast(gbase + vb * 3, cnt);
-    fetch_rows(gbase + vb * 3, nfast, nxt, tid);
-  }
-#pragma unroll 1
-  for (; chunk < cw.end; chunk += cw.step) {
-    const long long vb = (long long)chunk * (TPB * PASSES);
-    const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
-    __syncthreads();                                  // the previous chunk's readers of sg are done
-    commit_rows(gbase + vb * 3, cnt, nfast, nxt, sg, tid);
-    __syncthreads();
-    {                                                 // the next chunk's rows: in flight under this chunk's gathers
-      const int c2 = chunk + cw.step;
-      if (c2 < cw.end) {
-        const long long vb2 = (long long)c2 * (TPB * PASSES);
-        const int cnt2 = ovox - vb2 < TPB * PASSES ? (int)(ovox - vb2) : TPB * PASSES;
-        nfast = rows_fast(gbase + vb2 * 3, cnt2);
-        fetch_rows(gbase + vb2 * 3, nfast, nxt, tid);
-      }
-    }
-#pragma unroll 1
-    for (int j0 = 0; j0 < PASSES; j0 += WD_ILP) {
-      TapB q[WD_ILP];
-#pragma unroll
-      for (int u = 0; u < WD_ILP; ++u) {
-        const int l = tid + (j0 + u) * TPB;
-        q[u] = make_tapb(make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W), D, H, W);
-        if (l >= cnt) {     // past the chunk: every corner reads 0 through the range check, and the weights must be finite
-          q[u].o00 = q[u].o01 = q[u].o10 = q[u].o11 = plane_bytes;      // (sg holds stale LDS there: 0 * NaN would poison
-          q[u].fx = q[u].fy = q[u].fz = 0.f;                             //  the wave's sums)
-        }
-      }
-      const int left = cnt - j0 * TPB;                 // voxels of the chunk from this sub-pass on (may be <= 0)
-      const unsigned fbytes = left > 0 ? 4u * (unsigned)left : 0u;
-      LabTaps lab[WD_ILP];
-      if constexpr (LAB) {
-        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(labx + (long long)n * plane), 0, (int)plane, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(labf + (long long)n * ovox + vb + j0 * TPB), 0, left > 0 ? left : 0, 0x00020000);
-#pragma unroll
-        for (int u = 0; u < WD_ILP; ++u) {
-          const bool live = tid + (j0 + u) * TPB < cnt;
-          gather_labels(rl, q[u], live, lab[u]);
-          const unsigned t = ld_lab(rt, (unsigned)(tid + u * TPB));
-          lab[u].t = live ? t : 255u;
-        }
-      }
-#pragma unroll 1
-      for (int c = 0; c < C; ++c) {
-        float v[WD_ILP][8], tv[WD_ILP];
-        if constexpr (LAB) {
-#pragma unroll
-          for (int u = 0; u < WD_ILP; ++u) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[u][k] = lab[u].c[k] == (unsigned)c ? 1.f : 0.f;
-            tv[u] = lab[u].t == (unsigned)c ? 1.f : 0.f;
-          }
-        } else {
-          const __amdgpu_buffer_rsrc_t rx = make_rsrc(x + ((long long)n * C + c) * plane, plane_bytes);
-          const __amdgpu_buffer_rsrc_t rf = make_rsrc(fixed + ((long long)n * C + c) * ovox + vb + j0 * TPB, fbytes);
-#pragma unroll
-          for (int u = 0; u < WD_ILP; ++u) {
-            gather8_b(rx, q[u], v[u]);
-            tv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, 4 * (tid + u * TPB), 0, 0));
-          }
-        }
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int u = 0; u < WD_ILP; ++u) {
-          const float o = blend8f(v[u], q[u].fx, q[u].fy, q[u].fz);      // 0 for lanes past the chunk (all corners read 0)
-          s0 = fmaf(tv[u], o, s0); s1 = fmaf(o, o, s1); s2 = fmaf(tv[u], tv[u], s2);
-        }
-        s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-        if (lane == 0) { racc[wid][c][0] += (double)s0; racc[wid][c][1] += (double)s1; racc[wid][c][2] += (double)s2; }
-      }
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < C * 3; e += TPB) {
-    const int c = e / 3, k = e - c * 3;
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < TPB / kWave; ++w) s += racc[w][c][k];
-    partial[(((long long)n * gridDim.x + blockIdx.x) * C + c) * 3 + k] = s;
-  }
 }
 
 // Multi-channel bilinear warp (align_img of a one-hot segmentation, keymorph/utils.py:14-21 under
@@ -795,7 +431,7 @@ __device__ __forceinline__ void mc_box_channels(const float* __restrict__ x, flo
         __builtin_memcpy(&r, box + lo[u][k], sizeof(float2));      // 4-byte aligned pair: ds_read2_b32
         v[2 * k] = r.x; v[2 * k + 1] = r.y;
       }
-      const float o = blend8f(v, fr[u][0], fr[u][1], fr[u][2]);
+      const float o = blend8(v, fr[u][0], fr[u][1], fr[u][2]);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), ro, (int)oo[u], 0, 0);      // dropped past the volume
     }
   }
@@ -814,27 +450,21 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
   const unsigned plane_bytes = (unsigned)(plane * 4), out_bytes = (unsigned)(ovox * 4);
   const float* gbase = grid + (long long)n * ovox * 3;
   const int lx = tid & (MT_X - 1), ly = (tid >> MT_LX) & (MT_Y - 1), lz = tid >> MT_LXY, dzp = TPB >> MT_LXY;      // pass u: plane lz + u * dzp
+  struct TileAt { int tx, ty, tz; };
+  auto tile_at = [&](int tile) { return TileAt{tile % ntx, (tile / ntx) % nty, tile / (ntx * nty)}; };      // x-fastest
   // the tile's 32 grid rows (96 floats each) as 768 float4: thread t owns numbers t, t + 256, t + 512
-  auto row_src = [&](int tile, int idx, bool& ok) -> const float* {
-    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+  auto row4 = [&](int tile, int idx) -> float4 {       // (zeros for the rows of a tile that ends past the volume in y or z)
+    const auto [tx, ty, tz] = tile_at(tile);
     const int r = idx / MT_Q4, q4 = idx - r * MT_Q4;
     const int z = tz * MT_Z + r / MT_Y, y = ty * MT_Y + (r & (MT_Y - 1));
-    ok = z < Do && y < Ho;
-    return gbase + (((long long)z * Ho + y) * Wo + tx * MT_X) * 3 + q4 * 4;
+    const float* p = gbase + (((long long)z * Ho + y) * Wo + tx * MT_X) * 3 + q4 * 4;
+    return z < Do && y < Ho ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
   };
   auto tile_fast = [&](int tile) -> bool {       // whole 32-voxel rows, 16-byte aligned: Wo % 4 == 0 and the tile inside in x
-    const int tx = tile % ntx;
+    const int tx = tile_at(tile).tx;
     return (Wo & 3) == 0 && tx * MT_X + MT_X <= Wo && ((reinterpret_cast<unsigned long long>(gbase) & 15) == 0);
   };
-  auto fetch = [&](int tile, GridRows& g) {
-    bool ok;
-    const float* p0 = row_src(tile, tid, ok);
-    g.a = ok ? *reinterpret_cast<const float4*>(p0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* p1 = row_src(tile, tid + TPB, ok);
-    g.b = ok ? *reinterpret_cast<const float4*>(p1) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* p2 = row_src(tile, tid + 2 * TPB, ok);
-    g.c = ok ? *reinterpret_cast<const float4*>(p2) : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
+  auto fetch = [&](int tile, GridRows& g) { g.a = row4(tile, tid); g.b = row4(tile, tid + TPB); g.c = row4(tile, tid + 2 * TPB); };
   const ChunkWalk cw = chunk_walk(blockIdx.x, gridDim.x, ntile);
   int tile = cw.cur;
   GridRows nxt = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
@@ -845,7 +475,7 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
   }
 #pragma unroll 1
   for (; tile < cw.end; tile += cw.step) {
-    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    const auto [tx, ty, tz] = tile_at(tile);
     const int x0 = tx * MT_X, y0 = ty * MT_Y, z0 = tz * MT_Z;
     __syncthreads();                                  // the previous tile's readers of sg / box are done
     if (nfast) {
@@ -867,6 +497,10 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
       }
     }
     const bool in_xy = x0 + lx < Wo && y0 + ly < Ho;
+    // byte offset of the lane's output voxel of plane z inside a channel plane; a dead lane's store is dropped by the range check
+    auto out_off = [&](bool live, int z) -> unsigned {
+      return live ? 4u * (unsigned)(((long long)z * Ho + (y0 + ly)) * Wo + (x0 + lx)) : 0xfffffffcu;
+    };
     bool boxed = false;
     if (use_box) {
       // corners of the lane's 4 voxels (one per tile plane) and the box that holds every live corner of the tile
@@ -880,9 +514,10 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
         const Tap t = make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W);
         const bool live = in_xy && z < Do;
         cx[u] = t.x0; cy[u] = t.y0; cz[u] = t.z0;      // (the pair of x0 = W - 1 takes a zero from past the box's last column)
-        cy1[u] = t.y0 + 1 < H ? t.y0 + 1 : t.y0; cz1[u] = t.z0 + 1 < D ? t.z0 + 1 : t.z0;
+        const CornerRows cr = corner_rows(t, D, H, W);
+        cy1[u] = cr.y1; cz1[u] = cr.z1;
         fr[u][0] = t.fx; fr[u][1] = t.fy; fr[u][2] = t.fz;
-        oo[u] = live ? 4u * (unsigned)(((long long)z * Ho + (y0 + ly)) * Wo + (x0 + lx)) : 0xfffffffcu;
+        oo[u] = out_off(live, z);
         if (live) {
           mn[0] = cx[u] < mn[0] ? cx[u] : mn[0]; mx[0] = cx[u] + 1 > mx[0] ? cx[u] + 1 : mx[0];
           mn[1] = cy[u] < mn[1] ? cy[u] : mn[1]; mx[1] = cy1[u] > mx[1] ? cy1[u] : mx[1];
@@ -939,15 +574,15 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
 #pragma unroll 1
     for (int j0 = 0; j0 < PASSES; j0 += MC_ILP) {
       TapB q[MC_ILP];
-      unsigned oo[MC_ILP];                            // byte offset of the lane's output voxel inside a channel plane
+      unsigned oo[MC_ILP];
 #pragma unroll
       for (int u = 0; u < MC_ILP; ++u) {
         const int l = tid + (j0 + u) * TPB;
         const int z = z0 + lz + (j0 + u) * dzp;
         q[u] = make_tapb(make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W), D, H, W);
         const bool live = in_xy && z < Do;
-        oo[u] = live ? 4u * (unsigned)(((long long)z * Ho + (y0 + ly)) * Wo + (x0 + lx)) : 0xfffffffcu;   // dropped by the range check
-        if (!live) q[u].o00 = q[u].o01 = q[u].o10 = q[u].o11 = plane_bytes;      // reads zeros
+        oo[u] = out_off(live, z);
+        if (!live) park(q[u], plane_bytes);
       }
 #pragma unroll 2
       for (int c = 0; c < C; ++c) {
@@ -958,181 +593,12 @@ __global__ __launch_bounds__(TPB, 3) void sample_fwd_mc_kernel(
         for (int u = 0; u < MC_ILP; ++u) gather8_b(rx, q[u], v[u]);
 #pragma unroll
         for (int u = 0; u < MC_ILP; ++u) {
-          const float o = blend8f(v[u], q[u].fx, q[u].fy, q[u].fz);
+          const float o = blend8(v[u], q[u].fx, q[u].fy, q[u].fz);
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), ro, (int)oo[u], 0, 0);
         }
       }
     }
   }
-}
-
-// partial (N, nb, C, 3) -> sums (N*C, 3) floats: one wave per (n, c, k), fixed order
-__global__ __launch_bounds__(TPB) void warp_dice_final_kernel(const double* __restrict__ partial, int nb, int C, int total,
-                                                              float* __restrict__ sums) {
-  const int e = blockIdx.x * (TPB / kWave) + (threadIdx.x >> 6);
-  if (e >= total) return;
-  const int lane = threadIdx.x & 63;
-  const int n = e / (C * 3), r = e - n * (C * 3);
-  const double* p = partial + (long long)n * nb * C * 3 + r;
-  double s = 0.0;
-  for (int b = lane; b < nb; b += kWave) s += p[(long long)b * C * 3];
-  s = wave_sum(s);
-  if (lane == 0) sums[e] = (float)s;
-}
-
-template <int WD_ILP, bool LAB = false>
-__global__ __launch_bounds__(TPB) void warp_dice_grad_kernel(
-    const float* __restrict__ x, const float* __restrict__ grid, const float* __restrict__ fixed,
-    const float* __restrict__ ca, const float* __restrict__ cb, float* __restrict__ dgrid, int C, int D, int H, int W,
-    long long ovox, int nchunk, const unsigned char* __restrict__ labx = nullptr,
-    const unsigned char* __restrict__ labf = nullptr, const int* __restrict__ gate = nullptr) {
-  if (gate && ((*gate != 0) != LAB)) return;
-  __shared__ __attribute__((aligned(16))) float sg[TPB * PASSES * 3];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const long long plane = (long long)D * H * W;
-  const unsigned plane_bytes = (unsigned)(plane * 4);
-  const float* gbase = grid + (long long)n * ovox * 3;
-  const ChunkWalk cw = chunk_walk(blockIdx.x, gridDim.x, nchunk);
-  int chunk = cw.cur;
-  GridRows nxt = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-  bool nfast = false;
-  if (chunk < cw.end) {
-    const long long vb = (long long)chunk * (TPB * PASSES);
-    const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
-    nfast = rows_fast(gbase + vb * 3, cnt);
-    fetch_rows(gbase + vb * 3, nfast, nxt, tid);
-  }
-#pragma unroll 1
-  for (; chunk < cw.end; chunk += cw.step) {
-    const long long vb = (long long)chunk * (TPB * PASSES);
-    const int cnt = ovox - vb < TPB * PASSES ? (int)(ovox - vb) : TPB * PASSES;
-    __syncthreads();                                  // the previous chunk's gradient rows have left sg
-    commit_rows(gbase + vb * 3, cnt, nfast, nxt, sg, tid);
-    __syncthreads();
-    {
-      const int c2 = chunk + cw.step;
-      if (c2 < cw.end) {
-        const long long vb2 = (long long)c2 * (TPB * PASSES);
-        const int cnt2 = ovox - vb2 < TPB * PASSES ? (int)(ovox - vb2) : TPB * PASSES;
-        nfast = rows_fast(gbase + vb2 * 3, cnt2);
-        fetch_rows(gbase + vb2 * 3, nfast, nxt, tid);
-      }
-    }
-#pragma unroll 1
-    for (int j0 = 0; j0 < PASSES; j0 += WD_ILP) {
-      TapB q[WD_ILP];
-      float gx[WD_ILP], gy[WD_ILP], gz[WD_ILP];
-#pragma unroll
-      for (int u = 0; u < WD_ILP; ++u) {
-        const int l = tid + (j0 + u) * TPB;
-        q[u] = make_tapb(make_tap(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2], D, H, W), D, H, W);
-        if (l >= cnt) {     // reads 0 with finite weights: no contribution (and nothing of this row is stored)
-          q[u].o00 = q[u].o01 = q[u].o10 = q[u].o11 = plane_bytes;
-          q[u].fx = q[u].fy = q[u].fz = 0.f;
-        }
-        gx[u] = gy[u] = gz[u] = 0.f;
-      }
-      const int left = cnt - j0 * TPB;
-      const unsigned fbytes = left > 0 ? 4u * (unsigned)left : 0u;
-      LabTaps lab[WD_ILP];
-      if constexpr (LAB) {
-        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(labx + (long long)n * plane), 0, (int)plane, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned char*>(labf + (long long)n * ovox + vb + j0 * TPB), 0, left > 0 ? left : 0, 0x00020000);
-#pragma unroll
-        for (int u = 0; u < WD_ILP; ++u) {
-          const bool live = tid + (j0 + u) * TPB < cnt;
-          gather_labels(rl, q[u], live, lab[u]);
-          const unsigned t = ld_lab(rt, (unsigned)(tid + u * TPB));
-          lab[u].t = live ? t : 255u;
-        }
-      }
-#pragma unroll 1
-      for (int c = 0; c < C; ++c) {
-        const float a = ca[n * C + c], b = cb[n * C + c];
-        float v[WD_ILP][8], tv[WD_ILP];
-        if constexpr (LAB) {
-#pragma unroll
-          for (int u = 0; u < WD_ILP; ++u) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[u][k] = lab[u].c[k] == (unsigned)c ? 1.f : 0.f;
-            tv[u] = lab[u].t == (unsigned)c ? 1.f : 0.f;
-          }
-        } else {
-          const __amdgpu_buffer_rsrc_t rx = make_rsrc(x + ((long long)n * C + c) * plane, plane_bytes);
-          const __amdgpu_buffer_rsrc_t rf = make_rsrc(fixed + ((long long)n * C + c) * ovox + vb + j0 * TPB, fbytes);
-#pragma unroll
-          for (int u = 0; u < WD_ILP; ++u) {
-            gather8_b(rx, q[u], v[u]);
-            tv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, 4 * (tid + u * TPB), 0, 0));
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < WD_ILP; ++u) {
-          Tap t;
-          t.fx = q[u].fx; t.fy = q[u].fy; t.fz = q[u].fz;
-          const float o = blend8(v[u], t);
-          const float go = fmaf(a, tv[u], b * o);          // 0 past the chunk: tv and every corner read 0
-          float dx, dy, dz;
-          blend_grads(v[u], t, dx, dy, dz);
-          gx[u] = fmaf(dx, go, gx[u]); gy[u] = fmaf(dy, go, gy[u]); gz[u] = fmaf(dz, go, gz[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < WD_ILP; ++u) {              // each lane owns its rows of sg: coordinates in, gradient out
-        const int l = tid + (j0 + u) * TPB;
-        float mx, my, mz;                              // d(ix)/d(gx) incl. the clamp mask, from the coordinates still in sg
-        unnorm_clip(sg[l * 3], W, mx); unnorm_clip(sg[l * 3 + 1], H, my); unnorm_clip(sg[l * 3 + 2], D, mz);
-        if (any_nan(sg[l * 3], sg[l * 3 + 1], sg[l * 3 + 2])) mx = my = mz = 0.f;
-        sg[l * 3] = gx[u] * mx; sg[l * 3 + 1] = gy[u] * my; sg[l * 3 + 2] = gz[u] * mz;
-      }
-    }
-    __syncthreads();
-    unstage_rows(dgrid + ((long long)n * ovox + vb) * 3, cnt, sg, tid);
-  }
-}
-
-// x (N, C, V) floats -> lab (N, V) bytes when every voxel is exactly one-hot (one channel == 1.0f, all others == 0.0f);
-// any other voxel clears *ok (preset to 1 by the launcher; same-value stores from many threads)
-__global__ __launch_bounds__(TPB) void onehot_to_labels_kernel(const float* __restrict__ x, int C, long long V,
-                                                               unsigned char* __restrict__ lab, int* __restrict__ ok) {
-  const int n = blockIdx.y;
-  const float* xn = x + (long long)n * C * V;
-  unsigned char* ln = lab + (long long)n * V;
-  // 16-byte loads need every channel plane (and the byte map) aligned: V % 4 == 0 and aligned bases; else the scalar loop
-  const bool vec = (V & 3) == 0 && ((reinterpret_cast<unsigned long long>(x) & 15) == 0) &&
-                   ((reinterpret_cast<unsigned long long>(lab) & 3) == 0);
-  const long long V4 = vec ? (V >> 2) : 0;
-  bool good = true;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < V4; i += (long long)gridDim.x * TPB) {
-    int ones[4] = {0, 0, 0, 0}, which[4] = {0, 0, 0, 0};
-    bool clean = true;
-    for (int c = 0; c < C; ++c) {
-      const float4 v = *reinterpret_cast<const float4*>(xn + (long long)c * V + 4 * i);
-      const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (vv[j] == 1.f) { ++ones[j]; which[j] = c; }
-        else if (vv[j] != 0.f) clean = false;            // (NaN lands here too)
-      }
-    }
-    good = good && clean && ones[0] == 1 && ones[1] == 1 && ones[2] == 1 && ones[3] == 1;
-    *reinterpret_cast<unsigned*>(ln + 4 * i) = (unsigned)which[0] | ((unsigned)which[1] << 8) | ((unsigned)which[2] << 16) |
-                                               ((unsigned)which[3] << 24);
-  }
-  if (!vec) {                                            // unaligned shapes: one voxel per thread
-    for (long long v = (long long)blockIdx.x * TPB + threadIdx.x; v < V; v += (long long)gridDim.x * TPB) {
-      int ones = 0, which = 0;
-      for (int c = 0; c < C; ++c) {
-        const float t = xn[(long long)c * V + v];
-        if (t == 1.f) { ++ones; which = c; } else if (t != 0.f) good = false;
-      }
-      good = good && ones == 1;
-      ln[v] = (unsigned char)which;
-    }
-  }
-  if (!good) *ok = 0;
 }
 
 // scatter-add backward wrt the sampled volume (not on the training hot path: the volumes are data;
@@ -1160,185 +626,11 @@ __global__ __launch_bounds__(TPB) void sample_bwd_input_kernel(
   }
 }
 
-// ----------------------------------------------------------------------------------------------
-// reductions
-constexpr int RED_BLOCKS = 2048;
-
-__global__ __launch_bounds__(TPB) void sqdiff_partial_kernel(const float* __restrict__ a,
-                                                             const float* __restrict__ b, long long n,
-                                                             double* __restrict__ partial) {
-  float acc = 0.f;
-  double dacc = 0.0;
-  const long long n4 = n >> 2;
-  const float4* a4 = reinterpret_cast<const float4*>(a);
-  const float4* b4 = reinterpret_cast<const float4*>(b);
-  int cnt = 0;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n4; i += (long long)gridDim.x * TPB) {
-    float4 p = a4[i], q = b4[i];
-    float d0 = p.x - q.x, d1 = p.y - q.y, d2 = p.z - q.z, d3 = p.w - q.w;
-    acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-    if (++cnt == 64) { dacc += acc; acc = 0.f; cnt = 0; }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    float d = a[n4 * 4 + threadIdx.x] - b[n4 * 4 + threadIdx.x];
-    acc += d * d;
-  }
-  dacc += acc;
-  __shared__ double red[TPB / kWave];
-  double s = block_sum<double>(dacc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(TPB) void finalize_mean_kernel(const double* __restrict__ partial, int np,
-                                                            double inv_n, float* __restrict__ out) {
-  // fixed summation order (deterministic); 8 independent loads in flight per lane
-  double s8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int i = threadIdx.x;
-  for (; i + 7 * TPB < np; i += 8 * TPB) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s8[k] += partial[i + k * TPB];
-  }
-  for (int k = 0; i < np; i += TPB, ++k) s8[k & 7] += partial[i];
-  double s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-  __shared__ double red[TPB / kWave];
-  s = block_sum<double>(s, red);
-  if (threadIdx.x == 0) out[0] = (float)(s * inv_n);
-}
-
-__global__ __launch_bounds__(TPB) void mse_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      const float* __restrict__ gscale, long long n,
-                                                      float* __restrict__ da) {
-  const float s = gscale[0] * 2.f / (float)n;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB)
-    da[i] = s * (a[i] - b[i]);
-}
-
-// Dice: per row r: {sum t*p, sum p*p, sum t*t}.  grid (bx, R); partial (R, bx, 3) doubles.
-__global__ __launch_bounds__(TPB) void dice_partial_kernel(const float* __restrict__ pred,
-                                                           const float* __restrict__ target, long long V,
-                                                           double* __restrict__ partial) {
-  const int r = blockIdx.y;
-  const float* p = pred + (long long)r * V;
-  const float* t = target + (long long)r * V;
-  double s0 = 0, s1 = 0, s2 = 0;
-  float a0 = 0, a1 = 0, a2 = 0;
-  int cnt = 0;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < V; i += (long long)gridDim.x * TPB) {
-    float pv = p[i], tv = t[i];
-    a0 += tv * pv; a1 += pv * pv; a2 += tv * tv;
-    if (++cnt == 256) { s0 += a0; s1 += a1; s2 += a2; a0 = a1 = a2 = 0.f; cnt = 0; }
-  }
-  s0 += a0; s1 += a1; s2 += a2;
-  __shared__ double red[TPB / kWave];
-  s0 = block_sum<double>(s0, red);
-  s1 = block_sum<double>(s1, red);
-  s2 = block_sum<double>(s2, red);
-  if (threadIdx.x == 0) {
-    double* o = partial + ((long long)r * gridDim.x + blockIdx.x) * 3;
-    o[0] = s0; o[1] = s1; o[2] = s2;
-  }
-}
-
-__global__ __launch_bounds__(TPB) void dice_finalize_kernel(const double* __restrict__ partial, int nb,
-                                                            float* __restrict__ sums) {
-  const int r = blockIdx.x;
-  double s0 = 0, s1 = 0, s2 = 0;
-  for (int i = threadIdx.x; i < nb; i += TPB) {
-    const double* o = partial + ((long long)r * nb + i) * 3;
-    s0 += o[0]; s1 += o[1]; s2 += o[2];
-  }
-  __shared__ double red[TPB / kWave];
-  s0 = block_sum<double>(s0, red);
-  s1 = block_sum<double>(s1, red);
-  s2 = block_sum<double>(s2, red);
-  if (threadIdx.x == 0) { sums[r * 3] = (float)s0; sums[r * 3 + 1] = (float)s1; sums[r * 3 + 2] = (float)s2; }
-}
-
-__global__ __launch_bounds__(TPB) void rows_axpby_kernel(const float* __restrict__ t, const float* __restrict__ p,
-                                                         const float* __restrict__ ca, const float* __restrict__ cb,
-                                                         long long V, float* __restrict__ out) {
-  const int r = blockIdx.y;
-  const float a = ca[r], b = cb[r];
-  const long long base = (long long)r * V;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < V; i += (long long)gridDim.x * TPB)
-    out[base + i] = a * t[base + i] + b * p[base + i];
-}
-
-__global__ __launch_bounds__(TPB) void argmax_onehot_kernel(const float* __restrict__ pred, int C, long long V,
-                                                            float* __restrict__ out) {
-  const int n = blockIdx.y;
-  const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-  if (i >= V) return;
-  const float* p = pred + (long long)n * C * V + i;
-  float best = p[0];
-  int bi = 0;
-  for (int c = 1; c < C; ++c) {
-    float v = p[(long long)c * V];
-    if (v > best) { best = v; bi = c; }
-  }
-  float* o = out + (long long)n * C * V + i;
-  for (int c = 0; c < C; ++c) o[(long long)c * V] = (c == bi) ? 1.f : 0.f;
-}
+// a block of the plain kernels takes TPB * VPT voxels, a block of the lane-contiguous ones TPB * PASSES
+static_assert(VPT == PASSES, "the plain and the lane-contiguous kernels share one launch grid");
+static inline dim3 sample_grid(long long ovox, int N) { return dim3(ceil_div(ovox, (long long)CHUNK), N); }
 
 }  // namespace
-
-// ----------------------------------------------------------------------------------------------
-// ----------------------------------------------------------------------------------------------
-// Jacobian determinant of a dense map (keymorph/loss_ops.py:161-247, eval metrics jdstd / jdlessthan0):
-// J[a][c] = d disp_c / d axis_a by central differences (0.5 (f[i+1] - f[i-1]), zero outside the volume) + I, on
-// the volume cropped by 2 voxels per side.  One pass: optional per-voxel determinant + {sum, sum^2, #(<= 0)}.
-__global__ __launch_bounds__(TPB) void jacdet_kernel(const float* __restrict__ disp, long long cstride,
-                                                     long long vstride, int D, int H, int W, float* __restrict__ jd,
-                                                     double* __restrict__ partial /* (nblocks, 3) */) {
-  const int Di = D - 4, Hi = H - 4, Wi = W - 4;
-  const long long total = (long long)Di * Hi * Wi;
-  double s = 0, ss = 0, neg = 0;
-  for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += (long long)gridDim.x * TPB) {
-    const int x = (int)(e % Wi) + 2, y = (int)((e / Wi) % Hi) + 2, z = (int)(e / ((long long)Wi * Hi)) + 2;
-    float J[3][3];   // [axis a][component c]
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* p = disp + c * cstride;
-      auto at = [&](int zz, int yy, int xx) { return p[(((long long)zz * H + yy) * W + xx) * vstride]; };
-      J[0][c] = 0.5f * at(z + 1, y, x) - 0.5f * at(z - 1, y, x);
-      J[1][c] = 0.5f * at(z, y + 1, x) - 0.5f * at(z, y - 1, x);
-      J[2][c] = 0.5f * at(z, y, x + 1) - 0.5f * at(z, y, x - 1);
-    }
-    J[0][0] += 1.f; J[1][1] += 1.f; J[2][2] += 1.f;
-    // same expansion (and association) as the reference
-    const float det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) -
-                      J[1][0] * (J[0][1] * J[2][2] - J[0][2] * J[2][1]) +
-                      J[2][0] * (J[0][1] * J[1][2] - J[0][2] * J[1][1]);
-    if (jd) jd[e] = det;
-    s += det; ss += (double)det * det; neg += det <= 0.f ? 1.0 : 0.0;
-  }
-  __shared__ double red[TPB / kWave];
-  s = block_sum<double>(s, red);
-  ss = block_sum<double>(ss, red);
-  neg = block_sum<double>(neg, red);
-  if (threadIdx.x == 0) { partial[blockIdx.x * 3] = s; partial[blockIdx.x * 3 + 1] = ss; partial[blockIdx.x * 3 + 2] = neg; }
-}
-
-__global__ __launch_bounds__(TPB) void jacdet_final_kernel(const double* __restrict__ partial, int nb, double count,
-                                                           double* __restrict__ out /* mean, std (ddof 0), #<=0, count */) {
-  double s = 0, ss = 0, neg = 0;
-  for (int i = threadIdx.x; i < nb; i += TPB) { s += partial[i * 3]; ss += partial[i * 3 + 1]; neg += partial[i * 3 + 2]; }
-  __shared__ double red[TPB / kWave];
-  s = block_sum<double>(s, red);
-  ss = block_sum<double>(ss, red);
-  neg = block_sum<double>(neg, red);
-  if (threadIdx.x == 0) {
-    const double mean = s / count;
-    double var = ss / count - mean * mean;
-    if (var < 0) var = 0;
-    out[0] = mean; out[1] = sqrt(var); out[2] = neg; out[3] = count;
-  }
-}
-
-static bool lane_contiguous_ok(int D, int H, int W) {
-  static const bool force_old = getenv("KMH_SAMPLER_OLD") != nullptr;   // A/B switch for tools/bench_sampler.py
-  return !force_old && W >= 2 && (long long)D * H * W < (1ll << 31);
-}
 
 KMH_API int kmh_abi_version(void) { return 1; }
 
@@ -1348,21 +640,18 @@ KMH_API int kmh_grid_sample3d_fwd(const float* x, const float* grid, float* out,
                                   int W, int Do, int Ho, int Wo, int mode, void* stream) {
   if (N <= 0 || C <= 0) return -22;
   const long long ovox = (long long)Do * Ho * Wo;
-  dim3 g(ceil_div(ovox, (long long)TPB * VPT), N);
+  const dim3 g = sample_grid(ovox, N);
   hipStream_t s = (hipStream_t)stream;
   // C >= 2, bilinear: the persistent tiled multi-channel kernel (KMH_SAMPLER_MC=0: the lc kernel; KMH_SAMPLER_MC_MINC=1: also C = 1)
-  static const int mc = getenv("KMH_SAMPLER_MC") ? atoi(getenv("KMH_SAMPLER_MC")) : 4;
-  static const int minc = getenv("KMH_SAMPLER_MC_MINC") ? atoi(getenv("KMH_SAMPLER_MC_MINC")) : 2;
+  static const int mc = env_int("KMH_SAMPLER_MC", 4);
+  static const int minc = env_int("KMH_SAMPLER_MC_MINC", 2);
   if (mode == 0 && C >= minc && mc && lane_contiguous_ok(D, H, W) && (long long)D * H * W < (1ll << 30) && ovox < (1ll << 30)) {
     const int ntx = (Wo + MT_X - 1) / MT_X, nty = (Ho + MT_Y - 1) / MT_Y, ntz = (Do + MT_Z - 1) / MT_Z;
     const long long nt = (long long)ntx * nty * ntz;
     if (nt < (1ll << 30)) {
-      static const int capa = getenv("KMH_MC_BLOCKS") ? atoi(getenv("KMH_MC_BLOCKS")) : 2048;   // ~ resident blocks of the chip
-      long long nb = (capa / N) & ~7;                  // a multiple of 8 per sample row: blockIdx.x % 8 is the XCD
-      if (nb < 8) nb = 8;
-      if (nb > nt) nb = nt;
-      const dim3 gm((unsigned)nb, N);
-      static const int use_box = getenv("KMH_SAMPLER_BOX") ? atoi(getenv("KMH_SAMPLER_BOX")) : 1;
+      static const int capa = env_int("KMH_MC_BLOCKS", 2048);   // ~ resident blocks of the chip
+      const dim3 gm((unsigned)persistent_blocks(capa, N, nt), N);
+      static const int use_box = env_int("KMH_SAMPLER_BOX", 1);
       if (mc == 2) sample_fwd_mc_kernel<2><<<gm, TPB, 0, s>>>(x, grid, out, C, D, H, W, Do, Ho, Wo, ntx, nty, (int)nt, use_box);
       else sample_fwd_mc_kernel<4><<<gm, TPB, 0, s>>>(x, grid, out, C, D, H, W, Do, Ho, Wo, ntx, nty, (int)nt, use_box);
       return KMH_LAUNCH_CHECK();
@@ -1385,7 +674,7 @@ KMH_API int kmh_warp_mse_fwd(const float* x, const float* grid, const float* fix
                              float* out_loss, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
                              void* ws, void* stream) {
   const long long ovox = (long long)Do * Ho * Wo;
-  dim3 g(ceil_div(ovox, (long long)TPB * VPT), N);
+  const dim3 g = sample_grid(ovox, N);
   if ((long long)g.x * g.y > 65536 * 3) return -22;
   hipStream_t s = (hipStream_t)stream;
   if (lane_contiguous_ok(D, H, W)) {
@@ -1393,9 +682,7 @@ KMH_API int kmh_warp_mse_fwd(const float* x, const float* grid, const float* fix
   } else {
     sample_fwd_kernel<0, true><<<g, TPB, 0, s>>>(x, grid, out, fixed, (double*)ws, C, D, H, W, ovox);
   }
-  finalize_mean_kernel<<<1, TPB, 0, s>>>((const double*)ws, (int)(g.x * g.y),
-                                         1.0 / ((double)N * C * (double)ovox), out_loss);
-  return KMH_LAUNCH_CHECK();
+  return kmh_launch_finalize_mean((const double*)ws, (int)(g.x * g.y), 1.0 / ((double)N * C * (double)ovox), out_loss, s);
 }
 
 namespace {
@@ -1420,14 +707,13 @@ KMH_API int kmh_warp_mse_fwd_grad(const float* x, const float* grid, const float
                                   float* dgrid, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, void* ws,
                                   void* stream) {
   const long long ovox = (long long)Do * Ho * Wo;
-  dim3 g(ceil_div(ovox, (long long)TPB * VPT), N);
+  const dim3 g = sample_grid(ovox, N);
   if ((long long)g.x * g.y > 65536 * 3 || !lane_contiguous_ok(D, H, W)) return -22;
   hipStream_t s = (hipStream_t)stream;
   const double cnt = (double)N * C * (double)ovox;
   sample_fwd_lc_kernel<0, true, true><<<g, TPB, 0, s>>>(x, grid, out, fixed, (double*)ws, C, D, H, W, ovox, dgrid,
                                                         (float)(2.0 / cnt));
-  finalize_mean_kernel<<<1, TPB, 0, s>>>((const double*)ws, (int)(g.x * g.y), 1.0 / cnt, out_loss);
-  return KMH_LAUNCH_CHECK();
+  return kmh_launch_finalize_mean((const double*)ws, (int)(g.x * g.y), 1.0 / cnt, out_loss, s);
 }
 
 /* a (n floats, n % 4 == 0, 16-byte aligned) *= g[0], skipped on the device when g[0] == 1 */
@@ -1443,7 +729,7 @@ KMH_API int kmh_grid_sample3d_bwd_grid(const float* x, const float* grid, const 
                                        int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
                                        void* stream) {
   const long long ovox = (long long)Do * Ho * Wo;
-  dim3 g(ceil_div(ovox, (long long)TPB * VPT), N);
+  const dim3 g = sample_grid(ovox, N);
   if (lane_contiguous_ok(D, H, W))
     sample_bwd_grid_lc_kernel<<<g, TPB, 0, (hipStream_t)stream>>>(x, grid, gout, dgrid, C, D, H, W, ovox);
   else
@@ -1456,160 +742,5 @@ KMH_API int kmh_grid_sample3d_bwd_input(const float* grid, const float* gout, fl
   const long long ovox = (long long)Do * Ho * Wo;
   dim3 g(ceil_div(ovox, TPB), N);
   sample_bwd_input_kernel<<<g, TPB, 0, (hipStream_t)stream>>>(grid, gout, dx, C, D, H, W, ovox);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API int kmh_mse_fwd(const float* a, const float* b, long long n, float* out, void* ws, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  int nb = (int)((n / 4 + TPB - 1) / TPB);
-  if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-  if (nb < 1) nb = 1;
-  sqdiff_partial_kernel<<<nb, TPB, 0, s>>>(a, b, n, (double*)ws);
-  finalize_mean_kernel<<<1, TPB, 0, s>>>((const double*)ws, nb, 1.0 / (double)n, out);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API int kmh_mse_bwd(const float* a, const float* b, const float* gscale, long long n, float* da,
-                        void* stream) {
-  int nb = (int)((n + TPB - 1) / TPB);
-  if (nb > 4096) nb = 4096;
-  mse_bwd_kernel<<<nb, TPB, 0, (hipStream_t)stream>>>(a, b, gscale, n, da);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API int kmh_dice_sums(const float* pred, const float* target, int R, long long V, float* sums, void* ws,
-                          void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  int nb = (int)((V + TPB * 8 - 1) / (TPB * 8));
-  int cap = 65536 / (R > 0 ? R : 1);
-  if (cap < 1) return -22;
-  if (nb > cap) nb = cap;
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  dice_partial_kernel<<<dim3(nb, R), TPB, 0, s>>>(pred, target, V, (double*)ws);
-  dice_finalize_kernel<<<R, TPB, 0, s>>>((const double*)ws, nb, sums);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* Fused align_img + soft Dice sums: sums[(n*C + c)*3 + {0,1,2}] = {sum t p, sum p^2, sum t^2} over the output voxels, with
- * p = grid_sample(x, grid)[n, c] (bilinear, border, align_corners = False) and t = fixed[n, c]; the warped tensor is never
- * written.  Replaces keymorph/utils.py:14-21 followed by the three reductions of keymorph/loss_ops.py:28-52 (caller
- * scripts/train.py:146-164).  ws: kmh_reduce_ws_bytes().  Returns KMH_EINVAL (-22) when the lane-contiguous kernel does
- * not apply (W < 2, a plane of >= 2^31 voxels, C > 128): the caller then uses the separate entry points. */
-/* The ONE statement of when the fused warp + Dice kernels apply (both entry points return -22 otherwise, and
- * kmh_warp_dice_ok lets the host decide BEFORE it builds an autograd node: the unfused composition align_img + DiceLoss is
- * the documented fallback): the lane-contiguous sampler (W >= 2, not switched off by KMH_SAMPLER_OLD), < 2^30 voxels per
- * channel plane (32-bit byte offsets), <= 128 channels (the sums' LDS table), and N * C rows whose block partials --
- * (N, nb, C, 3) doubles with nb >= 1 -- fit the reduction workspace. */
-static bool warp_dice_supported(int N, int C, int D, int H, int W) {
-  return N > 0 && C > 0 && C <= WD_MAXC && lane_contiguous_ok(D, H, W) && (long long)D * H * W < (1ll << 30) &&
-         (long long)N * C <= 65536;
-}
-KMH_API int kmh_warp_dice_ok(int N, int C, int D, int H, int W) { return warp_dice_supported(N, C, D, H, W) ? 1 : 0; }
-
-KMH_API int kmh_warp_dice_sums(const float* x, const float* grid, const float* fixed, float* sums, int N, int C, int D,
-                               int H, int W, int Do, int Ho, int Wo, const unsigned char* lab_x,
-                               const unsigned char* lab_fixed, const int* gate, void* ws, void* stream) {
-  if (!warp_dice_supported(N, C, D, H, W)) return -22;
-  const bool labs = lab_x && lab_fixed && gate;
-  if (!labs && (lab_x || lab_fixed || gate)) return -22;            // all three or none
-  const long long ovox = (long long)Do * Ho * Wo;
-  const int nchunk = ceil_div(ovox, (long long)TPB * PASSES);
-  const long long nb_cap = 65536 / ((long long)N * C);   // partial (N, nb, C, 3) doubles inside the reduction workspace
-  long long nb = nb_cap;                                 // (>= 1: warp_dice_supported)
-  if (nb > nchunk) nb = nchunk;
-  static const int capa = getenv("KMH_WD_BLOCKS") ? atoi(getenv("KMH_WD_BLOCKS")) : 768;   // ~ resident blocks of the chip
-  const int per_n = (capa / N) & ~7;                 // a multiple of 8 per sample row: blockIdx.x % 8 is the XCD
-  if (nb > per_n) nb = per_n < 8 ? 8 : per_n;
-  if (nb > nb_cap) nb = nb_cap;                      // (per_n < 8 rounds UP to 8: never past the workspace)
-  if (nb < 1) nb = 1;
-  hipStream_t s = (hipStream_t)stream;
-  static const int ilp = getenv("KMH_WD_ILP_A") ? atoi(getenv("KMH_WD_ILP_A")) : 4;        // A/B switch (tools/bench_warp_dice.py)
-  const dim3 g((unsigned)nb, N);
-  // with label maps: BOTH variants are launched with the same grid; the device flag lets exactly one of them work
-  if (labs)
-    warp_dice_sums_kernel<4, true><<<g, TPB, 0, s>>>(x, grid, fixed, (double*)ws, C, D, H, W, ovox, nchunk, lab_x,
-                                                         lab_fixed, gate);
-  if (ilp == 4)
-    warp_dice_sums_kernel<4><<<g, TPB, 0, s>>>(x, grid, fixed, (double*)ws, C, D, H, W, ovox, nchunk, nullptr, nullptr,
-                                                  labs ? gate : nullptr);
-  else
-    warp_dice_sums_kernel<2><<<g, TPB, 0, s>>>(x, grid, fixed, (double*)ws, C, D, H, W, ovox, nchunk, nullptr, nullptr,
-                                                  labs ? gate : nullptr);
-  const int total = N * C * 3;
-  warp_dice_final_kernel<<<ceil_div(total, TPB / kWave), TPB, 0, s>>>((const double*)ws, (int)nb, C, total, sums);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* x (N, C, V) floats -> lab (N, V) bytes = the channel that holds the 1 when every voxel is exactly one-hot; ok[0] (device
- * int, this call only ever CLEARS it: preset it to 1, chain several tensors onto one flag) stays 1 iff that held
- * everywhere.  What keymorph/utils.py:200-240 (one_hot / one_hot_subsampled_pair) and nearest-sampled augmentation
- * (keymorph/augmentation.py:160-163) produce is exactly one-hot; a soft segmentation clears the flag and the Dice kernels
- * then read the float tensors.  C <= 255. */
-KMH_API int kmh_onehot_to_labels(const float* x, int N, int C, long long V, unsigned char* lab, int* ok, void* stream) {
-  if (N <= 0 || C <= 0 || C > 255 || V <= 0) return -22;
-  long long nb = (V / 4 + TPB - 1) / TPB;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  onehot_to_labels_kernel<<<dim3((unsigned)nb, N), TPB, 0, (hipStream_t)stream>>>(x, C, V, lab, ok);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* d/d(grid) of sum_{n,c} g[n,c] * DiceRow[n,c] given ca[n*C+c] = -2 g / den and cb[n*C+c] = 2 g num / den^2 (num = 2 I + 1,
- * den = P + T + 1 from kmh_warp_dice_sums): dgrid[n, v, :] = sum_c (ca t + cb p) * d p / d grid, p recomputed from x.
- * Autograd of keymorph/loss_ops.py:16-63 through keymorph/utils.py:14-21 in one pass. */
-KMH_API int kmh_warp_dice_bwd_grid(const float* x, const float* grid, const float* fixed, const float* ca, const float* cb,
-                                   float* dgrid, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                                   const unsigned char* lab_x, const unsigned char* lab_fixed, const int* gate, void* stream) {
-  if (!warp_dice_supported(N, C, D, H, W)) return -22;
-  const bool labs = lab_x && lab_fixed && gate;
-  if (!labs && (lab_x || lab_fixed || gate)) return -22;
-  const long long ovox = (long long)Do * Ho * Wo;
-  const int nchunk = ceil_div(ovox, (long long)TPB * PASSES);
-  static const int cap = getenv("KMH_WD_BLOCKS") ? atoi(getenv("KMH_WD_BLOCKS")) : 768;
-  static const int ilp = getenv("KMH_WD_ILP_B") ? atoi(getenv("KMH_WD_ILP_B")) : 4;      // 1.97 ms vs 2.58 (ILP 2) at 2 x 14 x 256^3
-  int per_n = (cap / N) & ~7;
-  if (per_n < 8) per_n = 8;
-  int nb = nchunk < per_n ? nchunk : per_n;
-  const dim3 g(nb, N);
-  hipStream_t s = (hipStream_t)stream;
-  if (labs)
-    warp_dice_grad_kernel<2, true><<<g, TPB, 0, s>>>(x, grid, fixed, ca, cb, dgrid, C, D, H, W, ovox, nchunk, lab_x,
-                                                         lab_fixed, gate);
-  if (ilp == 4)
-    warp_dice_grad_kernel<4><<<g, TPB, 0, s>>>(x, grid, fixed, ca, cb, dgrid, C, D, H, W, ovox, nchunk, nullptr, nullptr,
-                                                  labs ? gate : nullptr);
-  else
-    warp_dice_grad_kernel<2><<<g, TPB, 0, s>>>(x, grid, fixed, ca, cb, dgrid, C, D, H, W, ovox, nchunk, nullptr, nullptr,
-                                                  labs ? gate : nullptr);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API int kmh_rows_axpby(const float* t, const float* p, const float* ca, const float* cb, int R,
-                           long long V, float* out, void* stream) {
-  int nb = (int)((V + TPB * 4 - 1) / (TPB * 4));
-  if (nb > 2048) nb = 2048;
-  if (nb < 1) nb = 1;
-  rows_axpby_kernel<<<dim3(nb, R), TPB, 0, (hipStream_t)stream>>>(t, p, ca, cb, V, out);
-  return KMH_LAUNCH_CHECK();
-}
-
-KMH_API int kmh_argmax_onehot(const float* pred, int N, int C, long long V, float* out, void* stream) {
-  argmax_onehot_kernel<<<dim3(ceil_div(V, TPB), N), TPB, 0, (hipStream_t)stream>>>(pred, C, V, out);
-  return KMH_LAUNCH_CHECK();
-}
-
-/* disp: 3 components of a (D,H,W) map, component c at disp + c*cstride, voxel v at + v*vstride (NCDHW: cstride =
- * D*H*W, vstride = 1; a permuted (D,H,W,3) grid: cstride = 1, vstride = 3).  jd (D-4,H-4,W-4) or NULL;
- * stats[4] doubles = {mean, std (ddof 0), #(det <= 0), #voxels}.  keymorph/loss_ops.py:161-247 */
-KMH_API int kmh_jacobian_det(const float* disp, long long cstride, long long vstride, int D, int H, int W, float* jd,
-                             double* stats, void* ws, void* stream) {
-  if (D < 5 || H < 5 || W < 5) return -22;
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = (long long)(D - 4) * (H - 4) * (W - 4);
-  int nb = ceil_div(total, TPB);
-  if (nb > 4096) nb = 4096;
-  jacdet_kernel<<<nb, TPB, 0, s>>>(disp, cstride, vstride, D, H, W, jd, (double*)ws);
-  jacdet_final_kernel<<<1, TPB, 0, s>>>((const double*)ws, nb, (double)total, stats);
   return KMH_LAUNCH_CHECK();
 }

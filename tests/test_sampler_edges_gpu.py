@@ -1,4 +1,4 @@
-"""GPU: the sampler kernels (csrc/sampler.hip) against the fp64 reference of tests/sampler_ref.py at lattice points, clamp
+"""GPU: the sampler kernels (csrc/sampler.hip, warp_dice.hip, losses.hip) against the fp64 reference of tests/sampler_ref.py at lattice points, clamp
 borders, non-finite coordinates and the shape edges that pick each kernel arm.
 
 Bars (against fp64, whose coordinate is ATen's fp32 one): forward 1e-6 * max|x|; grid gradient per axis
@@ -222,7 +222,7 @@ def test_mse_loss_and_dice_rows_vs_fp64(shape):
 
 # ------------------------------------------------------------------------------------------------------------ NaN
 def test_nan_coordinates():
-    """a NaN coordinate follows ATen's CPU kernels (sampler.hip header): the forward clamps it to the far border of its axis,
+    """a NaN coordinate follows ATen's CPU kernels (sampler_taps.h header): the forward clamps it to the far border of its axis,
     the voxel passes no gradient to the grid or the volume; every other voxel is unaffected -- through the lane-contiguous
     (C = 1), tiled multi-channel (C = 2, 14), plain (W = 1) kernels and the fused losses"""
     from keymorph_amd import loss_ops
@@ -257,6 +257,7 @@ ARMS = {
     "mc2_minc1": {"KMH_SAMPLER_MC": "2", "KMH_SAMPLER_MC_MINC": "1"},
     "mc4_nobox_minc1": {"KMH_SAMPLER_BOX": "0", "KMH_SAMPLER_MC_MINC": "1"},
     "old": {"KMH_SAMPLER_OLD": "1"},
+    "walk": {"KMH_WD_BLOCKS": "8", "KMH_MC_BLOCKS": "8"},
 }
 ARM_CASES = ["identity_W100_C1", "identity_H97_C2", "shift_W97_C14", "xz_flip_W100_C2", "down2_N3_C1", "border_C2_ovox105",
              "beyond_C3_ovox15", "steep_affine_C2", "random_N3_C4_ovox45"]
@@ -283,37 +284,73 @@ def _dice_inputs():
     return out
 
 
-def child_main(path):
-    """one environment arm (set by the parent before this process started): every sampler entry point on the arm cases"""
+# The "walk" arm: 8 persistent blocks per sample row over 10 x 16 x 100 = 16 000 output voxels.  The Dice kernels see 16 chunks
+# of 1024 voxels, the last one ragged (640): every block walks two consecutive chunks, so the register prefetch of the next
+# chunk runs, and the block that owns chunks 14 and 15 steps from a prefetched full chunk to the element-wise tail.  The
+# multi-channel kernel sees 7 x 2 x 2 = 28 tiles of 16 x 8 x 8, three or four per block: tx = 0..5 fast (Wo % 4 == 0), tx = 6
+# an edge tile.  No default-sized case makes a block take more than one chunk or tile.
+WALK_SHAPE = (10, 16, 100)
+
+
+def _walk_inputs():
+    """(sampler cases, Dice cases) of the walk arm: C = 2 under a mild rotation about z (the tiles' source boxes fit the LDS
+    box), and the three Dice arms on a shifted identity"""
+    rng = np.random.default_rng(97)
+    N, shp = 2, WALK_SHAPE
+    theta = torch.zeros(N, 3, 4)
+    for n, a in enumerate((0.08, -0.05)):
+        theta[n] = torch.tensor([[np.cos(a), -np.sin(a), 0, 0.01], [np.sin(a), np.cos(a), 0, -0.02], [0, 0, 1, 0]])
+    rot = torch.nn.functional.affine_grid(theta, (N, 1) + shp, align_corners=False).numpy()
+    x = rng.random((N, 2) + shp, dtype=np.float32) + np.float32(0.25)
+    sampler = [("walk_rot_C2", x, rot, R.cotangent(x, rot, 13), None)]
+    grid = R.shift(R.identity(N, shp), shp, (1, 0, -1))
+    dice = [(f"walk_onehot{C}", _onehot(N, C, shp, rng), grid, _onehot(N, C, shp, rng)) for C in (3, 14)]
+    dice.append(("walk_soft4", rng.random((N, 4) + shp, dtype=np.float32), grid, rng.random((N, 4) + shp, dtype=np.float32)))
+    return sampler, dice
+
+
+def _inputs(arm):
+    return _walk_inputs() if arm == "walk" else (_arm_inputs(), _dice_inputs())
+
+
+def child_main(path, arm=None):
+    """one environment arm (set by the parent before this process started): every sampler entry point on the arm's cases
+    (fixed is None: no warp + MSE)"""
     res = {}
-    for n, x, g, gout, fixed in _arm_inputs():
+    sampler, dice = _inputs(arm)
+    for n, x, g, gout, fixed in sampler:
         out, dgrid, dx, near = _run_sampler(x, g, gout)
         res.update({f"{n}/out": out, f"{n}/dgrid": dgrid, f"{n}/dx": dx, f"{n}/near": near})
+        if fixed is None:
+            continue
         loss, warped, (g1, g2) = _run_warp_mse(x, g, fixed)
         res.update({f"{n}/mse": np.float64(loss), f"{n}/warped": warped, f"{n}/mse_g1": g1, f"{n}/mse_g2": g2})
-    for n, x, g, f in _dice_inputs():
+    for n, x, g, f in dice:
         loss, dgrid = _run_warp_dice(x, g, f)
         res.update({f"{n}/dice": np.float64(loss), f"{n}/dice_g": dgrid})
     np.savez(path, **res)
 
 
 def test_environment_arms(tmp_path):
-    """KMH_SAMPLER_MC=0|2, KMH_SAMPLER_BOX=0, KMH_SAMPLER_MC_MINC=1, KMH_SAMPLER_OLD=1, KMH_WD_ILP_A/B=2 and
-    KEYMORPH_DICE_NO_LABELS=1, each arm in a fresh child process, one after another, stopping at the first that fails"""
+    """KMH_SAMPLER_MC=0|2, KMH_SAMPLER_BOX=0, KMH_SAMPLER_MC_MINC=1, KMH_SAMPLER_OLD=1, KMH_WD_ILP_A/B=2,
+    KEYMORPH_DICE_NO_LABELS=1 and KMH_WD_BLOCKS=KMH_MC_BLOCKS=8 (on the walk inputs), each arm in a fresh child process, one
+    after another, stopping at the first that fails"""
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from tests import test_sampler_edges_gpu as m\n"
-            "m.child_main(sys.argv[1])\n" % ROOT)
+            "m.child_main(sys.argv[1], sys.argv[2])\n" % ROOT)
     keep = {k: v for k, v in os.environ.items() if not (k.startswith("KMH_") or k == "KEYMORPH_DICE_NO_LABELS")}
     for arm, env in ARMS.items():
         path = str(tmp_path / f"{arm}.npz")
-        r = subprocess.run([sys.executable, "-c", code, path], env=dict(keep, **env), capture_output=True, text=True,
+        r = subprocess.run([sys.executable, "-c", code, path, arm], env=dict(keep, **env), capture_output=True, text=True,
                            timeout=300)
         assert r.returncode == 0, f"arm {arm} exited with {r.returncode}:\n{r.stderr[-3000:]}"
         got = np.load(path)
-        for n, x, g, gout, fixed in _arm_inputs():
+        sampler, dice = _inputs(arm)
+        for n, x, g, gout, fixed in sampler:
             what = f"{arm}: {n}"
             _check_sampler(what, x, g, gout, got[f"{n}/out"], got[f"{n}/dgrid"], got[f"{n}/dx"], got[f"{n}/near"])
-            _check_warp_mse(what, x, g, fixed, float(got[f"{n}/mse"]), got[f"{n}/warped"],
-                            [got[f"{n}/mse_g1"], got[f"{n}/mse_g2"]])
-        for n, x, g, f in _dice_inputs():
+            if fixed is not None:
+                _check_warp_mse(what, x, g, fixed, float(got[f"{n}/mse"]), got[f"{n}/warped"],
+                                [got[f"{n}/mse_g1"], got[f"{n}/mse_g2"]])
+        for n, x, g, f in dice:
             _check_warp_dice(f"{arm}: {n}", x, g, f, float(got[f"{n}/dice"]), got[f"{n}/dice_g"])

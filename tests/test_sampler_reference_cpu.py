@@ -56,7 +56,7 @@ def test_fp32_rounding_of_the_product_matters():
 
 
 def test_nan_coordinate_follows_aten():
-    """the documented NaN rule (sampler.hip header): ATen's forward samples a NaN coordinate at the far border of its axis,
+    """the documented NaN rule (sampler_taps.h header): ATen's forward samples a NaN coordinate at the far border of its axis,
     and its backward gives such a voxel a zero grid gradient on all three axes and sends nothing to the input"""
     rng = np.random.default_rng(3)
     x = rng.random((1, 2, 3, 4, 5), dtype=np.float32)
