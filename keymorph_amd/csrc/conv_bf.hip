@@ -890,62 +890,28 @@ constexpr int S_OFF_BYTES = S_NLD * S_TPB * 4;                        // 16 384
 constexpr int S_COEF = 1024;                                          // channels of one sample's (scale, shift) table
 constexpr int S_LDS_BYTES = 2 * S_BUF_BYTES + S_OFF_BYTES + 2 * S_COEF * 4;      // 155 648
 static_assert(GPL <= S_PLANE && GTZ == 4 && GTY == S_MR, "wave = plane, 8 rows");
-#ifndef KMH_S_VPM
-#define KMH_S_VPM 3
-#endif
-#ifndef KMH_S_BD
-#define KMH_S_BD 2
-#endif
-#ifndef KMH_S_LEAD
-#define KMH_S_LEAD 6
-#endif
-#ifndef KMH_S_RF
-#define KMH_S_RF 1
-#endif
-#ifndef KMH_S_ADB
-#define KMH_S_ADB 1
-#endif
-#ifndef KMH_SP_BA
-#define KMH_SP_BA 9
-#endif
+// the step's issue plan, swept and settled:
+constexpr int S_ILR = 12, S_ILRN = 2;                                 // gaps that take LDS reads, reads per such gap
+constexpr int S_ILV0 = 3, S_ILV1 = 3, S_ILV2 = 2;                     // first gap that takes conversion VALU; VALU per gap on the 32-wide / 64-wide tile
+constexpr int SP_BA = 9, SP_PS = 5;                                   // SPLIT: request distance = drain period; the stage's 16 DMA pieces go out in
+                                                                      // steps 0 .. SP_PS - 1 (flat over the valid range: profiles/r5g_zp_split_ring_sweep.txt)
+// What is still a compile-time switch is built by something: KMH_S_CW=0 KMH_S_DEEP=0 is the library's fall-back when the ISA audit
+// fails (keymorph_amd/build.py), KMH_S_DEEP_RING_V=1 KMH_S_IL=0 the audit's positive control (tests/test_asm_audit_cpu.py),
+// KMH_S_STAMPALL an instrument.
 #ifndef KMH_S_DEEP
 #define KMH_S_DEEP 1
 #endif
-#ifndef KMH_S_POOLZ            // 1 = the pooling variant's waves own both planes of a pair (0: a plane each + LDS exchange, the A/B arm)
-#define KMH_S_POOLZ 1
-#endif
-#ifndef KMH_S_CW               // 1 = hand-counted waits in the kernels that convert their operand (0: full drains, the A/B arm)
+#ifndef KMH_S_CW               // 1 = hand-counted waits in the kernels that convert their operand (0: full drains)
 #define KMH_S_CW 1
 #endif
 #ifndef KMH_S_STAMPALL
 #define KMH_S_STAMPALL 0
 #endif
-#ifndef KMH_S_IL               // 1 = LDS reads / conversion VALU dealt over the MFMA gaps of the whole step (0: reads first, the A/B arm)
+#ifndef KMH_S_IL               // 1 = LDS reads / conversion VALU dealt over the MFMA gaps of the whole step (0: reads first)
 #define KMH_S_IL 1
 #endif
-#ifndef KMH_S_ILR              // gaps that take LDS reads, reads per such gap
-#define KMH_S_ILR 12
-#endif
-#ifndef KMH_S_ILRN
-#define KMH_S_ILRN 2
-#endif
-#ifndef KMH_S_ILV0             // first gap that takes conversion VALU; VALU per gap on the 32-wide / 64-wide tile
-#define KMH_S_ILV0 3
-#endif
-#ifndef KMH_S_ILV1
-#define KMH_S_ILV1 3
-#endif
-#ifndef KMH_S_ILV2
-#define KMH_S_ILV2 2
-#endif
-#ifndef KMH_S_UNCOND           // 1 = the step loop requests the "next stage's" fragments / voxels / pieces even when there is no next
-#define KMH_S_UNCOND 1         // stage (addresses stay valid: stage 0 of the current pair): no branch inside a step, one scheduling
-#endif                         // region per step (0 = the A/B arm)
 #ifndef KMH_S_DEEP_RING_V      // 1 = the DEEP ring in "=v" registers: the variant that CRASHED (kept as the positive control of
 #define KMH_S_DEEP_RING_V 0    // tests/test_asm_audit_cpu.py; never built into the library)
-#endif
-#ifndef KMH_SP_PSTEPS
-#define KMH_SP_PSTEPS 5
 #endif
 
 // ZP (Cout <= 16, z-paired weights, NT = 1): wave = (plane pair, row half) -- 4 rows, the N tile is (16 couts x 2 planes) over the
@@ -960,9 +926,9 @@ static_assert(GPL <= S_PLANE && GTZ == 4 && GTY == S_MR, "wave = plane, 8 rows")
 // conversion of the same length (cycle stamps, profiles/r5a): 1300-1800 cycles per conversion step against 384 of MFMA time.
 // Bit-identical to the fp32 input: the producer applies the same fmaf(x, S, 0) and split8<2>.
 // POOL (round 5; NT = 1, not z-paired: 16 < Cout <= 32): the pooling epilogue of conv3_fwd_g_kernel on this kernel's waves -- a
-// wave holds one PLANE of the brick (8 rows), so the x children of a window meet in one lane of the row tile's read-back, its
-// y children in consecutive rows of the same wave, and its z children in the wave next to it (odd planes publish their
-// (x, y)-pooled partials through LDS); ATen's first-max rule, the same winners, the same outputs bit for bit.  What it buys:
+// wave holds four rows of BOTH planes of a plane pair, so the x children of a window meet in one lane's accumulator registers,
+// its y children in consecutive rows and its z children in rows m / m + 4 of the same wave: nothing crosses waves; ATen's
+// first-max rule, the same winners, the same outputs bit for bit.  What it buys:
 // the plain one-wave kernel spends 38 % of a two-chunk 16 -> 32 brick in its epilogue storing 128 KB (cycle stamps, r5a); the
 // pooled tensor is 16 KB.
 template <int NT, bool ZP = false, bool SPLIT = false, bool POOL = false, bool AMP = false>
@@ -1010,13 +976,13 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   const float sA = ascale ? ascale[0] : 1.f;
   const float desc = (ascale ? ascale[1] : 1.f) * (wscale ? wscale[1] : 1.f);
   const int nchunk = Cin / KC;
-  // PZ (the pooling variant, round 5): a wave owns rows 4 (wv & 1) .. + 3 of BOTH planes of a plane pair (accumulator rows 0-3 /
+  // POOL (round 5): a wave owns rows 4 (wv & 1) .. + 3 of BOTH planes of a plane pair (accumulator rows 0-3 /
   // 4-7) instead of 8 rows of one plane, so the 2 x 2 x 2 pooling window -- x: a register pair, y: two rows, z: rows m / m + 4 --
   // lies inside ONE wave: no exchange through LDS, no idle odd-plane waves, every wave transposes and stores 16 values per lane
-  constexpr bool PZ = POOL && (KMH_S_POOLZ != 0);
-  const int wz = (ZP || PZ) ? 2 * (wv >> 1) : wv, wy = ZP ? (wv & 1) * MR : (PZ ? (wv & 1) * (MR / 2) : 0);      // first output plane / row of the wave
+  // (- 4.7 % against a plane per wave: profiles/r5z_pool_epilogue_in_wave_z_pooling.txt)
+  const int wz = (ZP || POOL) ? 2 * (wv >> 1) : wv, wy = ZP ? (wv & 1) * MR : (POOL ? (wv & 1) * (MR / 2) : 0);      // first output plane / row of the wave
   const int vrow = (wz * GHY + wy) * HX + li;
-  auto arow = [](int m) -> int { return PZ ? (m & 3) * HX + (m >> 2) * (GHY * HX) : m * HX; };      // A-image offset of accumulator row m
+  auto arow = [](int m) -> int { return POOL ? (m & 3) * HX + (m >> 2) * (GHY * HX) : m * HX; };      // A-image offset of accumulator row m
   const long long vox = (long long)D * H * W;
   const long long plane = SPLIT ? (vox + 1) * KC : vox * KC;      // floats per (sample, chunk) plane of a channel-blocked input
   const long long chunk_stride = (in_blocked || SPLIT) ? plane : KC;
@@ -1066,7 +1032,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   // by the drain at the head of step j + 1, converted there).  (LDS-DMA pieces -- no staging registers -- cost this single wave 100+ cycles of issue
   // each, 16 per chunk: steps with two pieces ran 1.8k cycles against the 1.54k of their 48 MFMAs.)
   typedef float kmh_f4 __attribute__((ext_vector_type(4)));      // (a native vector: the asm's "=v" operand)
-  // DEEP (round 5, the 32-wide tile without a pre-split operand; KMH_S_DEEP=0: the A/B arm): its 24 MFMAs per step (768 cycles)
+  // DEEP (round 5, the 32-wide tile without a pre-split operand; KMH_S_DEEP=0: the fall-back build): its 24 MFMAs per step (768 cycles)
   // do not cover an HBM round trip, and a `vmcnt(0)` at every step head made every raw load issued in step s a wait at step
   // s + 1 (conversion steps 1200 cycles against 910 without a conversion).  As for SPLIT, the B ring holds a whole stage (in
   // AGPRs) and fragments are requested 7 steps ahead; the raw voxels are requested THREE steps before their conversion instead
@@ -1084,7 +1050,6 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   // is waited for with a count (the fragments requested before an epilogue are drained / waited for with vmcnt(0)), so their
   // completion order does not matter: pending stores only make a counted wait stricter.
   constexpr bool CW = !SPLIT && (KMH_S_CW != 0);
-  static_assert(!CW || KMH_S_UNCOND, "counted waits need the same loads in every stage");
   constexpr int CD = DEEP ? 3 : (CW ? 2 : 1);              // steps between a voxel's request and its conversion
   constexpr int RQ = CD + 1;                               // raw ring slots
   kmh_f4 rawq[RQ][2];
@@ -1167,9 +1132,8 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   // s, so that the wave drains its memory queue only at the head of every BA-th step: the LDS-DMA pieces of the next stage's
   // halo, issued in the steps right after a drain, then have BA - SP_PS + 1 or more steps (thousands of cycles) to come in
   // from HBM before anything waits for them -- a drain at every step head would expose that latency 18 times per chunk.
-  constexpr int BD = (SPLIT || DEEP) ? NST : KMH_S_BD;   // ring slots
-  constexpr int BA = SPLIT ? KMH_SP_BA : (DEEP ? 7 : 1); // request distance = drain period (steps)
-  constexpr int SP_PS = KMH_SP_PSTEPS;                   // SPLIT: the stage's 16 DMA pieces go out in steps 0 .. SP_PS - 1
+  constexpr int BD = (SPLIT || DEEP) ? NST : 2;        // ring slots
+  constexpr int BA = SPLIT ? SP_BA : (DEEP ? 7 : 1);     // request distance = drain period (steps)
   static_assert(NST % BD == 0 && (SPLIT || DEEP || BD == 2), "the ring slot of a step must not depend on the stage");
   static_assert(!SPLIT || (NST % BA == 0 && SP_PS < BA && NT == 1), "drains at steps 0, BA, ...; pieces land before the next one");
   auto piece_beg = [](int s) -> int { return s >= SP_PS ? S_NLD : (S_NLD * s) / SP_PS; };      // pieces of steps 0 .. SP_PS - 1
@@ -1278,8 +1242,11 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
       stamp();                                             // barrier passed
       const bf16x8* sIn = reinterpret_cast<const bf16x8*>(gsm + pb * S_BUF_BYTES);      // [TERMS][S_PLANE]
       const bool last_ch = ch + 1 == nchunk;
-      const bool have_next = KMH_S_UNCOND || !last_ch || more;
-      const int nn = (last_ch && more) ? nxt.n : n, nch = last_ch ? 0 : ch + 1;      // (no next stage: any valid pair)
+      // The step loop requests the "next stage's" fragments / voxels / pieces even when there is no next stage (the addresses
+      // stay valid: stage 0 of the current pair): no branch inside a step, one scheduling region per step, and the same loads in
+      // every stage, which the counted waits need.  (With a branch around them the ISA audit flags the pooling instances of the
+      // full-drain build: profiles/ab_arms_retired_kernel_identity.md.)
+      const int nn = (last_ch && more) ? nxt.n : n, nch = last_ch ? 0 : ch + 1;
       unsigned cv_next = last_ch ? 0u : cv_in;             // (the next BRICK's table and bits: inside step 0, below)
       if (!SPLIT && nn != coef_n) {                        // uniform, rare: the work list moves on to another sample
         fill_coef(nn);
@@ -1289,7 +1256,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
       int vr = vrow;
       asm volatile("" : "+v"(vr));
       int dof0 = 0, dof1 = 0;                              // the next raw voxel's source offsets (read one step ahead)
-      bf16x8 a[KMH_S_ADB ? 2 : 1][MR][TERMS];              // this step's A fragments (and the next step's)
+      bf16x8 a[2][MR][TERMS];                              // this step's A fragments and the next step's
       {
         const int ab = vr + a_offset(0);
 #pragma unroll
@@ -1311,7 +1278,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
           if (s >= 1 + CD && s < 9 + CD) raw_tie((s - 1 - CD) % RQ);
         } else if (!(SPLIT || DEEP) || (s % BA == 0 && !(s == 0 && ch == 0))) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (s + BA < NST) b_issue((s + BA) % BD);             // the fragments of step s + BA ...
-        else if (have_next) {                                 // ... or of step s + BA - NST of the next stage
+        else {                                                // ... or of step s + BA - NST of the next stage
           if (s + BA == NST) o0 = (long long)nch * TERMS * term_stride + lh * CoutP + co0n + li;
           b_issue((s + BA - NST) % BD);
         }
@@ -1323,27 +1290,18 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
         if (s == 0 && last_ch && more) { cv_brick_next = fill_offsets(nxt); cv_next = cv_brick_next; }
         if constexpr (SPLIT) {
           // this step's share of the next stage's 16 pieces (step 0: after the offset table has been replaced)
-          if (have_next) {
 #pragma unroll
-            for (int p = piece_beg(s); p < piece_beg(s + 1); ++p) dma_piece(nn, nch, pb ^ 1, p, sOff[(p >> 1) * S_TPB + tid]);
-          }
+          for (int p = piece_beg(s); p < piece_beg(s + 1); ++p) dma_piece(nn, nch, pb ^ 1, p, sOff[(p >> 1) * S_TPB + tid]);
         } else {
-        if (!CW && s >= 1 && s < 9 && have_next) raw_issue(nn, nch, (s - 1) % RQ, dof0, dof1);
+        if (!CW && s >= 1 && s < 9) raw_issue(nn, nch, (s - 1) % RQ, dof0, dof1);
         if (s < 8) { dof0 = sOff[s * S_TPB + tid]; dof1 = sOff[(8 + s) * S_TPB + tid]; }
         }
-        if (KMH_S_ADB && s + 1 < NST) {
+        if (s + 1 < NST) {
           const int ab = vr + a_offset(s + 1);
 #pragma unroll
           for (int m = 0; m < MR; ++m)
 #pragma unroll
             for (int q = 0; q < TERMS; ++q) a[(s + 1) & 1][m][q] = sIn[q * S_PLANE + ab + arow(m)];
-        }
-        if (!KMH_S_ADB && s > 0) {                          // single set: read right here, the compiler places the reads
-          const int ab = vr + a_offset(s);
-#pragma unroll
-          for (int m = 0; m < MR; ++m)
-#pragma unroll
-            for (int q = 0; q < TERMS; ++q) a[0][m][q] = sIn[q * S_PLANE + ab + arow(m)];
         }
         // the next stage's voxel s - 2 (requested in the last step)
         if (!SPLIT && s >= 1 + CD && s < 9 + CD) convert1(nch, cv_next, pb ^ 1, s - 1 - CD, rawq[(s - 1 - CD) % RQ][0], rawq[(s - 1 - CD) % RQ][1]);
@@ -1354,30 +1312,31 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
           for (int m = 0; m < MR; ++m)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-              acc[m][t] = mfma16<TERMS>(a[KMH_S_ADB ? (s & 1) : 0][m][q3 == 0 ? 1 : 0], bq[s % BD][t][q3 == 1 ? 1 : 0], acc[m][t]);
+              acc[m][t] = mfma16<TERMS>(a[s & 1][m][q3 == 0 ? 1 : 0], bq[s % BD][t][q3 == 1 ? 1 : 0], acc[m][t]);
         constexpr int NMF = MR * NT * (AMP ? 1 : 3);          // MFMAs of a step
         if constexpr (KMH_S_IL != 0) {
-          // ONE scheduling region per step (no branch inside: KMH_S_UNCOND), its single-issue instructions dealt over the MFMA
-          // gaps: a wave alone on its SIMD hides about five of them beside a 32-cycle MFMA, and whatever sits in front of the
-          // step's first MFMA runs with the matrix pipe idle (the "reads first" arrangement put 30-60 instructions there).
+          // ONE scheduling region per step (no branch inside: the next stage's requests are unconditional), its single-issue
+          // instructions dealt over the MFMA gaps: a wave alone on its SIMD hides about five of them beside a 32-cycle MFMA, and
+          // whatever sits in front of the step's first MFMA runs with the matrix pipe idle (the "reads first" arrangement put
+          // 30-60 instructions there).
           const bool conv_step = !SPLIT && s >= 1 + CD && s < 9 + CD;
 #pragma unroll
           for (int k = 0; k < NMF; ++k) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   // one MFMA
-            if (k < KMH_S_ILR) __builtin_amdgcn_sched_group_barrier(0x100, KMH_S_ILRN, 0);      // LDS reads: early gaps
+            if (k < S_ILR) __builtin_amdgcn_sched_group_barrier(0x100, S_ILRN, 0);              // LDS reads: early gaps
             if (k == 1) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                       // the raw voxel's two loads
-            if (conv_step && k >= KMH_S_ILV0) __builtin_amdgcn_sched_group_barrier(0x002, NT == 2 ? KMH_S_ILV2 : KMH_S_ILV1, 0);
+            if (conv_step && k >= S_ILV0) __builtin_amdgcn_sched_group_barrier(0x002, NT == 2 ? S_ILV2 : S_ILV1, 0);
           }
-        } else {
-        if ((SPLIT || !(s >= 1 + CD && s < 9 + CD)) && KMH_S_RF) __builtin_amdgcn_sched_group_barrier(0x100, 64, 0);      // plain steps: reads first too
+        } else {      // the "reads first" arrangement the dealt one replaced: built only by the ISA audit's positive control
+        if (SPLIT || !(s >= 1 + CD && s < 9 + CD)) __builtin_amdgcn_sched_group_barrier(0x100, 64, 0);      // plain steps: reads first too
         if (!SPLIT && s >= 1 + CD && s < 9 + CD) {
           // every LDS read of the block first (the next step's A fragments, the coefficients, the next offsets), then a few bare
           // MFMAs while they land -- a wait in the middle of the MFMA stream stalls it --, then the conversion's VALU a few per gap
           __builtin_amdgcn_sched_group_barrier(0x100, 64, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, KMH_S_LEAD, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
 #pragma unroll
-          for (int k = 0; k < MR * NT * (AMP ? 1 : 3) - KMH_S_LEAD; ++k) {
-            __builtin_amdgcn_sched_group_barrier(0x002, KMH_S_VPM, 0);     // a few of the conversion's VALU ...
+          for (int k = 0; k < NMF - 6; ++k) {
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);             // a few of the conversion's VALU ...
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             // ... one MFMA
           }
         }
@@ -1419,8 +1378,8 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
       // (x, y) pooling IN REGISTERS: a lane's accumulator registers (2 q, 2 q + 1) of row m are the two x children of pooled
       // column X = (q & 1) + 4 (q >> 1) + 2 lh for ONE channel (column li of the tile), rows 2 p / 2 p + 1 of the same wave its
       // y children: no LDS round trip per row (the row-tile version: 16 stores, a wait, 4 loads, a wait, eight times over --
-      // this single wave per SIMD is latency-bound there).  Planes wz (even) and wz + 1 hold the z children: odd planes publish
-      // through LDS.  Scan order of the reference (z, y, x; a later value wins only if strictly greater, or NaN): lower-index
+      // this single wave per SIMD is latency-bound there).  Planes wz (even) and wz + 1, both this wave's, hold the z children.
+      // Scan order of the reference (z, y, x; a later value wins only if strictly greater, or NaN): lower-index
       // halves are combined first -- the same winners as kmh_maxpool3d_fwd.
       // (after a ReLU no value is NaN -- v_max_f32 returns its other operand -- and ATen's "a NaN wins" test, one unordered compare
       // and one mask OR per comparison, 274 of the epilogue's ~ 2000 instructions, is compiled out: two instances of the block)
@@ -1452,100 +1411,42 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
         }
       }
       stamp();
-      if constexpr (PZ) {
-        // z children = rows m / m + 4 of THIS wave: pooled rows p = 0, 1 of the lower plane meet p + 2 of the upper one.  Then
-        // the wave's pooled tile (2 rows x 16 columns x 32 channels) is transposed through its own 5 KB so that a lane stores 4
-        // channels of one pooled voxel (16 bytes; a wave instruction = 8 voxels = 1 KB of contiguous output).
-        float* tv = reinterpret_cast<float*>(sEp) + wv * (32 * 32 + 32 * 8);                                // [32 voxels][32]
-        unsigned char* tc = reinterpret_cast<unsigned char*>(tv + 32 * 32);                                 // [32 voxels][32] bytes
+      // z children = rows m / m + 4 of THIS wave: pooled rows p = 0, 1 of the lower plane meet p + 2 of the upper one.  Then
+      // the wave's pooled tile (2 rows x 16 columns x 32 channels) is transposed through its own 5 KB so that a lane stores 4
+      // channels of one pooled voxel (16 bytes; a wave instruction = 8 voxels = 1 KB of contiguous output).
+      float* tv = reinterpret_cast<float*>(sEp) + wv * (32 * 32 + 32 * 8);                                // [32 voxels][32]
+      unsigned char* tc = reinterpret_cast<unsigned char*>(tv + 32 * 32);                                 // [32 voxels][32] bytes
 #pragma unroll
-        for (int p = 0; p < MR / 4; ++p) {
+      for (int p = 0; p < MR / 4; ++p) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            float o;
-            unsigned c;
-            pick(pvv[p][q], pvv[p + MR / 4][q], (pcc[p] >> (4 * q)) & 15u, ((pcc[p + MR / 4] >> (4 * q)) & 15u) + 4u, o, c);
-            const int X = (q & 1) + 4 * (q >> 1) + 2 * lh;
-            tv[(p * 16 + X) * 32 + li] = o;
-            tc[(p * 16 + X) * 32 + li] = (unsigned char)c;
-          }
-        }
-        // (the wave's own LDS writes are ordered before its reads)
-        stamp();
-        const int Do = D >> 1, Ho = H >> 1, Wo = W >> 1;
-        const int oz = (z0 + wz) >> 1;
-        const int jx = lane >> 3;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int vi = jx + 8 * k, pr = vi >> 4, X = vi & 15;
-          const float4 o4 = *reinterpret_cast<const float4*>(tv + vi * 32 + col);
-          const unsigned cw = *reinterpret_cast<const unsigned*>(tc + vi * 32 + col);
-          const int oy = ((y0 + wy) >> 1) + pr, ox = (x0 >> 1) + X;
-          if (oz < Do && oy < Ho && ox < Wo && co_ok) {
-            const long long e = ((((long long)n * Do + oz) * Ho + oy) * Wo + ox) * Cout + co;
-            *reinterpret_cast<float4*>(y + e) = o4;
-            pool_arg[e >> 2] = cw;
-            st1[0] += o4.x; st2[0] += o4.x * o4.x; st1[1] += o4.y; st2[1] += o4.y * o4.y;
-            st1[2] += o4.z; st2[2] += o4.z * o4.z; st1[3] += o4.w; st2[3] += o4.w * o4.w;
-          }
-        }
-      } else {
-      // z children: waves 1, 3 (odd planes) publish, waves 0, 2 combine.  (Splitting the rest of the epilogue between the two
-      // waves of a pair -- each finishing two of the four window rows -- was measured: 4.08 against 3.95-4.08 ms, the selects
-      // that deal the halves cost what the idle partner would have saved.)
-      float* xv = reinterpret_cast<float*>(sEp);                              // [pair][36][64]: 32 values + 4 code words per lane
-      const bool odd_plane = (wv & 1) != 0;
-      float* xs = xv + (wv >> 1) * (36 * 64) + lane;
-      if (odd_plane) {
-#pragma unroll
-        for (int p = 0; p < MR / 2; ++p) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) xs[(p * 8 + q) * 64] = pvv[p][q];
-          xs[(32 + p) * 64] = __uint_as_float(pcc[p]);
+        for (int q = 0; q < 8; ++q) {
+          float o;
+          unsigned c;
+          pick(pvv[p][q], pvv[p + MR / 4][q], (pcc[p] >> (4 * q)) & 15u, ((pcc[p + MR / 4] >> (4 * q)) & 15u) + 4u, o, c);
+          const int X = (q & 1) + 4 * (q >> 1) + 2 * lh;
+          tv[(p * 16 + X) * 32 + li] = o;
+          tc[(p * 16 + X) * 32 + li] = (unsigned char)c;
         }
       }
-      __syncthreads();
+      // (the wave's own LDS writes are ordered before its reads)
       stamp();
-      if (!odd_plane) {
-        // ... and transpose the pooled tile (4 rows x 16 columns x 32 channels) through this wave's 10 KB so that a lane stores 4
-        // channels of one pooled voxel (16 bytes; a wave instruction = 8 voxels = 1 KB of contiguous output)
-        float* tv = reinterpret_cast<float*>(sEp + 2 * 36 * 64 * 4) + (wv >> 1) * (64 * 32 + 64 * 8);      // [64 voxels][32]
-        unsigned char* tc = reinterpret_cast<unsigned char*>(tv + 64 * 32);                                 // [64 voxels][32] bytes
+      const int Do = D >> 1, Ho = H >> 1, Wo = W >> 1;
+      const int oz = (z0 + wz) >> 1;
+      const int jx = lane >> 3;
 #pragma unroll
-        for (int p = 0; p < MR / 2; ++p) {
-          const unsigned B = __float_as_uint(xs[(32 + p) * 64]);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const float Q = xs[(p * 8 + q) * 64];
-            float o;
-            unsigned c;
-            pick(pvv[p][q], Q, (pcc[p] >> (4 * q)) & 15u, ((B >> (4 * q)) & 15u) + 4u, o, c);
-            const int X = (q & 1) + 4 * (q >> 1) + 2 * lh;
-            tv[(p * 16 + X) * 32 + li] = o;
-            tc[(p * 16 + X) * 32 + li] = (unsigned char)c;
-          }
-        }
-        // (the wave's own LDS writes are ordered before its reads)
-        stamp();
-        const int Do = D >> 1, Ho = H >> 1, Wo = W >> 1;
-        const int oz = (z0 + wz) >> 1;
-        const int jx = lane >> 3;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int vi = jx + 8 * k, pr = vi >> 4, X = vi & 15;
-          const float4 o4 = *reinterpret_cast<const float4*>(tv + vi * 32 + col);
-          const unsigned cw = *reinterpret_cast<const unsigned*>(tc + vi * 32 + col);
-          const int oy = (y0 >> 1) + pr, ox = (x0 >> 1) + X;
-          if (oz < Do && oy < Ho && ox < Wo && co_ok) {
-            const long long e = ((((long long)n * Do + oz) * Ho + oy) * Wo + ox) * Cout + co;
-            *reinterpret_cast<float4*>(y + e) = o4;
-            pool_arg[e >> 2] = cw;
-            st1[0] += o4.x; st2[0] += o4.x * o4.x; st1[1] += o4.y; st2[1] += o4.y * o4.y;
-            st1[2] += o4.z; st2[2] += o4.z * o4.z; st1[3] += o4.w; st2[3] += o4.w * o4.w;
-          }
+      for (int k = 0; k < 4; ++k) {
+        const int vi = jx + 8 * k, pr = vi >> 4, X = vi & 15;
+        const float4 o4 = *reinterpret_cast<const float4*>(tv + vi * 32 + col);
+        const unsigned cw = *reinterpret_cast<const unsigned*>(tc + vi * 32 + col);
+        const int oy = ((y0 + wy) >> 1) + pr, ox = (x0 >> 1) + X;
+        if (oz < Do && oy < Ho && ox < Wo && co_ok) {
+          const long long e = ((((long long)n * Do + oz) * Ho + oy) * Wo + ox) * Cout + co;
+          *reinterpret_cast<float4*>(y + e) = o4;
+          pool_arg[e >> 2] = cw;
+          st1[0] += o4.x; st2[0] += o4.x * o4.x; st1[1] += o4.y; st2[1] += o4.y * o4.y;
+          st1[2] += o4.z; st2[2] += o4.z * o4.z; st1[3] += o4.w; st2[3] += o4.w * o4.w;
         }
       }
-      }   // !PZ
       };
       if (relu_out) pool_block(std::false_type{});
       else pool_block(std::true_type{});
@@ -1623,7 +1524,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
     cv_in = cv_brick_next;
     pb ^= 1;
   }
-  // (KMH_S_UNCOND: the last stage requested a "next stage" that does not exist -- nothing may still be in flight to this wave's
+  // (the last stage requested a "next stage" that does not exist -- nothing may still be in flight to this wave's
   // registers or to the workgroup's LDS when they are handed to another workgroup)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }

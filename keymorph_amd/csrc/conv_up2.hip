@@ -582,15 +582,6 @@ __global__ __launch_bounds__(256) void up2_wgrad_reduce_kernel(const float* __re
 // 1.91 -> 1.40 ms.  With the box sums AND the MFMAs compiled out a launch still takes 2.08 / 1.03 ms: the kernel is bound by what
 // a CU can load (window 19.2 KB + A rows 16 KB per step: 9.2 GB per launch, mostly L2 hits, at ~ 10 B / cycle / CU); the box sums
 // add 0.5 ms, the MFMAs 0.25.  Fetching the window before or after the box sums: no difference.
-#ifndef WF_DMA                 // 1 = the dz window by LDS-DMA (0: through registers, the A/B arm)
-#define WF_DMA 1
-#endif
-#ifndef KMH_WF_MAP
-#define KMH_WF_MAP 1
-#endif
-#ifndef WF_EARLY_W
-#define WF_EARLY_W 1
-#endif
 constexpr int WF_HX = 10, WF_HY = 10, WF_HZ = 6, WF_VOX = WF_HX * WF_HY * WF_HZ;      // window of a 4 x 4 x 2 low tile
 constexpr int WF_NC = 224;                                                           // 216 columns, padded to 7 x 32
 // MODE (round 5, last): the kernel is bound by what a CU can load, so two of its workgroups become the two halves of ONE
@@ -651,12 +642,11 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
   // staging: the window (600 voxels x 2 quads = 1200 float4) by LDS-DMA, the A rows (16 voxel pairs x 32 quads) through registers
   constexpr int NIW = MODE == 2 ? 3 : 5;                                            // window elements per thread
   constexpr int NIA = MODE == 1 ? 1 : 2;                                            // A items per thread
-  float4 pw[WF_DMA ? 1 : NIW], pa[NIA][2];
+  float4 pa[NIA][2];
   int x0 = 0, y0 = 0, z0 = 0;                                                       // the tile the registers hold
   auto fetch_w = [&](int t) {                             // the window of tile t
     const int bx = t % tiles_x, by = (t / tiles_x) % tiles_y, bz = t / (tiles_x * tiles_y);
     const int wx = 8 * bx - 1, wy = 8 * by - 1, wz = 4 * bz - 1;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4* sWt = reinterpret_cast<float4*>(sW0 + iw_t * W_BYTES);
 #pragma unroll
     for (int i = 0; i < NIW; ++i) {
@@ -666,15 +656,12 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
       const bool in = e < 2 * WF_VOX && (unsigned)ux < (unsigned)W && (unsigned)uy < (unsigned)H && (unsigned)uz < (unsigned)D;
       const long long vox = in ? ((long long)uz * H + uy) * W + ux : 0;
       const float* src = dz_blocked ? dn + ((long long)oct_t * Vh + vox) * 8 + 4 * q : dn + vox * Cout + 8 * oct_t + 4 * q;
-      if constexpr (WF_DMA != 0) {
-        // straight into the window (element e = lane-linear: 16 bytes per lane behind a wave-uniform base), no staging
-        // registers; voxels outside the volume copy 16 bytes of zeros.  (Past element 1199 a lane must not write: what
-        // follows the window in LDS is another image.)
-        if (e < 2 * WF_VOX)
-          __builtin_amdgcn_global_load_lds((kmh_glb_ptr)(in ? src : zero16), (kmh_lds_ptr)(sWt + (e - lane)), 16, 0, 0);
-      } else {
-        pw[i] = in ? *reinterpret_cast<const float4*>(src) : z4;
-      }
+      // straight into the window (element e = lane-linear: 16 bytes per lane behind a wave-uniform base), no staging
+      // registers; voxels outside the volume copy 16 bytes of zeros.  (Past element 1199 a lane must not write: what
+      // follows the window in LDS is another image.)  Against the window through registers:
+      // profiles/r5w_up2_wgrad_fold_window_by_lds_dma.txt.
+      if (e < 2 * WF_VOX)
+        __builtin_amdgcn_global_load_lds((kmh_glb_ptr)(in ? src : zero16), (kmh_lds_ptr)(sWt + (e - lane)), 16, 0, 0);
     }
   };
   auto fetch_a = [&](int t) {                             // the A rows of tile t (which becomes the tile the registers hold)
@@ -697,15 +684,7 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
     sC[c] = (a_scale && ca < Cl) ? a_scale[(long long)n * Cl + ca] : 1.f;
     sC[128 + c] = (a_scale && ca < Cl) ? a_shift[(long long)n * Cl + ca] : 0.f;
   }
-  auto commit = [&]() {                                   // registers -> the window and the A image (tile x0, y0, z0)
-    if constexpr (WF_DMA == 0) {
-      float4* sWt = reinterpret_cast<float4*>(sW0 + iw_t * W_BYTES);
-#pragma unroll
-      for (int i = 0; i < NIW; ++i) {
-        const int e = (MODE == 2 ? tid + i * 512 : t8 + i * 256);
-        if (e < 2 * WF_VOX) sWt[e] = pw[i];
-      }
-    }
+  auto commit = [&]() {                                   // registers -> the A image (tile x0, y0, z0)
     unsigned char* sA = sA0 + ia_t * A_BYTES;
     const float* sC = sC0 + ia_t * 256;
 #pragma unroll
@@ -733,15 +712,11 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
     if (bt >= 192) return;
     const float4* sW = reinterpret_cast<const float4*>(sW0 + iw_t * W_BYTES);
     unsigned char* sB = sB0 + iw_t * B_BYTES;
-#if KMH_WF_MAP
     // a WAVE = one kz: (q, low voxel m) vary over its lanes.  With kz across the lanes (round 5) three lanes of every quad of
     // lanes wrote the same bank of the B image (72 columns x 80 bytes = 0 mod 128 bytes between the kz groups) and read window
     // planes 32 banks apart: 58 % of the kernel's LDS-active cycles were bank conflicts at 59 % LDS busy
     // (profiles/r6n_lds_by_kernel.txt).  Same sums per (m, kz, q), same order: bit-identical.
     const int q = bt & 1, kz = bt >> 6, m = (bt >> 1) & 31;
-#else
-    const int q = bt & 1, kz = (bt >> 1) % 3, m = bt / 6;
-#endif
     const int lmx = m & 3, lmy = (m >> 2) & 3, lmz = m >> 4;
     float4 Y[3][3];
 #pragma unroll
@@ -790,13 +765,12 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
   for (int t = t_beg; t < t_end; ++t) {
     __syncthreads();                           // the previous step's fragment reads are done
     commit();
-    if (WF_DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this lane's pieces of the window are in LDS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this lane's pieces of the window are in LDS
     __syncthreads();
-    if (!WF_DMA && WF_EARLY_W && t + 1 < t_end) fetch_w(t + 1);      // the next window: in flight during the box sums and the MFMAs
     boxes();
     __syncthreads();
-    if (t + 1 < t_end) {                       // the next A rows: during the MFMAs (after the box sums: their registers are free again)
-      if (WF_DMA || !WF_EARLY_W) fetch_w(t + 1);
+    if (t + 1 < t_end) {                       // the next window and A rows: during the MFMAs (after the box sums: the window is
+      fetch_w(t + 1);                          // read, their registers are free again)
       fetch_a(t + 1);
     }
 #pragma unroll

@@ -36,19 +36,11 @@ constexpr int RZ = 8;                                  // ring planes
 // 16-byte reads that the compiler never emitted) 32 lanes hit 8 banks -- 57 % of the LDS-active cycles were bank conflicts and the LDS
 // was 86 % busy (profiles/r6i_sq_counters_wgrad_ring.txt).  At 2 mod 32 the channels take 16 distinct banks and the producers'
 // 4-byte stores (channel quads 8 banks apart) stay conflict-free: -6 ... -11 % on every launch; 6, 10, 18 mod 32 the same, an ODD
-// pitch twice as slow (profiles/r6k_wgrad_ring_pitch_ab.txt).  KMH_WG_RPAD (A/B builds): bytes added to the 2304 of the rows.
-#ifndef KMH_WG_RPAD
-#define KMH_WG_RPAD 8
-#endif
-#ifndef KMH_WG_RROW
-#define KMH_WG_RROW 24          // elements (2 bytes) per halo row of the ring image (18 used; a lane reads 5 dwords from byte 0 or 16)
-#endif
-#ifndef KMH_WG_RZPAD
-#define KMH_WG_RZPAD 0          // bytes added to a ring plane
-#endif
-constexpr int XPITCH_R = KMH_WG_RROW;
-constexpr int ZSLOT = WHY * XPITCH_R * 2 + KMH_WG_RZPAD;   // bytes per ring plane inside a channel plane
-constexpr int XPLANE_R = RZ * ZSLOT + KMH_WG_RPAD;
+// pitch twice as slow (profiles/r6k_wgrad_ring_pitch_ab.txt).
+constexpr int WG_RPAD = 8;              // bytes added to the 2304 of the rows of a channel plane
+constexpr int XPITCH_R = 24;            // elements (2 bytes) per halo row of the ring image (18 used; a lane reads 5 dwords from byte 0 or 16)
+constexpr int ZSLOT = WHY * XPITCH_R * 2;                  // bytes per ring plane inside a channel plane
+constexpr int XPLANE_R = RZ * ZSLOT + WG_RPAD;
 static_assert(XPITCH_R * 2 >= 36 && (XPLANE_R & 3) == 0 && (ZSLOT & 3) == 0, "a row holds 18 elements; dword-aligned planes");
 constexpr int WGB_TPB = 512;
 constexpr int MTWB = 2;                    // M tiles per wave (14 tiles over 8 waves)

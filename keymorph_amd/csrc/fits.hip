@@ -479,14 +479,6 @@ __global__ __launch_bounds__(256) void tps_assemble_kernel(const float* __restri
   A[(size_t)b * a_stride + (size_t)i * lda + j] = v;
 }
 
-// (KMH_LU_EXP: timing experiments only, tools/build_exp_lib.sh -DKMH_LU_EXP=<bits>; results are garbage with any bit set.
-//  1 = no trailing update, 2 = no U12 strip, 4 = no pivot search, 8 = no rank-1 update inside the panel)
-#ifndef KMH_LU_EXP
-#define KMH_LU_EXP 0
-#endif
-#ifndef KMH_LU_KEYED
-#define KMH_LU_KEYED 1          // 0: round 3's four-barrier column step (A/B: tools/build_exp_lib.sh -DKMH_LU_KEYED=0)
-#endif
 // Blocked right-looking LU with partial pivoting, one workgroup per sample.
 // LDS: sP[m][NB+1] (panel, rows k0..n) then sU[NB][ncols] (U12 strip).
 template <int NB, bool MFMA64>
@@ -498,10 +490,7 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
   constexpr int PS = NB + 1;
   double* sP = smem;                       // [n][PS]
   double* sU = smem + (size_t)n * PS;      // [NB][n]
-  __shared__ double s_val[LU_TPB / kWave];
-  __shared__ int s_idx[LU_TPB / kWave];
-  __shared__ int s_piv[NB];
-  __shared__ unsigned long long s_key[NB];      // KMH_LU_KEYED: (magnitude, row) key of every panel column's pivot
+  __shared__ unsigned long long s_key[NB];      // (magnitude, row) key of every panel column's pivot
   // Row interchanges are NOT carried out in memory: rowmap[i] = the physical (= original) row that currently sits at
   // position i of the pivoted order.  Every access to a row of A goes through it, a pivot swaps two of its entries, and the
   // solve reads the same map (ipiv_all receives rowmap, not LAPACK's sequential interchanges).  Swapping the rows of the
@@ -525,108 +514,56 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
     }
     __syncthreads();
     // 2. unblocked LU of the panel
-    if constexpr (KMH_LU_KEYED) {
-      // Round 4: two barriers per column instead of four.  The pivot of column j+1 is found WHILE column j's rank-1 update
-      // writes it: every thread turns |its new entry| into a 64-bit key (magnitude bits with the low 11 replaced by
-      // 2047 - row, so that equal magnitudes resolve to the smallest row like LAPACK's idamax and a plain unsigned maximum is
-      // order independent), a wave reduces with shuffles and ONE LDS atomicMax per wave publishes it -- no second reduction
-      // stage on wave 0, no separate search phase re-reading the column.  (Magnitudes are compared to 42 mantissa bits: a
-      // pivot within 2^-42 of the largest is as good as the largest.)
-      auto row_key = [](double v, int r) -> unsigned long long {
-        const double a = fabs(v);
-        const unsigned long long b = (a == a) ? (unsigned long long)__double_as_longlong(a) : 0ull;     // NaN never wins
-        return (b & ~0x7FFull) | (unsigned long long)(0x7FF - r);
-      };
-      auto publish = [&](unsigned long long key, int col) {
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-          const unsigned long long ok = __shfl_xor(key, o, kWave);
-          key = ok > key ? ok : key;
-        }
-        if (lane == 0 && key) atomicMax(&s_key[col], key);
-      };
-      if (tid < NB) s_key[tid] = 0ull;
-      __syncthreads();
-      {
-        unsigned long long key = 0ull;
-        for (int r = tid; r < m; r += LU_TPB) { const unsigned long long k = row_key(sP[r * PS], r); key = k > key ? k : key; }
-        publish(key, 0);
-      }
-      for (int j = 0; j < nb; ++j) {
-        __syncthreads();               // column j's keys are in (and the previous column's update is visible)
-        const unsigned long long kj = s_key[j];
-        const int p = 0x7FF - (int)(kj & 0x7FFull);
-        if (tid == 0 && (kj >> 11) == 0ull) bad = 1;       // the whole column is zero (or NaN): singular
-        const bool have = (kj >> 11) != 0ull;
-        if (have && p != j && tid < nb) {
-          const double t = sP[j * PS + tid];
-          sP[j * PS + tid] = sP[p * PS + tid];
-          sP[p * PS + tid] = t;
-        }
-        if (have && p != j && tid == LU_TPB - 1) { const int t = rowmap[k0 + j]; rowmap[k0 + j] = rowmap[k0 + p]; rowmap[k0 + p] = t; }
-        __syncthreads();
-        const double pinv = 1.0 / sP[j * PS + j];
-        unsigned long long key = 0ull;
-        for (int r = j + 1 + tid; r < m; r += LU_TPB) {
-          const double l = sP[r * PS + j] * pinv;
-          sP[r * PS + j] = l;
-          for (int c = j + 1; c < nb; ++c) sP[r * PS + c] -= l * sP[j * PS + c];
-          if (j + 1 < nb) { const unsigned long long k = row_key(sP[r * PS + j + 1], r); key = k > key ? k : key; }
-        }
-        if (j + 1 < nb) publish(key, j + 1);
-      }
-      __syncthreads();
-    } else {
-    for (int j = 0; j < nb; ++j) {
-      // pivot search over rows j..m-1 of column j
-      double best = -1.0;
-      int bi = j;
-      if (KMH_LU_EXP & 4) { if (tid == 0) s_piv[j] = j; __syncthreads(); } else {
-      for (int r = j + tid; r < m; r += LU_TPB) {
-        const double v = fabs(sP[r * PS + j]);
-        if (v > best) { best = v; bi = r; }
-      }
+    // Round 4: two barriers per column instead of four.  The pivot of column j+1 is found WHILE column j's rank-1 update
+    // writes it: every thread turns |its new entry| into a 64-bit key (magnitude bits with the low 11 replaced by
+    // 2047 - row, so that equal magnitudes resolve to the smallest row like LAPACK's idamax and a plain unsigned maximum is
+    // order independent), a wave reduces with shuffles and ONE LDS atomicMax per wave publishes it -- no second reduction
+    // stage on wave 0, no separate search phase re-reading the column.  (Magnitudes are compared to 42 mantissa bits: a
+    // pivot within 2^-42 of the largest is as good as the largest.)
+    auto row_key = [](double v, int r) -> unsigned long long {
+      const double a = fabs(v);
+      const unsigned long long b = (a == a) ? (unsigned long long)__double_as_longlong(a) : 0ull;     // NaN never wins
+      return (b & ~0x7FFull) | (unsigned long long)(0x7FF - r);
+    };
+    auto publish = [&](unsigned long long key, int col) {
 #pragma unroll
       for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(best, o, kWave);
-        const int oi = __shfl_xor(bi, o, kWave);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        const unsigned long long ok = __shfl_xor(key, o, kWave);
+        key = ok > key ? ok : key;
       }
-      if (lane == 0) { s_val[wid] = best; s_idx[wid] = bi; }
-      __syncthreads();
-      if (wid == 0) {
-        best = lane < LU_TPB / kWave ? s_val[lane] : -1.0;
-        bi = lane < LU_TPB / kWave ? s_idx[lane] : 0x7fffffff;
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-          const double ov = __shfl_xor(best, o, kWave);
-          const int oi = __shfl_xor(bi, o, kWave);
-          if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        if (lane == 0) { s_piv[j] = bi; if (!(best > 0.0)) bad = 1; }
-      }
-      __syncthreads();
-      }
-      const int p = s_piv[j];
-      if (p != j && tid < nb) {
+      if (lane == 0 && key) atomicMax(&s_key[col], key);
+    };
+    if (tid < NB) s_key[tid] = 0ull;
+    __syncthreads();
+    {
+      unsigned long long key = 0ull;
+      for (int r = tid; r < m; r += LU_TPB) { const unsigned long long k = row_key(sP[r * PS], r); key = k > key ? k : key; }
+      publish(key, 0);
+    }
+    for (int j = 0; j < nb; ++j) {
+      __syncthreads();               // column j's keys are in (and the previous column's update is visible)
+      const unsigned long long kj = s_key[j];
+      const int p = 0x7FF - (int)(kj & 0x7FFull);
+      if (tid == 0 && (kj >> 11) == 0ull) bad = 1;       // the whole column is zero (or NaN): singular
+      const bool have = (kj >> 11) != 0ull;
+      if (have && p != j && tid < nb) {
         const double t = sP[j * PS + tid];
         sP[j * PS + tid] = sP[p * PS + tid];
         sP[p * PS + tid] = t;
       }
-      if (p != j && tid == LU_TPB - 1) { const int t = rowmap[k0 + j]; rowmap[k0 + j] = rowmap[k0 + p]; rowmap[k0 + p] = t; }
+      if (have && p != j && tid == LU_TPB - 1) { const int t = rowmap[k0 + j]; rowmap[k0 + j] = rowmap[k0 + p]; rowmap[k0 + p] = t; }
       __syncthreads();
-      // scale + rank-1 update of the remaining panel columns: one thread per row (rows are
-      // private to their thread; row j is read-only here), so no extra barrier is needed
       const double pinv = 1.0 / sP[j * PS + j];
-      if (!(KMH_LU_EXP & 8))
+      unsigned long long key = 0ull;
       for (int r = j + 1 + tid; r < m; r += LU_TPB) {
         const double l = sP[r * PS + j] * pinv;
         sP[r * PS + j] = l;
         for (int c = j + 1; c < nb; ++c) sP[r * PS + c] -= l * sP[j * PS + c];
+        if (j + 1 < nb) { const unsigned long long k = row_key(sP[r * PS + j + 1], r); key = k > key ? k : key; }
       }
-      __syncthreads();
+      if (j + 1 < nb) publish(key, j + 1);
     }
-    }
+    __syncthreads();
     // 3. (no interchanges in memory: rowmap)
     // 4. panel back to global
     for (int e = tid; e < m * nb; e += LU_TPB) {
@@ -637,7 +574,6 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
     const int ncols = n - k0 - nb;
     if (ncols > 0) {
       // 5. U12 = L11^-1 A12, one thread per column
-      if (!(KMH_LU_EXP & 2))
       for (int c = tid; c < ncols; c += LU_TPB) {
         double col[NB];
 #pragma unroll
@@ -660,8 +596,7 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
       // factorisation, which the round-2 experiments went after, is the smaller part); a matrix-core tile reads 2
       // per 16.  A / B operands: lane l holds L[r0 + (l & 15)][4 s + (l >> 4)] and U[4 s + (l >> 4)][c0 + (l & 15)];
       // result register q of lane l is row (l >> 4) + 4 q, column l & 15.
-      if (KMH_LU_EXP & 1) {
-      } else if (MFMA64) {
+      if (MFMA64) {
         typedef double kmh_d4 __attribute__((ext_vector_type(4)));
         const int t16 = (ncols + 15) / 16;
         const int li = lane & 15, lk = lane >> 4;

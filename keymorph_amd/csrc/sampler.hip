@@ -355,12 +355,7 @@ __global__ __launch_bounds__(TPB) void sample_bwd_grid_lc_kernel(
 // registers, 32-bit corner offsets, buffer loads, range-checked stores.
 // The blend is blend8 on the same corner values (a corner past the far border has weight 0 there and reads 0 here):
 // bit-equal to the single-channel kernel (tests/test_ops_gpu.py::test_multichannel_sampler_equals_per_channel).
-#ifndef KMH_MT_X
-#define KMH_MT_X 16
-#define KMH_MT_Y 8
-#define KMH_MT_Z 8
-#endif
-constexpr int MT_X = KMH_MT_X, MT_Y = KMH_MT_Y, MT_Z = KMH_MT_Z;
+constexpr int MT_X = 16, MT_Y = 8, MT_Z = 8;
 static_assert(MT_X * MT_Y * MT_Z == TPB * PASSES && (MT_X & (MT_X - 1)) == 0 && (MT_Y & (MT_Y - 1)) == 0 && MT_X % 4 == 0,
               "1024-voxel tiles with power-of-two sides");
 constexpr int MT_LX = __builtin_ctz(MT_X), MT_LXY = __builtin_ctz(MT_X * MT_Y);

@@ -39,9 +39,19 @@ def test_no_inflight_asm_destination_is_copied():
 @needs_hipcc
 def test_audit_flags_the_variant_that_crashed():
     """Positive control: the stage-deep fragment ring in "=v" registers (KMH_S_DEEP_RING_V=1, never built into the library) is the
-    variant whose in-flight destinations the compiler moved into AGPRs and which faulted on the GPU -- the audit must see that."""
-    res = _audit("-DKMH_S_DEEP_RING_V=1", "-DKMH_S_CW=0", "-DKMH_S_IL=0", "-DKMH_S_UNCOND=0")      # (the configuration it crashed in)
-    assert any(bad for _, bad in res.values()), res
+    variant whose in-flight destinations the compiler moved into AGPRs and which faulted on the GPU -- the audit must see that, in
+    the DEEP instances (the only ones with that ring) and nowhere else, and must see nothing once the ring is taken out again."""
+    # The configuration it crashed in, less its conditional requests for a stage after the last (-DKMH_S_UNCOND=0, a switch that is
+    # gone): with full drains that arm alone put in-flight destinations into the pooling instances, ring or no ring, so it
+    # confounded the control.  The "reads first" schedule (KMH_S_IL=0) stays: under the dealt one the compiler moves no ring register.
+    flags = ("-DKMH_S_CW=0", "-DKMH_S_IL=0")
+    res = _audit("-DKMH_S_DEEP_RING_V=1", *flags)
+    bad = {k for k, (_, touched) in res.items() if touched}
+    assert bad, res
+    assert all("conv3_fwd_s_kernelILi1ELb0ELb0E" in k for k in bad), bad          # <NT = 1, !ZP, !SPLIT, ...>: the DEEP instances
+    assert any("conv3_fwd_s_kernelILi1ELb0ELb0ELb0ELb0E" in k for k in bad), bad   # ... the plain one among them
+    res = _audit(*flags)                                                           # negative control: the same build without the ring
+    assert not {k: v for k, v in res.items() if v[1]}, res
 
 
 def test_scan_follows_loop_back_edges():

@@ -4,7 +4,9 @@ code as it was.  Every csrc/*.hip is compiled to gfx950 assembly with exactly th
 FILE_FLAGS, `-S --cuda-device-only`); per kernel instance (mangled name) the fingerprint is the sha256 of its instruction text up
 to .Lfunc_end -- comments and .loc / .file / .cfi / .p2align lines dropped, .LBB<n>_ renumbered to .LBB_ -- plus its
 .amdhsa_kernel ... .end_amdhsa_kernel block (registers, LDS, scratch).
-usage: tools/kernel_fingerprint.py > table.tsv      (object, kernel, instruction count, hash; run in both trees, then diff)"""
+usage: tools/kernel_fingerprint.py [FILE.hip ...] [-DNAME=V ...] > table.tsv
+(object, kernel, instruction count, hash; run in both trees, then diff.  Names ending in .hip restrict the run to those units of
+csrc/; every other argument goes to the compiler after the library's flags, to fingerprint a build arm such as the fall-back.)"""
 import hashlib
 import os
 import re
@@ -30,11 +32,15 @@ def kernels(txt):
 
 
 if __name__ == "__main__":
+    only = [a for a in sys.argv[1:] if a.endswith(".hip")]
+    extra = [a for a in sys.argv[1:] if not a.endswith(".hip")]
     for src in build.sources():
         name = os.path.basename(src)
+        if only and name not in only:
+            continue
         with tempfile.TemporaryDirectory() as td:
             out = os.path.join(td, "k.s")
-            subprocess.run([build._hipcc(), *build.FLAGS, *build.FILE_FLAGS.get(name, []), "-S", "--cuda-device-only", src, "-o", out],
+            subprocess.run([build._hipcc(), *build.FLAGS, *build.FILE_FLAGS.get(name, []), *extra, "-S", "--cuda-device-only", src, "-o", out],
                            check=True, stderr=subprocess.DEVNULL)
             for n, k, h in kernels(open(out).read()):
                 print(f"{name}\t{n}\t{k}\t{h}")
