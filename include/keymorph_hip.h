@@ -474,6 +474,43 @@ int kmh_headcom_bwd_bf(const float* dpts, const float* dpower, const float* feat
 int kmh_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_scale, void* stream);
 
+/* ---- brain extraction (keymorph/model.py:533-659, notebooks/[B] Brain Extraction.ipynb) ---- */
+/* Trilinear resize with PyTorch's align_corners=False semantics.  channels_last == 0: (N,C,D,H,W) storage, else (N,D,H,W,C);
+ * the two layouts give bit-identical values.  tz / ty / tx: per-axis device tables of 3 * out ints built by the host with
+ * separately rounded fp32 operations: taps i0[out], taps i1[out], weights lam[out] (float bits).  The backward is the exact
+ * transpose written as a gather (no float atomics): rz / ry / rx hold 2 * in ints, the first and the last output index that
+ * references each input index (first > last: none).  Tensors of 2^31 elements or more: -22. */
+int kmh_resize_trilinear3d_fwd(const float* x, float* y, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                               const int* tz, const int* ty, const int* tx, int channels_last, void* stream);
+int kmh_resize_trilinear3d_bwd(const float* gy, float* gx, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                               const int* tz, const int* ty, const int* tx, const int* rz, const int* ry, const int* rx,
+                               int channels_last, void* stream);
+/* Connected components with 26-neighbour connectivity of N binary masks (N,D,H,W) bytes: labels (int32) = 1 + the
+ * raster-order linear index of the component's first voxel, 0 = background.  kmh_clean_mask3d: out = 1 where the voxel's
+ * component has size / (largest size of its sample) > threshold (division in double).  info (N + 1 ints) | NULL: the largest
+ * component size per sample (kmh_clean_mask3d only), then a flag set when a mask value other than 0 / 1 was seen. */
+size_t kmh_components3d_ws_bytes(int N, int D, int H, int W);
+int kmh_components3d(const unsigned char* mask, int* labels, int N, int D, int H, int W, int* info, void* ws, void* stream);
+int kmh_clean_mask3d(const unsigned char* mask, unsigned char* out, int N, int D, int H, int W, double threshold, int* info,
+                     void* ws, void* stream);
+
+/* Direct fp32 3x3x3 convolutions (padding 1, NDHWC, exact fp32 FMAs) for thin layers the split-operand kernels are not built
+ * for (Simple_Unet: 1 -> 4, 4 -> 8, 8 -> 1, 1 -> 1 and the transposed pairs).  kmh_conv3d_thin_ok(Cin, Cout): the forward /
+ * data-gradient kernel serves a LAUNCH with these input / output channels (Cin <= 8, Cout in {1, 4, 8, 16});
+ * kmh_conv3d_thin_wgrad_ok: the weight gradient serves the layer (27 Cin Cout + Cout <= 1024).
+ * fwd: y = conv(x, w (Cout,Cin,3,3,3)) + bias|NULL, ReLU if relu_out.  dgrad: dx (..,Cin) from dz (..,Cout) and the layer's w;
+ * dzmask (dz's shape)|NULL: the layer's ReLU output, dz counts as 0 where it is not > 0.  wgrad: dw and db|NULL; partial sums go
+ * through ws and a fixed-order second pass (no float atomics: repeat calls are bit-identical). */
+int kmh_conv3d_thin_ok(int Cin, int Cout);
+int kmh_conv3d_thin_wgrad_ok(int Cin, int Cout);
+int kmh_conv3d_thin_fwd(const float* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int Cin,
+                        int Cout, int relu_out, void* stream);
+int kmh_conv3d_thin_dgrad(const float* dz, const float* dzmask, const float* w, float* dx, int N, int D, int H, int W, int Cin,
+                          int Cout, void* stream);
+size_t kmh_conv3d_thin_wgrad_ws_bytes(int N, int D, int H, int W, int Cin, int Cout);
+int kmh_conv3d_thin_wgrad(const float* x, const float* dz, const float* dzmask, float* dw, float* db, int N, int D, int H,
+                          int W, int Cin, int Cout, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

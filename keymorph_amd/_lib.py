@@ -138,6 +138,17 @@ PROTOS = {
     "kmh_headcom_fwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f]),
     "kmh_headcom_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f]),
     "kmh_adam_step": (_i, [_f, _f, _f, _f, _ll, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _f]),
+    "kmh_resize_trilinear3d_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f]),
+    "kmh_resize_trilinear3d_bwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f]),
+    "kmh_components3d_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "kmh_components3d": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f]),
+    "kmh_clean_mask3d": (_i, [_f, _f, _i, _i, _i, _i, C.c_double, _f, _f, _f]),
+    "kmh_conv3d_thin_ok": (_i, [_i, _i]),
+    "kmh_conv3d_thin_wgrad_ok": (_i, [_i, _i]),
+    "kmh_conv3d_thin_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_conv3d_thin_dgrad": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_conv3d_thin_wgrad_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "kmh_conv3d_thin_wgrad": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f]),
 }
 
 _lib = None

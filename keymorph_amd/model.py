@@ -354,9 +354,98 @@ class KeyMorph(nn.Module):
             self.align_keypoints_in_real_world_coords = saved
 
 
-# keymorph/model.py:533-640 also holds a brain-mask U-Net and its post-processing, unrelated to registration: names only.
-from ._absent import absent_class as _absent_class, absent_function as _absent_function   # noqa: E402
+# ----------------------------------------------------------------------------------------------------------------------
+# Brain extractor (keymorph/model.py:533-659; notebooks/[B] Brain Extraction.ipynb): the preprocessing step users run before
+# they register their own scans.  Same constructors and state_dict keys as the reference (block{0..8}.conv1.{weight,bias},
+# conv.{weight,bias}; InstanceNorm holds no parameters and no buffers), so its checkpoints load with strict=True.
+# ----------------------------------------------------------------------------------------------------------------------
+class simple_block(nn.Module):
+    """Conv3d(k3,p1,bias) -> [InstanceNorm3d(affine=False)] -> ReLU (keymorph/model.py:598-616).  Called on its own it takes
+    and returns (N,C,D,H,W) like the reference; Simple_Unet calls `ndhwc` and stays in (N,D,H,W,C) between the blocks."""
 
-Simple_Unet = _absent_class("Simple_Unet", "keymorph/model.py:533", nn.Module)
-simple_block = _absent_class("simple_block", "keymorph/model.py:598", nn.Module)
-clean_mask = _absent_function("clean_mask", "keymorph/model.py:622")
+    def __init__(self, in_channels, out_channels, use_in):
+        super().__init__()
+        self.use_in = use_in
+        self.conv1 = nn.Conv3d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)     # parameter holder
+        self.bn1 = nn.InstanceNorm3d(out_channels)                                                # no parameters, no buffers
+        self.activation = nn.ReLU(out_channels)
+
+    def ndhwc(self, x):
+        from . import brain_ops
+        return brain_ops.conv_layer(x, self.conv1.weight, self.conv1.bias, use_in=bool(self.use_in))
+
+    def forward(self, x):
+        from . import backbone_ops as B
+        return B.to_ncdhw(self.ndhwc(B.to_ndhwc(x)))
+
+
+class Simple_Unet(nn.Module):
+    """Neural network of the brain extractor (keymorph/model.py:533-595): four encoder blocks with MaxPool3d(2) between them, a
+    bottleneck, four decoder blocks on [x2 trilinear upsampling, skip] and a final Conv3d(out_ch, out_ch, 3, padding 1).
+    (N,C,D,H,W) fp32 in and out, (N,D,H,W,C) inside; D, H, W must be multiples of 16."""
+
+    def __init__(self, input_ch, out_ch, use_in, enc_nf, dec_nf):
+        super().__init__()
+        self.down = torch.nn.MaxPool3d(2, 2)                  # holder (no parameters): the pooling runs in backbone_ops
+        self.block0 = simple_block(input_ch, enc_nf[0], use_in)
+        self.block1 = simple_block(enc_nf[0], enc_nf[1], use_in)
+        self.block2 = simple_block(enc_nf[1], enc_nf[2], use_in)
+        self.block3 = simple_block(enc_nf[2], enc_nf[3], use_in)
+        self.block4 = simple_block(enc_nf[3], dec_nf[0], use_in)
+        self.block5 = simple_block(dec_nf[0] * 2, dec_nf[1], use_in)
+        self.block6 = simple_block(dec_nf[1] * 2, dec_nf[2], use_in)
+        self.block7 = simple_block(dec_nf[2] * 2, dec_nf[3], use_in)
+        self.block8 = simple_block(dec_nf[3] * 2, out_ch, use_in)
+        self.conv = nn.Conv3d(out_ch, out_ch, kernel_size=3, padding=1)
+
+    def forward(self, x_in):
+        from . import backbone_ops as B
+        from . import brain_ops
+        if x_in.dim() != 5:
+            raise ValueError(f"Simple_Unet: expected (N, C, D, H, W), got {tuple(x_in.shape)}")
+        if any(int(s) % 16 or int(s) == 0 for s in x_in.shape[2:]):
+            raise ValueError(f"Simple_Unet: D, H, W must be multiples of 16 (four 2x poolings whose upsampled outputs are "
+                             f"concatenated with the skips), got {tuple(x_in.shape[2:])}")
+        x = B.to_ndhwc(x_in)                                   # raises KeymorphHipError for a CPU tensor
+        x0 = self.block0.ndhwc(x)
+        x1 = self.block1.ndhwc(B.maxpool2(x0))
+        x2 = self.block2.ndhwc(B.maxpool2(x1))
+        x3 = self.block3.ndhwc(B.maxpool2(x2))
+        x = self.block4.ndhwc(B.maxpool2(x3))
+        for blk, skip in ((self.block5, x3), (self.block6, x2), (self.block7, x1), (self.block8, x0)):
+            x = blk.ndhwc(torch.cat([brain_ops.upsample2(x), skip], dim=-1))
+        out = brain_ops.conv_layer(x, self.conv.weight, self.conv.bias, use_in=False, relu=False)
+        return B.to_ncdhw(out)
+
+
+def clean_mask(mask, threshold=0.2):
+    """keymorph/model.py:622-659 on the GPU: label the binary 3-D mask under full 26-neighbour connectivity (what
+    skimage.morphology.label's default is in 3-D) and keep the components with size / (largest size) > threshold -- strict,
+    the division in double on two integers, as numpy decides it.  A numpy array in gives a numpy uint8 array out (the
+    reference's contract; the work still runs on the current GPU), a torch tensor in gives a uint8 tensor on the current GPU.
+    ValueError: not 3-D, values other than 0 / 1 (the reference labels by VALUE, so only a binary mask means the same here),
+    or an empty mask (the reference's np.max([]))."""
+    from . import ops
+    as_numpy = isinstance(mask, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(mask)) if as_numpy else mask
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"clean_mask: expected a numpy array or a torch tensor, got {type(mask).__name__}")
+    if t.dim() != 3:
+        raise ValueError(f"clean_mask: expected a 3-D mask, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError("clean_mask: the mask is empty (no component to compare sizes with)")
+    if t.dtype not in (torch.bool, torch.uint8):
+        # any other dtype: binary means every value is exactly 0 or 1
+        if not bool(((t == 0) | (t == 1)).all()):
+            raise ValueError("clean_mask: the mask holds values other than 0 and 1")
+        t = t != 0
+    if as_numpy or not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    out, info = ops.clean_mask3d(t[None], threshold)
+    largest, bad = info.tolist()
+    if bad:
+        raise ValueError("clean_mask: the mask holds values other than 0 and 1")
+    if largest == 0:
+        raise ValueError("clean_mask: the mask is empty (no component to compare sizes with)")
+    out = out[0]
+    return out.cpu().numpy() if as_numpy else out

@@ -643,3 +643,163 @@ def lc2(us: Tensor, mr: Tensor, patch: int, radii: Sequence[int], alpha: float =
         if pad < 1 or patch - 2 * pad != w:
             raise ValueError(f"lc2: radius {r} does not fit a patch of {patch}: the crop [{pad}:-{pad}] is not {w} voxels wide")
     return _LC2.apply(us, mr, patch, radii, float(alpha), float(beta), bool(mean))
+
+
+# --------------------------------------------------------------------------
+# trilinear resize (F.interpolate(mode="trilinear", align_corners=False); keymorph/model.py:576-588)
+# --------------------------------------------------------------------------
+def resize_out_size(n_in: int, scale_factor: float) -> int:
+    import math
+    return int(math.floor(n_in * float(scale_factor)))
+
+
+def resize_axis_scale(n_in: int, n_out: int, scale_factor=None):
+    """The fp32 coordinate scale of one axis: the fp32 quotient in / out when a size was given, fp32(1 / scale_factor) when a
+    factor was."""
+    import numpy as np
+    if scale_factor is None:
+        return np.float32(n_in) / np.float32(n_out)
+    return np.float32(1.0 / float(scale_factor))
+
+
+def resize_axis_table(n_in: int, n_out: int, s):
+    """THE per-axis definition shared by the kernel, the tests and the fp64 restatement.  For output index o:
+    src = max(s * (o + 0.5) - 0.5, 0) in fp32 with separately rounded multiply and subtract, i0 = min(floor(src), in - 1),
+    i1 = min(i0 + 1, in - 1), lam = src - i0.  Returns numpy (i0, i1, lam, lo, hi): lo[i] .. hi[i] is the range of outputs that
+    reference input i (lo > hi: none); a set of referencing outputs that is not one contiguous range raises."""
+    import numpy as np
+    s = np.float32(s)
+    o = np.arange(n_out, dtype=np.float32)
+    src = np.maximum(s * (o + np.float32(0.5)) - np.float32(0.5), np.float32(0.0)).astype(np.float32)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    lam = (src - i0.astype(np.float32)).astype(np.float32)
+    lo = np.ones(n_in, dtype=np.int64)
+    hi = np.zeros(n_in, dtype=np.int64)
+    for i in range(n_in):
+        ref = np.nonzero((i0 == i) | (i1 == i))[0]
+        if len(ref):
+            lo[i], hi[i] = ref[0], ref[-1]
+            if hi[i] - lo[i] + 1 != len(ref):
+                raise ValueError(f"resize {n_in} -> {n_out}: the outputs that read input {i} are not one contiguous range")
+    return i0.astype(np.int32), i1.astype(np.int32), lam, lo.astype(np.int32), hi.astype(np.int32)
+
+
+_RESIZE_TABS = {}
+
+
+def _resize_tables(n_in: int, n_out: int, s, device):
+    """device int32 tensors (forward table 3 * out, range table 2 * in) of one axis, built once per (in, out, s, device)"""
+    import numpy as np
+    key = (n_in, n_out, np.float32(s).tobytes(), str(device))
+    t = _RESIZE_TABS.get(key)
+    if t is None:
+        i0, i1, lam, lo, hi = resize_axis_table(n_in, n_out, s)
+        fwd = torch.from_numpy(np.concatenate([i0, i1, lam.view(np.int32)])).to(device)
+        rng = torch.from_numpy(np.concatenate([lo, hi])).to(device)
+        t = _RESIZE_TABS[key] = (fwd, rng)
+    return t
+
+
+class _ResizeTrilinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, out_size, scales, channels_last):
+        lib = _lib.load()
+        x = _prep(x, "x")
+        if channels_last:
+            N, D, H, W, C = x.shape
+        else:
+            N, C, D, H, W = x.shape
+        Do, Ho, Wo = out_size
+        tabs = [_resize_tables(i, o, s, x.device) for i, o, s in zip((D, H, W), out_size, scales)]
+        y = torch.empty((N, Do, Ho, Wo, C) if channels_last else (N, C, Do, Ho, Wo), dtype=torch.float32, device=x.device)
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": 4.0 * (x.numel() + y.numel())}
+        check(lib.kmh_resize_trilinear3d_fwd(_p(x), _p(y), N, C, D, H, W, Do, Ho, Wo, _p(tabs[0][0]), _p(tabs[1][0]),
+                                             _p(tabs[2][0]), int(channels_last), _stream()), "kmh_resize_trilinear3d_fwd")
+        ctx.tabs, ctx.dims, ctx.cl = tabs, (N, C, D, H, W, Do, Ho, Wo), bool(channels_last)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib.load()
+        gy = _prep(gy)
+        N, C, D, H, W, Do, Ho, Wo = ctx.dims
+        tz, ty, tx = ctx.tabs
+        gx = torch.empty((N, D, H, W, C) if ctx.cl else (N, C, D, H, W), dtype=torch.float32, device=gy.device)
+        check(lib.kmh_resize_trilinear3d_bwd(_p(gy), _p(gx), N, C, D, H, W, Do, Ho, Wo, _p(tz[0]), _p(ty[0]), _p(tx[0]),
+                                             _p(tz[1]), _p(ty[1]), _p(tx[1]), int(ctx.cl), _stream()),
+              "kmh_resize_trilinear3d_bwd")
+        return gx, None, None, None
+
+
+def resize_trilinear3d(x: Tensor, size=None, scale_factor=None, channels_last: bool = False) -> Tensor:
+    """x (N,C,D,H,W), or (N,D,H,W,C) with channels_last, resized like F.interpolate(mode="trilinear", align_corners=False);
+    exactly one of `size` (3 ints) and `scale_factor` (a number or 3 numbers).  Differentiable; the gradient is bitwise
+    repeatable.  The two layouts give bit-identical values."""
+    if (size is None) == (scale_factor is None):
+        raise ValueError("resize_trilinear3d: give exactly one of size and scale_factor")
+    if x.dim() != 5:
+        raise ValueError(f"resize_trilinear3d: expected a 5-D tensor, got {tuple(x.shape)}")
+    dims = tuple(x.shape[1:4]) if channels_last else tuple(x.shape[2:5])
+    if size is not None:
+        out = tuple(int(v) for v in size)
+        factors = (None,) * 3
+    else:
+        factors = tuple(float(v) for v in scale_factor) if isinstance(scale_factor, (tuple, list)) else (float(scale_factor),) * 3
+        if len(factors) != 3:
+            raise ValueError("resize_trilinear3d: scale_factor needs one or three numbers")
+        out = tuple(resize_out_size(i, f) for i, f in zip(dims, factors))
+    if len(out) != 3 or min(out) < 1:
+        raise ValueError(f"resize_trilinear3d: bad output size {out}")
+    scales = tuple(resize_axis_scale(i, o, f) for i, o, f in zip(dims, out, factors))
+    return _ResizeTrilinear.apply(x, out, scales, bool(channels_last))
+
+
+# --------------------------------------------------------------------------
+# connected components / clean_mask (keymorph/model.py:622-659)
+# --------------------------------------------------------------------------
+def _mask_bytes(mask: Tensor, name: str) -> Tensor:
+    if not mask.is_cuda:
+        raise _lib.KeymorphHipError(f"{name} is on {mask.device}: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
+    if mask.device.index != torch.cuda.current_device():
+        raise _lib.KeymorphHipError(f"{name} is on {mask.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    elif mask.dtype != torch.uint8:
+        raise ValueError(f"{name}: expected a bool or uint8 mask, got {mask.dtype}")
+    return mask.contiguous()
+
+
+def connected_components3d(mask: Tensor) -> Tensor:
+    """(D,H,W) bool / uint8 mask on the GPU -> int32 labels under full 26-neighbour connectivity: 1 + the raster-order linear
+    index of the component's first voxel, 0 = background.  The numbering is canonical: the same on every run."""
+    if mask.dim() != 3:
+        raise ValueError(f"connected_components3d: expected a (D, H, W) mask, got {tuple(mask.shape)}")
+    lib = _lib.load()
+    m = _mask_bytes(mask, "mask")
+    D, H, W = m.shape
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=m.device)
+    if m.numel() == 0:
+        return labels
+    ws = workspace(int(lib.kmh_components3d_ws_bytes(1, D, H, W)), m.device, "components")
+    check(lib.kmh_components3d(_p(m), _p(labels), 1, D, H, W, None, _p(ws), _stream()), "kmh_components3d")
+    return labels
+
+
+def clean_mask3d(mask: Tensor, threshold: float):
+    """(N,D,H,W) bool / uint8 masks on the GPU -> (uint8 masks that keep the components with size / largest size > threshold,
+    info): info is an int32 device tensor of N + 1 entries, the largest component size per sample and then a flag that is 1
+    when some mask value was neither 0 nor 1."""
+    if mask.dim() != 4:
+        raise ValueError(f"clean_mask3d: expected (N, D, H, W) masks, got {tuple(mask.shape)}")
+    lib = _lib.load()
+    m = _mask_bytes(mask, "mask")
+    N, D, H, W = m.shape
+    out = torch.empty_like(m)
+    info = torch.zeros(N + 1, dtype=torch.int32, device=m.device)
+    if m.numel() == 0:
+        return out, info
+    ws = workspace(int(lib.kmh_components3d_ws_bytes(N, D, H, W)), m.device, "components")
+    check(lib.kmh_clean_mask3d(_p(m), _p(out), N, D, H, W, float(threshold), _p(info), _p(ws), _stream()), "kmh_clean_mask3d")
+    return out, info

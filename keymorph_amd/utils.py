@@ -210,3 +210,9 @@ def sample_valid_coordinates_2d(x, num_points, point_space="norm"):
 def sample_valid_coordinates_3d(x, num_points, point_space="norm"):
     """keymorph/utils.py:139-162: the "xy" draw of `sample_valid_coordinates` for a (1, 1, D, H, W) volume."""
     return sample_valid_coordinates(x, num_points, 3, point_space=point_space, indexing="xy")
+
+
+def resize_trilinear(x, size=None, scale_factor=None):
+    """F.interpolate(x, size | scale_factor, mode="trilinear", align_corners=False) for (N, C, D, H, W) fp32 CUDA tensors
+    (keymorph/model.py:576-588; what tio.Resize / --half_resolution amount to): exactly one of the two arguments."""
+    return ops.resize_trilinear3d(x, size=size, scale_factor=scale_factor)
