@@ -132,6 +132,18 @@ int kmh_lc2_fwd(const float* us, const float* mr, int N, int S, int P, const int
 int kmh_lc2_bwd(const float* us, const float* mr, const float* gout, int N, int S, int P, const int* radii, int R,
                 int reduce_mean, const void* ws, float* dus, float* dmr, void* stream);
 
+/* ---- mutual information through a Parzen-window joint histogram (csrc/mi.hip states the definition) ---- */
+/* a, b: (N, V) float32 contiguous, 8 <= bins <= 64.  kmh_mi_hist: per-sample ranges (has_range_x != 0: the caller's (lo_x, hi_x)
+ * instead of the image's minimum and maximum) -> rng (N, 4) = (lo_a, s_a, lo_b, s_b), and the fixed-point joint table in ws
+ * (kmh_mi_ws_bytes(N, bins) bytes).  kmh_mi_final: the table -> mi (N floats) and G (N, bins, bins) = ln(p / (pa pb)) where
+ * p > 0, else 0.  kmh_mi_bwd: da = gout[n] dMI_n / da, db likewise, (N, V) float32, either may be NULL. */
+size_t kmh_mi_ws_bytes(int N, int bins);
+int kmh_mi_hist(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
+                int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream);
+int kmh_mi_final(const void* ws, const float* rng, int N, long long V, int bins, float* mi, float* G, void* stream);
+int kmh_mi_bwd(const float* a, const float* b, const float* rng, const float* G, const float* gout, int N, long long V,
+               int bins, float* da, float* db, void* stream);
+
 /* ---- a9: AffineTransform.get_flow_field, keymorph/transformations.py:37-79 and
  *      uniform_norm_grid keymorph/utils.py:387-398.  mat (N,3,4) = inverse_transform_matrix[:, :3, :]
  *      acting on ij coords; out (N,D,H,W,3) already flipped to xyz. */

@@ -65,6 +65,10 @@ PROTOS = {
     "kmh_lc2_ws_bytes": (_sz, [_i, _i]),
     "kmh_lc2_fwd": (_i, [_f, _f, _i, _i, _i, _f, _i, C.c_double, C.c_double, _i, _f, _f, _f]),
     "kmh_lc2_bwd": (_i, [_f, _f, _f, _i, _i, _i, _f, _i, _i, _f, _f, _f, _f]),
+    "kmh_mi_ws_bytes": (_sz, [_i, _i]),
+    "kmh_mi_hist": (_i, [_f, _f, _i, _ll, _i, _i, C.c_float, C.c_float, _i, C.c_float, C.c_float, _f, _f, _f]),
+    "kmh_mi_final": (_i, [_f, _f, _i, _ll, _i, _f, _f, _f]),
+    "kmh_mi_bwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
     "kmh_affine_build_matrix": (_i, [_f, _f, _f, _f, _f, _i, _f]),
     "kmh_affine_points_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _f]),
     "kmh_com3d_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),

@@ -1,8 +1,9 @@
 """On-disk formats and loader shims either side of the registration path: host-side
-only -- no GPU code and no third-party readers (torchio / nibabel are not needed).  brain.py is the one exception: the
-notebook's brain-extraction cell as a call, which runs the package's GPU operators."""
+only -- no GPU code and no third-party readers (torchio / nibabel are not needed).  brain.py and centering.py are the
+exceptions: the notebooks' brain-extraction and centering cells as calls, which run the package's GPU operators."""
 from .checkpoint import load_checkpoint, save_checkpoint          # noqa: F401
 from .nifti import read_nifti, write_nifti                        # noqa: F401
 from .pairs import DATA, AFFINE, PairLoader, make_subject         # noqa: F401
 from .groupwise import evaluate_group, save_dict_as_json         # noqa: F401
 from .brain import extract_brain, load_brain_extractor         # noqa: F401
+from .centering import center_to, estimate_translation, translate         # noqa: F401

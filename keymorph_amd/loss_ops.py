@@ -431,3 +431,19 @@ class ImageLC2(torch.nn.Module):
         """run() on a batch of (B, 1, P, P, P) patches -> (B,)."""
         us, mr = us.squeeze(1), mr.squeeze(1)
         return ops.lc2(us, mr, us.shape[-1], (radius,), alpha, beta)
+
+
+# --------------------------------------------------------------------------
+# mutual information on the GPU (csrc/mi.hip): the intensity similarity between MR modalities (T1 / T2 / PD)
+# --------------------------------------------------------------------------
+class MILoss(torch.nn.Module):
+    """-mean over the batch of the mutual information of (N, 1, D, H, W) float32 pairs (ops.mutual_information: cubic B-spline
+    Parzen windows, `bins` bins, per-sample ranges); lower is better, differentiable in both inputs:
+    MILoss()(align_img(grid, img_m), img_f) scores or trains a multi-modal alignment."""
+
+    def __init__(self, bins=32):
+        super().__init__()
+        self.bins = bins
+
+    def forward(self, pred, target):
+        return -ops.mutual_information(pred, target, self.bins).mean()

@@ -646,6 +646,94 @@ def lc2(us: Tensor, mr: Tensor, patch: int, radii: Sequence[int], alpha: float =
 
 
 # --------------------------------------------------------------------------
+# mutual information through a Parzen-window joint histogram (csrc/mi.hip states the definition)
+# --------------------------------------------------------------------------
+MI_MIN_BINS, MI_MAX_BINS = 8, 64
+
+
+def _mi_forward(a, b, bins, range_a, range_b):
+    """(mi (N,), rng (N, 4), G (N, bins, bins)) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise."""
+    lib = _lib.load()
+    N, V = a.shape[0], a[0].numel()
+    dev = a.device
+    ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=dev)
+    rng = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    mi = torch.empty((N,), dtype=torch.float32, device=dev)
+    G = torch.empty((N, bins, bins), dtype=torch.float32, device=dev)
+    ra, rb = range_a or (0.0, 0.0), range_b or (0.0, 0.0)
+    if _lib.profiler.enabled:  # 8 B read per voxel
+        _lib.profiler.meta = {"bytes": 8.0 * N * V}
+    check(lib.kmh_mi_hist(_p(a), _p(b), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None), rb[0],
+                          rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_hist")
+    check(lib.kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+    return mi, rng, G
+
+
+class _MI(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, bins, range_a, range_b):
+        mi, rng, G = _mi_forward(a, b, bins, range_a, range_b)
+        ctx.save_for_backward(a, b, rng, G)
+        ctx.bins = bins
+        return mi
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        a, b, rng, G = ctx.saved_tensors
+        gout = _prep(gout)
+        N, V = a.shape[0], a[0].numel()
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if _lib.profiler.enabled:  # 8 B read and 4 B written per voxel and gradient
+            _lib.profiler.meta = {"bytes": (8.0 + 4.0 * ((da is not None) + (db is not None))) * N * V}
+        check(lib.kmh_mi_bwd(_p(a), _p(b), _p(rng), _p(G), _p(gout), N, V, ctx.bins, _p(da), _p(db), _stream()), "kmh_mi_bwd")
+        return da, db, None, None, None
+
+
+def _mi_check(a, b, bins, range_a, range_b):
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, Tensor) or not t.is_cuda:
+            raise _lib.KeymorphHipError(f"mutual_information: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
+                                        "(no CPU fallback)")
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.KeymorphHipError(f"mutual_information: {name} is on {t.device} but the current device is "
+                                        f"cuda:{torch.cuda.current_device()}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"mutual_information: {name} must be float32, got {t.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"mutual_information: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0:
+        raise ValueError(f"mutual_information: expected two non-empty (N, 1, D, H, W) volumes, got {tuple(a.shape)}")
+    if int(bins) != bins or not MI_MIN_BINS <= bins <= MI_MAX_BINS:
+        raise ValueError(f"mutual_information: bins must be an integer in [{MI_MIN_BINS}, {MI_MAX_BINS}], got {bins}")
+    out = []
+    for name, r in (("range_a", range_a), ("range_b", range_b)):
+        if r is not None:
+            if len(r) != 2 or not float(r[0]) <= float(r[1]):
+                raise ValueError(f"mutual_information: {name} must be (lo, hi) with lo <= hi, got {r}")
+            r = (float(r[0]), float(r[1]))
+        out.append(r)
+    return a.contiguous(), b.contiguous(), int(bins), out[0], out[1]
+
+
+def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None) -> Tensor:
+    """Mutual information (nats) of two (N, 1, D, H, W) float32 volumes on the current GPU, per sample -> (N,), differentiable in
+    both.  Parzen-window joint histogram with the cubic B-spline and Mattes' padding: per sample and image, u = (x - lo) s + 1 with
+    s = (bins - 3) / (hi - lo) over the image's own minimum and maximum (no gradient through them), or over `range_x = (lo, hi)`
+    (values outside are taken at the range's ends); a constant image has s = 0, MI = 0 and zero gradients.  Two calls give
+    bit-identical values and gradients; a batch equals its samples run one by one."""
+    return _MI.apply(*_mi_check(a, b, bins, range_a, range_b))
+
+
+def _mi_table(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None):
+    """(MI (N,), G (N, bins, bins)) without autograd: G = ln(p / (pa pb)) where the joint probability p > 0, else 0 -- the table the
+    gradient of mutual_information gathers from."""
+    mi, _, G = _mi_forward(*_mi_check(a.detach(), b.detach(), bins, range_a, range_b))
+    return mi, G
+
+
+# --------------------------------------------------------------------------
 # trilinear resize (F.interpolate(mode="trilinear", align_corners=False); keymorph/model.py:576-588)
 # --------------------------------------------------------------------------
 def resize_out_size(n_in: int, scale_factor: float) -> int:
