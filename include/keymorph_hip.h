@@ -260,6 +260,17 @@ int kmh_conv3d_fwd_bf_set_dispatch(int mode);
  * returns 1 for the shapes it takes, kmh_conv3d_fwd_bf returns -22 for the others.  Replaces the data gradient of
  * keymorph/unet3d/buildingblocks.py:46-58 (autograd of conv3d) behind a pooling layer (:321-380). */
 int kmh_conv3d_fwd_bf_split_ok(int N, int D, int H, int W, int Cin, int Cout, int terms);
+/* The same operand WITHOUT the scatter ("pooled + winners", layout kind 3 of the backbone's gradient hand-off): xp (N, D/2, H/2,
+ * W/2, Cin) fp32 = the pooled gradient, winners (same shape, bytes) = the window indices 0..7 = (dz, dy, dx) of
+ * kmh_conv3d_fwd_bf_pool / kmh_maxpool3d_fwd; the kernel builds in its own staging the fragment images the pre-split records
+ * would give (the dense tensor, 7/8 zeros, is never written or read).  y and stats_out are bit-identical to in_blocked == 2.
+ * kmh_conv3d_fwd_bf_sparse_ok: 1 for the shapes served (those of kmh_conv3d_fwd_bf_split_ok with even D, H, W, terms == 2 -- not
+ * use_amp's terms == 1), whatever the dispatch mode; -22 from kmh_conv3d_fwd_bf_sparse elsewhere.  Replaces
+ * MaxPool3d's backward (keymorph/unet3d/buildingblocks.py:321-380) followed by conv3d's data gradient (:46-58). */
+int kmh_conv3d_fwd_bf_sparse_ok(int N, int D, int H, int W, int Cin, int Cout, int terms);
+int kmh_conv3d_fwd_bf_sparse(const float* xp, const unsigned char* winners, const void* packed, const float* bias, float* y,
+                             int N, int D, int H, int W, int Cin, int Cout, int relu_out, int terms, const float* ascale,
+                             const float* wscale, void* stats_ws, double* stats_out, void* stream);
 /* the kernel kmh_conv3d_fwd_bf would launch for this call now: 0 conv3_fwd_bf_kernel, 1 / 2 conv3_fwd_g_kernel with a
  * 32- / 64-wide output-channel tile, 3 its z-paired variant (Cout <= 16) */
 int kmh_conv3d_fwd_bf_variant(int N, int D, int H, int W, int Cin, int Cout, int terms, int has_mask, int has_addend);
@@ -333,6 +344,14 @@ int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float* shift, 
                         const float* dzmask, float* dw, int N, int D, int H, int W, int Cin, int Cout, int relu_in,
                         int accumulate, int terms, int append_ones, const float* xscale, const float* dscale, int dz_blocked, const float* w_fold, double* bhat,
                         void* ws, void* stream);
+/* The same weight gradient from the POOLED gradient dzp (N, D/2, H/2, W/2, Cout) and its winner bytes (see
+ * kmh_conv3d_fwd_bf_sparse): bit-identical to dz_blocked == 2 on the scattered records.  kmh_conv3d_wgrad_bf_sparse_ok: 1 where
+ * served (the shapes of kmh_conv3d_wgrad_bf_blocked_ok with even D, H, W, terms == 2). */
+int kmh_conv3d_wgrad_bf_sparse_ok(int N, int D, int H, int W, int Cin, int Cout, int terms);
+int kmh_conv3d_wgrad_bf_sparse(const float* x, const float* scale, const float* shift, const float* dzp,
+                               const unsigned char* winners, float* dw, int N, int D, int H, int W, int Cin, int Cout,
+                               int relu_in, int accumulate, int terms, const float* xscale, const float* dscale,
+                               const float* w_fold, double* bhat, void* ws, void* stream);
 /* First U-Net convolution, forward (csrc/firstlayer.hip): x (N,D,H,W) raw 1-channel input, scale / shift (N)
  * GroupNorm coefficients of that channel (NULL: identity), w (Cout,1,3,3,3), Cout <= 16 ->
  * y (N,D,H,W,Cout) = relu(conv3(x * scale + shift)) in exact fp32 (keymorph/unet3d/buildingblocks.py:46-78 for

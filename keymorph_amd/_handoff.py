@@ -4,7 +4,8 @@ pass that consumes it, each guarded by the tensor's version counter.
     stats       (N,C,2) float64 (sum, sum^2) per (n, channel), from the epilogue that wrote the tensor
     grad_scale  device float[2] {S, 1/S}: the f16x3 range scale of a gradient
     layout      1 = fp32 channel-blocked (N, C/8, D, H, W, 8); 2 = pre-split records (N, C/8, V + 1, 8 floats = 8 fp16 hi + 8 fp16
-                lo, what kmh_maxpool3d_bwd_split writes); absent = dense (N,D,H,W,C)
+                lo, what kmh_maxpool3d_bwd_split writes); 3 = pooled + winners: the pooled gradient (N,D/2,H/2,W/2,C) itself, which with
+                the pooling operator's winner bytes stands for its scatter; absent = dense (N,D,H,W,C)
     lazy_gn     (c123, x): a GroupNorm backward still to be applied to this normalised-input gradient
     up_sources  (skip, low, skip_version, low_version) on the output of upcat()
     packed      (terms, wscale) on a packed-weight buffer

@@ -82,6 +82,8 @@ PROTOS = {
     "kmh_conv3d_fwd_bf_variant": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "kmh_conv3d_fwd_bf_pool_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "kmh_conv3d_fwd_bf_split_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "kmh_conv3d_fwd_bf_sparse_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "kmh_conv3d_fwd_bf_sparse": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "kmh_conv3d_fwd_bf_pool": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f]),
     "kmh_conv3d_up2_dgrad_pack_bytes": (_sz, [_i, _i, _i]),
     "kmh_conv3d_up2_dgrad_pack_weight": (_i, [_f, _f, _i, _i, _i, _i, _i, _f, _f]),
@@ -102,6 +104,8 @@ PROTOS = {
     "kmh_conv3d_wgrad_bf_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "kmh_conv3d_wgrad_bf": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _f, _f]),
     "kmh_conv3d_wgrad_bf_blocked_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "kmh_conv3d_wgrad_bf_sparse_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "kmh_conv3d_wgrad_bf_sparse": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f]),
     "kmh_conv3d_first_layer_wgrad_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_conv3d_first_layer_wgrad": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
     "kmh_conv3d_first_layer_fold": (_i, [_f, _i, _f, _f, _f, _i, _f, _f, _i, _f]),

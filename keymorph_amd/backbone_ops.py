@@ -49,6 +49,7 @@ _SWITCHES = {
     "KEYMORPH_NO_BLOCKED_GRADS": "every gradient in (N,D,H,W,C)",
     "KEYMORPH_NO_BLOCKED_UPCAT": "only the fused decoder operator's gradient in (N,D,H,W,C)",
     "KEYMORPH_NO_SPLIT_POOLGRAD": "the 256^3-level pooled gradient scattered as fp32 instead of pre-split records",
+    "KEYMORPH_NO_SPARSE_POOLGRAD": "the 256^3-level pooled gradient scattered into pre-split records instead of handed over with its winners",
     "KEYMORPH_NO_CONV_POOL": "separate pooling pass instead of the conv epilogue's",
     "KEYMORPH_NO_LAZY_FIRST": "GroupNorm backward of the first block as its own pass",
     "KEYMORPH_NO_LAZY_SKIP": "GroupNorm's backward of a decoder skip applied in the decoder",
@@ -324,14 +325,26 @@ def _conv_meta(N, D, H, W, Cin, Cout, taps=27) -> None:
 
 def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, relu_out, mask=None,
               ascale=None, stats_out: Optional[Tensor] = None, in_blocked: bool = False,
-              addend: Optional[Tensor] = None) -> Tensor:
+              addend: Optional[Tensor] = None, winners: Optional[Tensor] = None) -> Tensor:
     """ascale: range scale of the (normalised) input for the f16x3 mode; measured here when not supplied.
     stats_out (N,Cout,2) float64: filled with the per-channel (sum y, sum y^2) of the output by the split-operand
-    kernels' epilogue (the caller checks `conv_emits_stats()` first)."""
+    kernels' epilogue (the caller checks `conv_emits_stats()` first).
+    in_blocked: the layout kind of x (_blocked_kind); 3: x is the pooled tensor (N,D/2,H/2,W/2,Cin) and `winners` its window bytes."""
     lib = _lib.load()
     y = _f32((N, D, H, W, Cout), x.device)
     _conv_meta(N, D, H, W, Cin, Cout)
     terms, wscale = _packed(packed)
+    if int(in_blocked) == 3:
+        assert terms == 2 and winners is not None and scale is None and shift is None and mask is None and addend is None \
+            and not relu_in and ascale is not None and not amp_enabled(), "pooled + winners: a gradient operand of the f16x3 mode"
+        assert x.shape == winners.shape == (N, D // 2, H // 2, W // 2, Cin) and winners.dtype == torch.uint8
+        sws = None
+        if stats_out is not None:
+            sws = workspace(int(lib.kmh_conv3d_fwd_bf_stats_ws_bytes(N, D, H, W, Cout, BF_ROWS_PER_WAVE)), x.device, "convstats")
+        check(lib.kmh_conv3d_fwd_bf_sparse(_p(x), _p(winners), _p(packed), _p(bias), _p(y), N, D, H, W, Cin, Cout, int(relu_out), 2,
+                                           _p(ascale), _p(wscale), _p(sws), _p(stats_out), _stream()), "kmh_conv3d_fwd_bf_sparse")
+        return y
+    assert winners is None
     if terms:
         if terms == 2 and ascale is None:
             assert scale is None, "a normalised input needs the range scale of the NORMALISED tensor (norm_coeffs)"
@@ -353,13 +366,25 @@ def conv3_raw(x, scale, shift, packed, bias, N, D, H, W, Cin, Cout, relu_in, rel
 
 
 def conv3_wgrad(x, scale, shift, dz, N, D, H, W, Cin, Cout, relu_in, dzmask=None, xscale=None, dscale=None,
-                dz_blocked: bool = False, fold: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+                dz_blocked: bool = False, fold: Optional[Tuple[Tensor, Tensor]] = None,
+                winners: Optional[Tensor] = None) -> Tensor:
     """fold = (weight (Cout,Cin,3,3,3), bhat (N,Cin) float64 zeros): bhat[n,c] += sum_{tap,co} W dW_n, which equals
     sum_v dxn[n,v,c] * xhat[n,v,c] for the data gradient dxn of the same dz (split-operand kernels only).
-    xscale / dscale: range scales of the (normalised) input and of dz for the f16x3 mode (measured if absent)."""
+    xscale / dscale: range scales of the (normalised) input and of dz for the f16x3 mode (measured if absent).
+    dz_blocked: the layout kind of dz (_blocked_kind); 3: dz is the pooled gradient (N,D/2,H/2,W/2,Cout), `winners` its window bytes."""
     lib = _lib.load()
     dw = _f32((Cout, Cin, 3, 3, 3), x.device)
     _conv_meta(N, D, H, W, Cin, Cout)
+    if int(dz_blocked) == 3:
+        assert CONV_MODE == "f16x3" and winners is not None and dzmask is None and xscale is not None and dscale is not None \
+            and not amp_enabled(), "pooled + winners: a gradient operand of the f16x3 mode"
+        assert dz.shape == winners.shape == (N, D // 2, H // 2, W // 2, Cout) and winners.dtype == torch.uint8
+        ws = workspace(int(lib.kmh_conv3d_wgrad_bf_ws_bytes(N, D, H, W, Cin, Cout, 2)), x.device, "wgrad")
+        check(lib.kmh_conv3d_wgrad_bf_sparse(_p(x), _p(scale), _p(shift), _p(dz), _p(winners), _p(dw), N, D, H, W, Cin, Cout,
+                                             int(relu_in), 0, 2, _p(xscale), _p(dscale), _p(fold[0] if fold else None),
+                                             _p(fold[1] if fold else None), _p(ws), _stream()), "kmh_conv3d_wgrad_bf_sparse")
+        return dw
+    assert winners is None
     if CONV_MODE != "f32":
         terms = _TERMS[CONV_MODE]
         ws = workspace(int(lib.kmh_conv3d_wgrad_bf_ws_bytes(N, D, H, W, Cin, Cout, terms)), x.device, "wgrad")
@@ -472,7 +497,9 @@ def grad_blocked_ok(N, D, H, W, Cin, Cout) -> bool:
 
 
 BLOCKED_STATS = {"handoffs": 0}      # channel-blocked gradient hand-offs performed (tests)
-SPLIT_STATS = {"handoffs": 0}        # pooled gradients scattered straight into pre-split fp16 records (tests)
+SPLIT_STATS = {"handoffs": 0}        # pooled gradients handed on with NO fp32 scatter: as pre-split fp16 records, or (counted in
+                                     # SPARSE_STATS too) as the pooled tensor with its winners (tests)
+SPARSE_STATS = {"handoffs": 0}       # pooled gradients handed to both gradient kernels as they are, with the winner bytes (tests)
 
 
 UP2_STATS = {"fold": 0, "boxsum": 0}      # which weight-gradient route the fused upsample + concat convolution took (tests)
@@ -498,9 +525,22 @@ def pool_grad_split_ok(N, D, H, W, Cin, Cout) -> bool:
         bool(lib.kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, 2))
 
 
+def pool_grad_sparse_ok(N, D, H, W, Cin, Cout) -> bool:
+    """May the backward of a (Cin -> Cout) conv + pooling operator hand the POOLED gradient and the winner bytes to both gradient
+    kernels (layout kind 3: no scatter pass, no full-resolution gradient tensor)?  Where the pre-split records are served
+    (`pool_grad_split_ok`) and both consumers take the pooled operand: even sizes, the f16x3 arithmetic -- not under use_amp,
+    whose one-product instances are not built for it.  KEYMORPH_NO_SPARSE_POOLGRAD=1 keeps the pre-split scatter (A/B, tests)."""
+    if _off("KEYMORPH_NO_SPARSE_POOLGRAD") or amp_enabled() or not pool_grad_split_ok(N, D, H, W, Cin, Cout):
+        return False
+    lib = _lib.load()
+    return bool(lib.kmh_conv3d_fwd_bf_sparse_ok(N, D, H, W, Cout, Cin, 2)) and \
+        bool(lib.kmh_conv3d_wgrad_bf_sparse_ok(N, D, H, W, Cin, Cout, 2))
+
+
 def _blocked_kind(t) -> int:
     """Layout of a gradient tensor handed from one operator's backward to the next (_handoff.py: "layout"): 0 = (N,D,H,W,C);
-    1 = fp32 channel-blocked; 2 = pre-split records.  1 and 2 are both "blocked"; a consumer must know which."""
+    1 = fp32 channel-blocked; 2 = pre-split records; 3 = the pooled gradient (N,D/2,H/2,W/2,C) standing, with the operator's
+    winner bytes, for its scatter.  1 and 2 are both "blocked"; a consumer must know which."""
     return peek(t, "layout") or 0
 
 
@@ -634,7 +674,7 @@ class _SingleConvGCR(torch.autograd.Function):
         expect(dy, "lazy_gn", dy_lazy, "the first encoder block's pending GroupNorm backward", "KEYMORPH_NO_LAZY_FIRST")
         lazy_tag = peek(dy, "lazy_gn")
         dy = _prep(dy)
-        dy_split = False
+        dy_split = dy_sparse = False
         if ctx.pool:
             # the pooled output's gradient -> the full-resolution one through the winners recorded by the epilogue
             # (the pooling layer's backward, kmh_maxpool3d_bwd), channel-blocked when the gradient kernels take it so
@@ -642,7 +682,16 @@ class _SingleConvGCR(torch.autograd.Function):
             dy_split = (dy_blocked and not odd and _needs_range_scales() and pool_grad_split_ok(N, D, H, W, Cin, Cout)
                         and not (Cin == 1 and not ctx.needs_input_grad[0])
                         and not ctx.dgrad_terms)            # (a bf16x6 data gradient reads the fp32 operand)
-            if dy_split:
+            dy_sparse = dy_split and pool_grad_sparse_ok(N, D, H, W, Cin, Cout)
+            if dy_sparse:
+                # ... or not scattered at all: one non-zero per window and channel, so both gradient kernels take the pooled
+                # tensor with the winner bytes and build in their own staging the words the records would give them
+                # (kmh_conv3d_fwd_bf_sparse, kmh_conv3d_wgrad_bf_sparse): no pass, no full-resolution tensor, same bits
+                sd_in = sd_in if sd_in is not None else absmax_scale(dy)
+                full = dy.detach()                 # (another tensor object: the tags below are this hand-off's own)
+                SPLIT_STATS["handoffs"] += 1
+                SPARSE_STATS["handoffs"] += 1
+            elif dy_split:
                 # ... and PRE-SPLIT into the fp16 hi / lo records both gradient kernels multiply with: a scatter keeps the
                 # range scale of the pooled gradient, so the split can be done by the pass that writes the tensor and the
                 # z-paired data gradient copies fragments instead of converting them (kmh_maxpool3d_bwd_split)
@@ -660,15 +709,15 @@ class _SingleConvGCR(torch.autograd.Function):
             _tag_grad_scale(full, sd_in)       # scattering moves values: the bound of the pooled gradient holds
             dy = full
             if dy_blocked:
-                attach(dy, "layout", 2 if dy_split else 1)
+                attach(dy, "layout", 3 if dy_sparse else (2 if dy_split else 1))
                 BLOCKED_STATS["handoffs"] += 1
         # ReLU backward (dz = dy * [y > 0]) is fused into the loaders of both gradient kernels -- and is
         # skipped altogether when every consumer of y already returned a gradient masked by (y > 0)
         # (a downstream SingleConv with x_from_relu, possibly through max-pool / upsample+concat).
-        kind = 2 if dy_split else int(dy_blocked)
+        kind = 3 if dy_sparse else (2 if dy_split else int(dy_blocked))
         if _blocked_kind(dy) != kind:
             raise RuntimeError("keymorph_amd: gradient layout kind %d where %d was expected (1 = fp32 channel-blocked, 2 = pre-split"
-                               " records); a hook or an in-place op between two operators changed the tensor" % (_blocked_kind(dy), kind))
+                               " records, 3 = pooled + winners); a hook or an in-place op between two operators changed the tensor" % (_blocked_kind(dy), kind))
         ymask = None if dy_premasked else y
         first = Cin == 1 and not ctx.needs_input_grad[0] and (Cout <= 16 or CONV_MODE != "f32")
         dscale = (grad_scale(dy) if (_needs_range_scales() and not (first and Cout <= 16)) else None)
@@ -685,7 +734,8 @@ class _SingleConvGCR(torch.autograd.Function):
         fold = need_dxn and ctx.needs_input_grad[3] and conv_emits_stats() and not _off("KEYMORPH_NO_STATS_FOLD")
         bhat = torch.zeros((N, Cin), dtype=torch.float64, device=x.device) if fold else None
         dw = (conv3_wgrad(x, scale, shift, dy, N, D, H, W, Cin, Cout, False, dzmask=ymask, xscale=ctx.ascale,
-                          dscale=dscale, dz_blocked=kind, fold=(weight, bhat) if fold else None)
+                          dscale=dscale, dz_blocked=kind, fold=(weight, bhat) if fold else None,
+                          winners=ctx.pool_arg if dy_sparse else None)
               if ctx.needs_input_grad[3] else None)
         dx = dgamma = dbeta = None
         if need_dxn:
@@ -695,7 +745,8 @@ class _SingleConvGCR(torch.autograd.Function):
             dxn = conv3_raw(dy, None, None,
                             pack_weight(weight, True, None if ctx.dgrad_terms else getattr(ctx, "wscale", None), terms=ctx.dgrad_terms),
                             None, N, D, H, W, Cout, Cin, False, False,
-                            mask=ymask, ascale=dscale, in_blocked=kind, stats_out=dstats)
+                            mask=ymask, ascale=dscale, in_blocked=kind, stats_out=dstats,
+                            winners=ctx.pool_arg if dy_sparse else None)
             sc2 = torch.zeros(2, dtype=torch.float32, device=x.device) if (_needs_range_scales() and ctx.needs_input_grad[0]) else None
             c123, dgamma, dbeta = _gn_bwd_coeffs(lambda flag: channel_stats(dxn, x, N, V, Cin, only_if=flag), gamma, mr,
                                                  N, Cin, G, V, fold=(dstats, bhat, beta) if fold else None)

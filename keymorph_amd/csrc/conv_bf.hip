@@ -11,7 +11,7 @@
 //                                                 NT = 32-wide cout tiles per wave, MR = rows per wave, ZP = z-paired N
 //                                                 tile for Cout <= 16, ZT = output-plane pairs per brick
 //   conv3_fwd_g_kernel<NT, ZP, POOL>             the same on big launches: persistent workgroups, LDS-DMA staging, eight waves
-//   conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, AMP> one wave per SIMD, hand-counted waits (audited: keymorph_amd/isa_audit.py)
+//   conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, AMP, SPARSE> one wave per SIMD, hand-counted waits (audited: keymorph_amd/isa_audit.py)
 //   pack_weight_bf_kernel<TERMS>
 //
 // Forward: same brick / wave decomposition as conv.hip (32x8x2 output voxels per 4-wave workgroup, 4 rows x NT
@@ -893,6 +893,7 @@ static_assert(GPL <= S_PLANE && GTZ == 4 && GTY == S_MR, "wave = plane, 8 rows")
 // the step's issue plan, swept and settled:
 constexpr int S_ILR = 12, S_ILRN = 2;                                 // gaps that take LDS reads, reads per such gap
 constexpr int S_ILV0 = 3, S_ILV1 = 3, S_ILV2 = 2;                     // first gap that takes conversion VALU; VALU per gap on the 32-wide / 64-wide tile
+constexpr int SPS_BA = 6;                                             // SPARSE: drains at steps 0, 6, 12; cell c is expanded in steps 6 + 6 c .. + 5
 constexpr int SP_BA = 9, SP_PS = 5;                                   // SPLIT: request distance = drain period; the stage's 16 DMA pieces go out in
                                                                       // steps 0 .. SP_PS - 1 (flat over the valid range: profiles/r5g_zp_split_ring_sweep.txt)
 // What is still a compile-time switch is built by something: KMH_S_CW=0 KMH_S_DEEP=0 is the library's fall-back when the ISA audit
@@ -931,7 +932,20 @@ constexpr int SP_BA = 9, SP_PS = 5;                                   // SPLIT: 
 // first-max rule, the same winners, the same outputs bit for bit.  What it buys:
 // the plain one-wave kernel spends 38 % of a two-chunk 16 -> 32 brick in its epilogue storing 128 KB (cycle stamps, r5a); the
 // pooled tensor is 16 KB.
-template <int NT, bool ZP = false, bool SPLIT = false, bool POOL = false, bool AMP = false>
+// SPARSE (round 7; with SPLIT, z-paired): the operand is the gradient of a tensor that feeds only a 2 x 2 x 2 max-pool, handed over
+// as the POOLED gradient x = (N, D/2, H/2, W/2, Cin) fp32 with its winner bytes (`pool_arg`: one per pooled element, 0..7 =
+// (dz, dy, dx)) -- one non-zero per window and channel, so the dense record tensor (7/8 zeros) and the pass that writes it are
+// gone.  With even brick origins the 34 x 10 x 6 halo is covered by 18 x 6 x 4 = 432 pooled cells per chunk: a lane owns two
+// (lanes 176 .. 255 own one and the 8 slots past the halo).  Per stage it loads each cell's 32 bytes of gradient and 8 winner
+// bytes in step 0 (landed by the drain at the head of step BA), forms fmaf(v, S, 0) and split8<2> ONCE per cell, writes zero
+// records to the cell's children and then each channel's hi / lo term, 2 bytes each, into the record of the child its winner byte
+// names -- six steps per cell from step BA on, dealt over the MFMA gaps.  A child outside the halo (border cells keep >= 1 child inside per axis)
+// is redirected to a sibling inside and its value zeroed; so are the children of cells outside the volume.  The winner byte
+// enters an address only as (byte & 7) through a per-lane table of the cell's OWN eight record offsets (two v_perm_b32 look-ups
+// serve four channels), so no byte value can write outside the cell's records; a byte > 7 cannot come from the pooling kernels.
+// Same words in the same slots as SPLIT: bit-identical.  The table (sOff) holds per lane and cell the eight record offsets, the
+// validity bytes, the cell's base slot and its global element offset.
+template <int NT, bool ZP = false, bool SPLIT = false, bool POOL = false, bool AMP = false, bool SPARSE = false>
 __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16x8* __restrict__ wp, const float* __restrict__ bias, float* __restrict__ y, int D, int H, int W, int Cin,
@@ -942,6 +956,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   constexpr int TERMS = 2, MR = ZP ? 4 : S_MR, NST = ZP ? NSTEP_Z : NSTEP;
   static_assert(!ZP || NT == 1, "z-paired tiles are for Cout <= 16");
   static_assert(!POOL || (NT == 1 && !ZP), "the pooling epilogue is built for the 32-wide tile");
+  static_assert(!SPARSE || (SPLIT && ZP && !AMP && TX % 2 == 0 && GTY % 2 == 0 && GTZ % 2 == 0), "pooled operand: the pre-split arm, even brick origins");
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
   int* sOff = reinterpret_cast<int*>(gsm + 2 * S_BUF_BYTES);
   float* sCoef = reinterpret_cast<float*>(gsm + 2 * S_BUF_BYTES + S_OFF_BYTES);
@@ -995,7 +1010,44 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
     const int x0 = it.bx * TX, y0 = it.by * GTY, z0 = it.bz * GTZ;
     int t_ = tid;
     asm volatile("" : "+v"(t_));
-    if constexpr (SPLIT) {
+    if constexpr (SPARSE) {
+      // per cell c of the lane: row 2 c = the 16-bit byte offsets of its 8 children's records from the cell's base slot (children
+      // outside the halo: a sibling's), row 2 c + 1 = {validity bytes of children 0-3, 4-7, base slot (bytes), global element offset}
+      typedef unsigned sp_u4 __attribute__((ext_vector_type(4)));
+      sp_u4* tab = reinterpret_cast<sp_u4*>(sOff);
+      constexpr int CX = HX / 2 + 1, CY = GHY / 2 + 1, CZ = GHZ / 2 + 1;      // 18 x 6 x 4 cells
+      static_assert(2 * S_TPB >= CX * CY * CZ && 4 * S_TPB * 16 <= S_OFF_BYTES, "two cells per lane, four table rows");
+      const int Wp = W >> 1, Hp = H >> 1, Dp = D >> 1;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int cell = c * S_TPB + t_;
+        const bool real = cell < CX * CY * CZ;
+        const int cl = real ? cell : 0;
+        const int cxl = cl % CX, cyl = (cl / CX) % CY, czl = cl / (CX * CY);
+        const int cgx = (x0 >> 1) - 1 + cxl, cgy = (y0 >> 1) - 1 + cyl, cgz = (z0 >> 1) - 1 + czl;
+        const bool in = real && ((unsigned)cgx < (unsigned)Wp) && ((unsigned)cgy < (unsigned)Hp) && ((unsigned)cgz < (unsigned)Dp);
+        const unsigned goff = in ? (unsigned)(((cgz * Hp + cgy) * Wp + cgx) * Cin) : 0u;
+        const bool ex = cxl == 0 || cxl == CX - 1, ey = cyl == 0 || cyl == CY - 1, ez = czl == 0 || czl == CZ - 1;
+        const int bx = cxl == 0 ? 0 : 2 * cxl - 1, by = cyl == 0 ? 0 : 2 * cyl - 1, bz = czl == 0 ? 0 : 2 * czl - 1;
+        unsigned B = (unsigned)(((bz * GHY + by) * HX + bx) * 16);
+        unsigned sx = ex ? 0u : 16u, sy = ey ? 0u : (unsigned)(HX * 16), sz = ez ? 0u : (unsigned)(GHY * HX * 16);
+        if (!real) { B = (unsigned)((GPL + (t_ & 7)) * 16); sx = sy = sz = 0u; }      // the slots past the halo: zeros
+        unsigned d[8], vl[2] = {0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
+          d[k] = dx * sx + dy * sy + dz * sz;
+          // the child outside the halo of a border cell: dx = 0 of the first column, dx = 1 of the last one (y, z alike)
+          const bool ok = in && !(ex && dx == (cxl == 0 ? 0 : 1)) && !(ey && dy == (cyl == 0 ? 0 : 1)) && !(ez && dz == (czl == 0 ? 0 : 1));
+          vl[k >> 2] |= (ok ? 0xffu : 0u) << (8 * (k & 3));
+        }
+        const sp_u4 r0 = {d[0] | (d[1] << 16), d[2] | (d[3] << 16), d[4] | (d[5] << 16), d[6] | (d[7] << 16)};
+        const sp_u4 r1 = {vl[0], vl[1], B, goff};
+        tab[(2 * c) * S_TPB + t_] = r0;                     // read back by this thread only
+        tab[(2 * c + 1) * S_TPB + t_] = r1;
+      }
+      return 0u;
+    } else if constexpr (SPLIT) {
       // one record offset (floats) per halo voxel of this lane: slot r * 256 + tid; padding voxels and the 8 slots past the
       // halo point at the plane's zero record
 #pragma unroll
@@ -1123,6 +1175,99 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
     unsigned char* dst = gsm + buf * S_BUF_BYTES + ((p & 1) * S_PLANE + (p >> 1) * S_TPB + wv * 64) * 16;
     __builtin_amdgcn_global_load_lds((kmh_glb_ptr)src, (kmh_lds_ptr)dst, 16, 0, 0);
   };
+  // SPARSE: the loads of a stage's two cells and the four parts of one cell's expansion into stage buffer `buf`, one part per
+  // step.  The loads are inline asm like the fragment loads (for compiler-visible ones hipcc adds counted waits of its own that do
+  // not count the asm loads queued behind them: vmcnt(1) / vmcnt(0) in the middle of the expansion steps, i.e. a wait for the
+  // fragments requested at that step's head); they are consumed behind the FULL drain at the head of step BA, followed by sp_tie
+  // (no hand-counted wait), and the ISA audit covers their destinations like every other asm load's.  The 8 winner bytes are a
+  // plain load whose first use is sp_tie: the compiler's own wait for it falls on the drain.
+  typedef unsigned sp_u4 __attribute__((ext_vector_type(4)));
+  const sp_u4* const spTab = reinterpret_cast<const sp_u4*>(sOff);
+  kmh_f4 spg[2][2];                                        // [cell][half]: 8 gradient values
+  typedef unsigned sp_u2 __attribute__((ext_vector_type(2)));
+  sp_u2 spw[2];                                            // [cell]: 8 winner bytes
+  unsigned sph[4], spl[4], spP[4], spM[4], spB = 0;        // the cell in expansion: hi / lo words, record offsets, masks (per channel pair)
+  auto sp_issue = [&](int n, int ch) {
+    const long long cells = vox >> 3;
+    const float* gb = x + ((long long)n * cells) * Cin + ch * KC;
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(pool_arg) + ((long long)n * cells) * Cin + ch * KC;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const unsigned goff = spTab[(2 * c + 1) * S_TPB + tid].w;
+      const float* gp = gb + goff;
+      const unsigned char* wq = wb + goff;
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(spg[c][0]) : "v"(gp) : "memory");
+      asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(spg[c][1]) : "v"(gp) : "memory");
+      spw[c] = *reinterpret_cast<const sp_u2*>(wq);      // (compiler-visible: its first use is sp_tie, right behind the drain)
+    }
+  };
+  auto sp_tie = [&]() {                                    // (after a full drain: the registers are defined HERE)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      asm volatile("" : "+v"(spg[c][0]));
+      asm volatile("" : "+v"(spg[c][1]));
+      asm volatile("" : "+v"(spw[c]));
+    }
+  };
+  constexpr int SP_PARTS = 6;
+  auto sp_part = [&](int c, int part, int buf) {
+    unsigned char* const img = gsm + buf * S_BUF_BYTES;
+    constexpr int LO = S_PLANE * 16;                       // the lo plane of a stage buffer
+    if (part == 0) {
+      // split once per cell; zero records to all children (a redirected child's lands on its sibling's), the hi plane
+      const sp_u4 r0 = spTab[(2 * c) * S_TPB + tid], r1 = spTab[(2 * c + 1) * S_TPB + tid];
+      const float raw[8] = {spg[c][0].x, spg[c][0].y, spg[c][0].z, spg[c][0].w, spg[c][1].x, spg[c][1].y, spg[c][1].z, spg[c][1].w};
+      float val[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) val[j] = fmaf(raw[j], sA, 0.f);
+      bf16x8 parts[TERMS];
+      split8<TERMS>(val, parts);
+      const sp_u4 hb = __builtin_bit_cast(sp_u4, parts[0]), lb = __builtin_bit_cast(sp_u4, parts[1]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { sph[q] = hb[q]; spl[q] = lb[q]; }
+      spB = r1.z;
+      const sp_u4 z4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const unsigned dk = (k & 1) ? r0[k >> 1] >> 16 : r0[k >> 1] & 0xffffu;
+        *reinterpret_cast<sp_u4*>(img + spB + dk) = z4;
+      }
+    } else if (part == 1) {
+      // the lo plane's zero records; record offsets and validity of every channel's winner: byte tables of the 8 children, looked
+      // up four channels at a time
+      const sp_u4 r0 = spTab[(2 * c) * S_TPB + tid], r1 = spTab[(2 * c + 1) * S_TPB + tid];
+      const sp_u4 z4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const unsigned dk = (k & 1) ? r0[k >> 1] >> 16 : r0[k >> 1] & 0xffffu;
+        *reinterpret_cast<sp_u4*>(img + spB + dk + LO) = z4;
+      }
+      const unsigned tl0 = __builtin_amdgcn_perm(r0[1], r0[0], 0x06040200u), th0 = __builtin_amdgcn_perm(r0[1], r0[0], 0x07050301u);
+      const unsigned tl1 = __builtin_amdgcn_perm(r0[3], r0[2], 0x06040200u), th1 = __builtin_amdgcn_perm(r0[3], r0[2], 0x07050301u);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned k4 = spw[c][h] & 0x07070707u;      // selector bytes 0..7: children 0-3 from the first table word, 4-7 from the second
+        const unsigned lo4 = __builtin_amdgcn_perm(tl1, tl0, k4), hi4 = __builtin_amdgcn_perm(th1, th0, k4);
+        const unsigned m4 = __builtin_amdgcn_perm(r1.y, r1.x, k4);
+        spP[2 * h] = __builtin_amdgcn_perm(hi4, lo4, 0x05010400u);          // channels 4 h, 4 h + 1: 16-bit offsets
+        spP[2 * h + 1] = __builtin_amdgcn_perm(hi4, lo4, 0x07030602u);      // channels 4 h + 2, 4 h + 3
+        spM[2 * h] = __builtin_amdgcn_perm(0u, m4, 0x01010000u);            // 16-bit masks
+        spM[2 * h + 1] = __builtin_amdgcn_perm(0u, m4, 0x03030202u);
+      }
+    } else {
+      // two channels: each one's hi / lo term into the record of its winner (zero where that child or the cell is outside)
+      {
+        const int q = part - 2;
+        const unsigned hv = sph[q] & spM[q], lv = spl[q] & spM[q];
+        unsigned char* const p0 = img + spB + (spP[q] & 0xffffu) + 4 * q;
+        unsigned char* const p1 = img + spB + (spP[q] >> 16) + 4 * q + 2;
+        *reinterpret_cast<unsigned short*>(p0) = (unsigned short)hv;
+        *reinterpret_cast<unsigned short*>(p0 + LO) = (unsigned short)lv;
+        *reinterpret_cast<unsigned short*>(p1) = (unsigned short)(hv >> 16);
+        *reinterpret_cast<unsigned short*>(p1 + LO) = (unsigned short)(lv >> 16);
+      }
+    }
+  };
   // B fragments straight from L2 through a two-slot register ring that runs THROUGH the stage boundaries: the fragments of step
   // s + 1 are requested at the HEAD of step s (into the slot step s - 1 has just finished issuing from), so they have a whole
   // step -- ~1.5k cycles, several L2 round trips -- to land.  Without CW (KMH_S_CW=0, round 4) every step opens with a plain
@@ -1133,7 +1278,9 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   // halo, issued in the steps right after a drain, then have BA - SP_PS + 1 or more steps (thousands of cycles) to come in
   // from HBM before anything waits for them -- a drain at every step head would expose that latency 18 times per chunk.
   constexpr int BD = (SPLIT || DEEP) ? NST : 2;        // ring slots
-  constexpr int BA = SPLIT ? SP_BA : (DEEP ? 7 : 1);     // request distance = drain period (steps)
+  // (SPARSE: no DMA pieces whose HBM latency the drain period must cover; a shorter period leaves 12 steps behind the first drain
+  // after the cells' loads to deal the expansion over)
+  constexpr int BA = SPARSE ? SPS_BA : (SPLIT ? SP_BA : (DEEP ? 7 : 1));     // request distance = drain period (steps)
   static_assert(NST % BD == 0 && (SPLIT || DEEP || BD == 2), "the ring slot of a step must not depend on the stage");
   static_assert(!SPLIT || (NST % BA == 0 && SP_PS < BA && NT == 1), "drains at steps 0, BA, ...; pieces land before the next one");
   auto piece_beg = [](int s) -> int { return s >= SP_PS ? S_NLD : (S_NLD * s) / SP_PS; };      // pieces of steps 0 .. SP_PS - 1
@@ -1200,7 +1347,15 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
   // prologue: the first stage's halo, fetched and converted with nothing to hide behind
   unsigned cv_in = fill_offsets(cur);
   unsigned cv_brick_next = 0u;                             // the NEXT brick's bits, formed with its table in its predecessor's last stage
-  if constexpr (SPLIT) {
+  if constexpr (SPARSE) {
+    sp_issue(cur.n, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    sp_tie();
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int part = 0; part < SP_PARTS; ++part) sp_part(c, part, 0);
+  } else if constexpr (SPLIT) {
 #pragma unroll
     for (int p = 0; p < S_NLD; ++p) dma_piece(cur.n, 0, 0, p, sOff[(p >> 1) * S_TPB + tid]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1277,6 +1432,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
           b_tie(s % BD);
           if (s >= 1 + CD && s < 9 + CD) raw_tie((s - 1 - CD) % RQ);
         } else if (!(SPLIT || DEEP) || (s % BA == 0 && !(s == 0 && ch == 0))) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (SPARSE) { if (s == BA) sp_tie(); }      // the two cells requested in step 0 have landed
         if (s + BA < NST) b_issue((s + BA) % BD);             // the fragments of step s + BA ...
         else {                                                // ... or of step s + BA - NST of the next stage
           if (s + BA == NST) o0 = (long long)nch * TERMS * term_stride + lh * CoutP + co0n + li;
@@ -1288,7 +1444,11 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
         // first replaces the offset table and the inside bits by the next brick's (~400 VALU: fillers here, 3k cycles at the
         // stage top before)
         if (s == 0 && last_ch && more) { cv_brick_next = fill_offsets(nxt); cv_next = cv_brick_next; }
-        if constexpr (SPLIT) {
+        if constexpr (SPARSE) {
+          // the next stage's two cells: requested in step 0 (after the table has been replaced), landed by the drain at the head
+          // of step BA, expanded one part per step after it
+          if (s == 0) sp_issue(nn, nch);
+        } else if constexpr (SPLIT) {
           // this step's share of the next stage's 16 pieces (step 0: after the offset table has been replaced)
 #pragma unroll
           for (int p = piece_beg(s); p < piece_beg(s + 1); ++p) dma_piece(nn, nch, pb ^ 1, p, sOff[(p >> 1) * S_TPB + tid]);
@@ -1303,6 +1463,9 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
 #pragma unroll
             for (int q = 0; q < TERMS; ++q) a[(s + 1) & 1][m][q] = sIn[q * S_PLANE + ab + arow(m)];
         }
+        constexpr int SP0 = BA;                              // SPARSE: first expansion step
+        static_assert(!SPARSE || SP0 + 2 * SP_PARTS <= NST, "two cells' expansion steps behind the drain");
+        if (SPARSE && s >= SP0 && s < SP0 + 2 * SP_PARTS) sp_part((s - SP0) / SP_PARTS, (s - SP0) % SP_PARTS, pb ^ 1);
         // the next stage's voxel s - 2 (requested in the last step)
         if (!SPLIT && s >= 1 + CD && s < 9 + CD) convert1(nch, cv_next, pb ^ 1, s - 1 - CD, rawq[(s - 1 - CD) % RQ][0], rawq[(s - 1 - CD) % RQ][1]);
         // term-major over the 8 x NT accumulators: per accumulator the order of conv3_fwd_bf_kernel (smallest terms first)
@@ -1325,6 +1488,11 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   // one MFMA
             if (k < S_ILR) __builtin_amdgcn_sched_group_barrier(0x100, S_ILRN, 0);              // LDS reads: early gaps
             if (k == 1) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                       // the raw voxel's two loads
+            if (SPARSE && s == 0 && k >= 2 && k < 5) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);      // the two cells' six loads
+            if (SPARSE && s >= SP0 && s < SP0 + 2 * SP_PARTS) {      // an expansion part: its VALU over all gaps, its LDS writes behind the reads
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+              if (k >= 6) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+            }
             if (conv_step && k >= S_ILV0) __builtin_amdgcn_sched_group_barrier(0x002, NT == 2 ? S_ILV2 : S_ILV1, 0);
           }
         } else {      // the "reads first" arrangement the dealt one replaced: built only by the ISA audit's positive control
@@ -1713,6 +1881,35 @@ KMH_API int kmh_conv3d_fwd_bf_split_ok(int N, int D, int H, int W, int Cin, int 
   if (N <= 0 || terms != 2 || (Cin & 7) || (Cout & 3)) return 0;
   if ((long long)D * H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 31)) return 0;          // 32-bit element offsets
   return 1;
+}
+
+/* The convolution of a tensor that is the backward of a 2 x 2 x 2 max-pool, WITHOUT forming it: xp (N, D/2, H/2, W/2, Cin) fp32 is
+ * the pooled gradient, `winners` (same shape, one byte per element) the window index 0..7 = (dz, dy, dx) that
+ * kmh_conv3d_fwd_bf_pool / kmh_maxpool3d_fwd record; the operand stands for the (N, D, H, W, Cin) tensor with xp at each window's
+ * winner and zeros elsewhere (what kmh_maxpool3d_bwd_split writes as records, in_blocked == 2 of kmh_conv3d_fwd_bf).  y and
+ * stats_out are bit-identical to that route.  Served (kmh_conv3d_fwd_bf_sparse_ok): where the pre-split operand is, with even
+ * D, H, W, in the f16x3 arithmetic (terms == 2; not use_amp's terms == 1).  The answer is for the SHAPE: it does not depend on the
+ * dispatch mode.  Other arguments as kmh_conv3d_fwd_bf. */
+KMH_API int kmh_conv3d_fwd_bf_sparse_ok(int N, int D, int H, int W, int Cin, int Cout, int terms) {
+  if (terms != 2 || ((D | H | W) & 1) || D < 2 || H < 2 || W < 2) return 0;
+  return kmh_conv3d_fwd_bf_split_ok(N, D, H, W, Cin, Cout, terms);
+}
+
+KMH_API int kmh_conv3d_fwd_bf_sparse(const float* xp, const unsigned char* winners, const void* packed, const float* bias,
+                                     float* y, int N, int D, int H, int W, int Cin, int Cout, int relu_out, int terms,
+                                     const float* ascale, const float* wscale, void* stats_ws, double* stats_out, void* stream) {
+  if (!kmh_conv3d_fwd_bf_sparse_ok(N, D, H, W, Cin, Cout, terms) || !xp || !winners || !ascale || !wscale) return -22;
+  if (((uintptr_t)xp & 15) || ((uintptr_t)winners & 7)) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  if (int e = allow_lds(conv3_fwd_s_kernel<1, true, true, false, false, true>, S_LDS_BYTES)) return e;
+  const PersistentGrid g = persistent_grid(N, D, H, W, 1);
+  long long* trace = trace_begin(s);
+  conv3_fwd_s_kernel<1, true, true, false, false, true><<<dim3(g.wgs), S_TPB, S_LDS_BYTES, s>>>(
+      xp, nullptr, nullptr, (const bf16x8*)packed, bias, y, D, H, W, Cin, Cout, cout_pad(Cout), 0, relu_out, g.tx, g.ty, g.tz, g.tzp,
+      ascale, wscale, stats_out ? (double*)stats_ws : nullptr, 0, nullptr, g.total, N, trace,
+      reinterpret_cast<unsigned*>(const_cast<unsigned char*>(winners)));
+  trace_end(trace, s, "KMH_G_TRACE fwd_s SPARSE Cin=%d Cout=%d D=%d:", Cin, Cout, D);
+  return finish_stats((double*)stats_ws, g.tx * g.ty * g.tz, Cout, N, stats_out, s);
 }
 
 /* Convolution + ReLU + MaxPool3d(2) in one launch, for an encoder block whose output feeds ONLY the next level's pooling

@@ -8,7 +8,7 @@
 // ds_read_b128.  M rows are packed (tap, ci) with ci tiles of <= 16 channels (2 taps per 32-row tile),
 // tiles dealt to the 8 waves exactly like the fp32 kernel; per-wave partial slabs, deterministic reduce.
 // Kernels in this file:
-//   conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, AMP>   producer / consumer waves over a ring of z planes (the default)
+//   conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, AMP, DSPARSE>   producer / consumer waves over a ring of z planes (the default)
 //   conv3_wgrad_bf_kernel<NT, TERMS>                          single-role (bf16x6, odd channel counts, huge volumes)
 //   wgrad_bf_reduce_kernel, wgrad_bf_reduce_fold_kernel
 #include <cstdlib>
@@ -491,7 +491,13 @@ __device__ __forceinline__ void ws_barrier() {
 // 8 fp16 lo terms of fmaf(dz, S, 0) -- so a producer item (4 channels of two x neighbours) is four 8-byte loads and eight
 // 16-bit packs instead of two 16-byte loads, eight multiplies and four split_pair sequences: the same words in the same
 // transposed image, bit-identical sums.
-template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false, bool AMP = false>
+// DSPARSE (round 7): dz is the POOLED gradient (N, D/2, H/2, W/2, Cout) fp32 and `dzmask` its winner bytes (one per pooled element,
+// 0..7 = (dz, dy, dx)) -- the gradient of a convolution whose output feeds only a 2 x 2 x 2 max-pool has one non-zero per window and
+// channel, so the dense tensor (7/8 zeros) is never formed.  The same item (4 channels of two x neighbours = the two dx children of
+// one pooled cell at the item's (dz, dy)) is one 16-byte load of the cell's channel quad, one 4-byte load of its winners,
+// fmaf(v, S, 0) and split_pair on 4 values; a child gets the words when the winner byte names it (compare-select, never an
+// address term) and zeros otherwise: the words DSPLIT builds, bit for bit.  Even D, H, W.
+template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false, bool AMP = false, bool DSPARSE = false>
 __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_wgrad_ws_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
     const float* __restrict__ dz, const float* __restrict__ dzmask, float* __restrict__ partial, int N, int D,
@@ -581,7 +587,9 @@ __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_
       // pre-split records: planes of V + 1 records of 8 floats; the quad's four fp16 hi terms are floats (quad in chunk) / 2 ..
       // + 1 of the record, its lo terms 4 floats further
       if (DSPLIT) di_q4[i] = on ? ((co0 + 4 * q) >> 3) * ((D * H * W + 1) * 8) + (((4 * q) & 7) >> 1) : 0;
+      if (DSPARSE) di_q4[i] = on ? co0 + 4 * q : 0;        // pooled cells are (.., Cout): the quad inside the cell
     }
+    static_assert(!(DSPLIT && DSPARSE), "one operand source");
     const int dstride = (dz_blocked || DSPLIT) ? 8 : Cout;      // floats between x neighbours of one dz quad
     const float sX = xscale ? xscale[0] : 1.f, sD = dscale ? dscale[0] : 1.f;
     float4 px[XI][2], pd[DI][2], pm[MASK ? DI : 1][2];
@@ -592,7 +600,8 @@ __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_
     auto issue = [&](int n, int x0, int y0, int z0, bool col_start) {
       const int xn_sets = col_start ? XI : XH;             // uniform: a column's first brick fetches all four planes
       const float* xn = x + (long long)n * D * H * W * Cin + ci0;
-      const float* dn = DSPLIT ? dz + (long long)n * (Cout >> 3) * ((long long)D * H * W + 1) * 8
+      const float* dn = DSPARSE ? dz + (long long)n * (D >> 1) * (H >> 1) * (W >> 1) * Cout
+                      : DSPLIT ? dz + (long long)n * (Cout >> 3) * ((long long)D * H * W + 1) * 8
                                : dz + (long long)n * D * H * W * Cout + (dz_blocked ? 0 : co0);
       const float* mn = MASK ? dzmask + (long long)n * D * H * W * Cout + co0 : nullptr;
       // all element offsets first, then the loads back to back
@@ -613,6 +622,8 @@ __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_
         const unsigned row = __umul24(__umul24(gz, H) + gy, W);
         dO[i][0] = __umul24(row + min(gx0, W - 1), dstride) + di_q4[i];
         dO[i][1] = __umul24(row + min(gx0 + 1, W - 1), dstride) + di_q4[i];
+        if (DSPARSE)       // the pooled cell of the pair (clamped into the volume as above); [1] is not used
+          dO[i][0] = __umul24(__umul24(__umul24(gz >> 1, H >> 1) + (gy >> 1), W >> 1) + (min(gx0, W - 1) >> 1), Cout) + di_q4[i];
       }
 #pragma unroll
       for (int i = 0; i < XI; ++i) {
@@ -622,6 +633,12 @@ __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_
       }
 #pragma unroll
       for (int i = 0; i < DI; ++i) {
+        if constexpr (DSPARSE) {       // the cell's channel quad and its four winner bytes (the same element offset, in bytes)
+          pd[i][0] = *reinterpret_cast<const float4*>(dn + dO[i][0]);
+          const unsigned char* wn = reinterpret_cast<const unsigned char*>(dzmask) + (long long)n * (D >> 1) * (H >> 1) * (W >> 1) * Cout;
+          pd[i][1] = make_float4(__uint_as_float(*reinterpret_cast<const unsigned*>(wn + dO[i][0])), 0.f, 0.f, 0.f);
+          continue;
+        }
         if constexpr (DSPLIT) {        // (hi.x, hi.y, lo.x, lo.y): 4 + 4 fp16 terms of the voxel's channel quad
           const float2 h0 = *reinterpret_cast<const float2*>(dn + dO[i][0]), l0 = *reinterpret_cast<const float2*>(dn + dO[i][0] + 4);
           const float2 h1 = *reinterpret_cast<const float2*>(dn + dO[i][1]), l1 = *reinterpret_cast<const float2*>(dn + dO[i][1] + 4);
@@ -692,6 +709,28 @@ __global__ __launch_bounds__(64 * (WS_CONS + PW), (PW == 8 ? 4 : 3)) void conv3_
       for (int i = 0; i < DI; ++i) {
         const int gz = z0 + (di_pk[i] & 15), gy = y0 + ((di_pk[i] >> 4) & 15), gx0 = x0 + ((di_pk[i] >> 8) & 255);
         const bool rok = (di_pk[i] >> 30) && gy < H && gz < D;
+        if constexpr (DSPARSE) {
+          static_assert(!DSPARSE || (TERMS == 2 && !MASK), "the pooled operand is split into fp16 hi / lo, already masked");
+          const bool k0 = rok && gx0 < W;                    // even W: both x neighbours are inside, or neither
+          const unsigned kk = ((di_pk[i] & 1) << 2) | (((di_pk[i] >> 4) & 1) << 1);      // window index of the dx = 0 child (even brick origins)
+          const unsigned wb = __float_as_uint(pd[i][1].x);
+          unsigned w01[2], w23[2];
+          split_pair<2>(fmaf(pd[i][0].x, sD, 0.f), fmaf(pd[i][0].y, sD, 0.f), w01);
+          split_pair<2>(fmaf(pd[i][0].z, sD, 0.f), fmaf(pd[i][0].w, sD, 0.f), w23);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const unsigned a = (wb >> (8 * j)) & 255u;
+            const bool m0 = k0 && a == kk, m1 = k0 && a == kk + 1;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              const unsigned pr = j < 2 ? w01[t] : w23[t];
+              const unsigned h16 = (j & 1) ? pr >> 16 : pr & 0xffffu;
+              const unsigned wd = m0 ? h16 : (m1 ? h16 << 16 : 0u);
+              *reinterpret_cast<unsigned*>(sDT + t * CO * DPLANE + di_lds[i] + j * DPLANE) = wd;
+            }
+          }
+          continue;
+        }
         if constexpr (DSPLIT) {
           // words of the transposed image: (voxel 0 | voxel 1 << 16) per channel and term
           static_assert(TERMS == 2 && !MASK, "pre-split records are fp16 hi / lo, already masked");
@@ -910,16 +949,16 @@ static int launch_wgrad_bf(const WgradBfPlan& p, const float* x, const float* sc
   return KMH_LAUNCH_CHECK();
 }
 
-template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false>
+template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false, bool DSPARSE = false>
 static int launch_wgrad_ws(const WgradBfPlan& p, const float* x, const float* scale, const float* shift,
                            const float* dz, const float* dzmask, float* ws, int N, int D, int H, int W, int Cin,
                            int Cout, int relu_in, const float* xscale, const float* dscale, int dz_blocked, hipStream_t s) {
   const size_t lds = p.lds_ws;                             // ring x image, two dz stages, the coefficient table
-  hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT>,
+  hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, false, DSPARSE>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
   dim3 g(p.ci_tiles * p.co_groups * p.nslab);
-  if constexpr (!MASK && PW == 8) {
+  if constexpr (!MASK && PW == 8 && !DSPARSE) {      // (the pooled operand is not served under use_amp)
     if (kmh_amp_enabled()) {
       e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -930,7 +969,7 @@ static int launch_wgrad_ws(const WgradBfPlan& p, const float* x, const float* sc
       return KMH_LAUNCH_CHECK();
     }
   }
-  conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT><<<g, 64 * (WS_CONS + PW), lds, s>>>(x, scale, shift, dz, dzmask, ws, N, D, H, W, Cin, Cout,
+  conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, false, DSPARSE><<<g, 64 * (WS_CONS + PW), lds, s>>>(x, scale, shift, dz, dzmask, ws, N, D, H, W, Cin, Cout,
                                                                relu_in, p.CP, p.MT, p.TG, p.KS, p.ci_tiles, p.tiles_x,
                                                                p.tiles_y, p.tiles_z, p.bricks_per_slab, p.nslab, xscale,
                                                                dscale, dz_blocked);
@@ -961,15 +1000,27 @@ KMH_API size_t kmh_conv3d_wgrad_bf_ws_bytes(int N, int D, int H, int W, int Cin,
 /* append_ones != 0: x has Cin-1 real channels in memory and a virtual last channel that reads 1 inside the volume
  * (0 in the zero padding); dw then has Cin logical input channels.  With scale == NULL this yields, per output
  * channel and tap, R = sum_v x[v+tap] dz[v] and S = sum_v [v+tap inside] dz[v] in ONE pass. */
-KMH_API int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float* shift, const float* dz,
-                                const float* dzmask, float* dw, int N, int D, int H, int W, int Cin, int Cout,
-                                int relu_in, int accumulate, int terms, int append_ones, const float* xscale,
-                                const float* dscale, int dz_blocked, const float* w_fold, double* bhat, void* ws,
-                                void* stream) {
+/* 1 when kmh_conv3d_wgrad_bf_sparse serves this shape: the wave-specialised kernel's preconditions (as for a channel-blocked dz),
+ * even D, H, W, the f16x3 arithmetic (terms == 2; not the one-product use_amp arithmetic, terms == 1). */
+KMH_API int kmh_conv3d_wgrad_bf_sparse_ok(int N, int D, int H, int W, int Cin, int Cout, int terms) {
+  if (N <= 0 || terms != 2 || ((D | H | W) & 1) || D < 2 || H < 2 || W < 2) return 0;
+  return kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, terms);
+}
+
+/* dz_kind: 0 dense, 1 channel-blocked, 2 pre-split records, 3 = dz is the POOLED gradient (N, D/2, H/2, W/2, Cout) and `winners`
+ * its window indices (kmh_conv3d_wgrad_bf_sparse) */
+static int wgrad_bf_impl(const float* x, const float* scale, const float* shift, const float* dz,
+                         const float* dzmask, float* dw, int N, int D, int H, int W, int Cin, int Cout,
+                         int relu_in, int accumulate, int terms, int append_ones, const float* xscale,
+                         const float* dscale, int dz_blocked, const unsigned char* winners, const float* w_fold, double* bhat,
+                         void* ws, void* stream) {
   KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   hipStream_t s = (hipStream_t)stream;
   if ((w_fold == nullptr) != (bhat == nullptr)) return -22;
   const WgradBfPlan p = wgrad_bf_plan(N, D, H, W, Cin, Cout, terms);
+  if (dz_blocked == 3 && (kmh_amp_enabled() || dzmask || append_ones || !winners || !xscale || !dscale ||
+                          ((uintptr_t)dz & 15) || ((uintptr_t)winners & 3) || !kmh_conv3d_wgrad_bf_sparse_ok(N, D, H, W, Cin, Cout, terms)))
+    return -22;
   if (dz_blocked && (dzmask || !kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, terms))) return -22;
   if (dz_blocked == 2 && (terms != 2 || ((long long)D * H * W + 1) * (Cout > Cin ? Cout : Cin) >= (1ll << 31))) return -22;
   if (p.MT > p.TG * MTWB || (terms != 2 && terms != 3)) return -22;
@@ -982,7 +1033,12 @@ KMH_API int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float*
   const bool ws_ok = wgrad_ws_ok(p, D, H, W, Cin, Cout, terms) && !append_ones;
 #define KMH_WS_CALL(NT_, M_, PW_) launch_wgrad_ws<NT_, 2, M_, PW_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, dz_blocked, s)
   static const int pw = getenv("KEYMORPH_WGRAD_PRODUCERS") ? atoi(getenv("KEYMORPH_WGRAD_PRODUCERS")) : 8;
-  if (ws_ok && dz_blocked == 2) {      // pre-split dz records (kmh_maxpool3d_bwd_split)
+  if (dz_blocked == 3) {               // the pooled gradient and its winner bytes (the winners travel in the mask operand's place)
+    if (!ws_ok) return -22;
+    const float* wn = reinterpret_cast<const float*>(winners);
+    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s)
+                   : launch_wgrad_ws<1, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s);
+  } else if (ws_ok && dz_blocked == 2) {      // pre-split dz records (kmh_maxpool3d_bwd_split)
     rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s)
                    : launch_wgrad_ws<1, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s);
   } else if (ws_ok) {
@@ -1006,4 +1062,27 @@ KMH_API int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float*
   else
     wgrad_bf_reduce_kernel<<<nb, 256, 0, s>>>((const float*)ws, p.nslab * p.KS, Cin, Cout, dw, accumulate, xscale, dscale);
   return KMH_LAUNCH_CHECK();
+}
+
+KMH_API int kmh_conv3d_wgrad_bf(const float* x, const float* scale, const float* shift, const float* dz,
+                                const float* dzmask, float* dw, int N, int D, int H, int W, int Cin, int Cout,
+                                int relu_in, int accumulate, int terms, int append_ones, const float* xscale,
+                                const float* dscale, int dz_blocked, const float* w_fold, double* bhat, void* ws,
+                                void* stream) {
+  if (dz_blocked < 0 || dz_blocked > 2) return -22;
+  return wgrad_bf_impl(x, scale, shift, dz, dzmask, dw, N, D, H, W, Cin, Cout, relu_in, accumulate, terms, append_ones, xscale,
+                       dscale, dz_blocked, nullptr, w_fold, bhat, ws, stream);
+}
+
+/* The weight gradient of a convolution whose output feeds only a 2 x 2 x 2 max-pool, from the POOLED gradient: dzp (N, D/2, H/2,
+ * W/2, Cout) fp32 and `winners` (same shape, one byte per element: the window index 0..7 = (dz, dy, dx) kmh_conv3d_fwd_bf_pool /
+ * kmh_maxpool3d_fwd record) stand for the dense gradient with one non-zero per window and channel, which is never formed.
+ * Bit-identical to kmh_conv3d_wgrad_bf on the scattered tensor (dz_blocked 1 or 2).  Other arguments as kmh_conv3d_wgrad_bf;
+ * served where kmh_conv3d_wgrad_bf_sparse_ok says so, -22 elsewhere. */
+KMH_API int kmh_conv3d_wgrad_bf_sparse(const float* x, const float* scale, const float* shift, const float* dzp,
+                                       const unsigned char* winners, float* dw, int N, int D, int H, int W, int Cin, int Cout,
+                                       int relu_in, int accumulate, int terms, const float* xscale, const float* dscale,
+                                       const float* w_fold, double* bhat, void* ws, void* stream) {
+  return wgrad_bf_impl(x, scale, shift, dzp, nullptr, dw, N, D, H, W, Cin, Cout, relu_in, accumulate, terms, 0, xscale, dscale, 3,
+                       winners, w_fold, bhat, ws, stream);
 }

@@ -1,6 +1,8 @@
 """Run one conv layer's forward / dgrad / wgrad a few times (for rocprofv3 --pmc runs).
 usage: prof_layer.py D Cin Cout [mode] [nomask] ; KMH_LIB=<path> loads another build of the library (A/B runs);
-KMH_TIME=1 also prints the event-timed average of each of the three launches."""
+KMH_TIME=1 also prints the event-timed average of each of the three launches; KMH_POOLGRAD=1 (f16x3, even D, Cout % 8 == 0) then
+runs and times the weight gradient of a pooled layer's three operand formats: the gradient scattered by the pooling backward as
+fp32, as pre-split records (kmh_maxpool3d_bwd_split), and not at all (the pooled gradient + winner bytes)."""
 import os, sys, torch
 sys.path.insert(0, '.')
 if os.environ.get("KMH_LIB"):
@@ -53,4 +55,27 @@ if os.environ.get("KMH_TIME"):
         e1.record()
         torch.cuda.synchronize()
         print(f"{name}: {e0.elapsed_time(e1) / 10:.3f} ms")
+if os.environ.get("KMH_POOLGRAD"):
+    from keymorph_amd import _lib
+    from keymorph_amd.ops import _p, _stream, check
+    lib = _lib.load()
+    V = D ** 3
+    dyp = torch.randn(N, D // 2, D // 2, D // 2, Cout, device=dev)
+    arg = torch.randint(0, 8, dyp.shape, dtype=torch.uint8, device=dev)
+    dps = B.absmax_scale(dyp)
+    rec = torch.empty(N, Cout // 8, V + 1, 8, device=dev)
+    check(lib.kmh_maxpool3d_bwd_split(_p(arg), _p(dyp), _p(dps), _p(rec), N, D, D, D, Cout, _stream()), "split")
+    arms = [("pre-split records", lambda: B.conv3_wgrad(x, sc, sh, rec, N, D, D, D, Cin, Cout, False, xscale=asc, dscale=dps, dz_blocked=2)),
+            ("pooled + winners", lambda: B.conv3_wgrad(x, sc, sh, dyp, N, D, D, D, Cin, Cout, False, xscale=asc, dscale=dps, dz_blocked=3, winners=arg))]
+    print("wgrad pooled + winners vs pre-split records: bit-identical =", bool(torch.equal(arms[0][1](), arms[1][1]())))
+    for name, f in arms:
+        for _ in range(3):
+            f()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            f()
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"wgrad {Cin} -> {Cout}, {name}: {e0.elapsed_time(e1) / 10:.3f} ms")
 print("done")

@@ -1,6 +1,7 @@
-"""The 32 -> 16 data gradient behind the 256^3 pooling (N = 2): pooling backward + convolution, three operand formats.
+"""The 32 -> 16 data gradient behind the 256^3 pooling (N = 2): pooling backward + convolution, four operand formats.
   blocked fp32 scatter -> conv3_fwd_g_kernel<1,true> (round 4) | KEYMORPH_FWD_S=3: conv3_fwd_s_kernel<1,true>
   pre-split records    -> conv3_fwd_s_kernel<1,true,true> (round 5)
+  pooled + winners     -> conv3_fwd_s_kernel<1,true,true,false,false,true> (round 7): no pooling backward at all
 usage: prof_split.py [D]   (KMH_G_TRACE=1: cycle stamps on stderr)"""
 import os, sys, torch
 sys.path.insert(0, '.')
@@ -30,7 +31,9 @@ pb = lambda: check(lib.kmh_maxpool3d_bwd(None, _p(arg), _p(dy), None, 0, _p(bloc
 ps = lambda: check(lib.kmh_maxpool3d_bwd_split(_p(arg), _p(dy), _p(sc), _p(rec), N, D, D, D, Cin, _stream()), "s")
 cb = lambda: B.conv3_raw(blocked, None, None, pk, None, N, D, D, D, Cin, Cout, False, False, ascale=sc, in_blocked=True)
 cs = lambda: B.conv3_raw(rec, None, None, pk, None, N, D, D, D, Cin, Cout, False, False, ascale=sc, in_blocked=2)
+cp = lambda: B.conv3_raw(dy, None, None, pk, None, N, D, D, D, Cin, Cout, False, False, ascale=sc, in_blocked=3, winners=arg)
 print(f"pool backward: blocked fp32 {t(pb):.3f} ms, pre-split {t(ps):.3f} ms")
 yb, ys = cb(), cs()
-print("bit-identical:", bool(torch.equal(yb, ys)), " max|y|", float(ys.abs().max()))
-print(f"data gradient 32 -> 16 at {N} x {D}^3: blocked fp32 {t(cb):.3f} ms, pre-split {t(cs):.3f} ms")
+yp = cp()
+print("bit-identical:", bool(torch.equal(yb, ys)), bool(torch.equal(yp, ys)), " max|y|", float(ys.abs().max()))
+print(f"data gradient 32 -> 16 at {N} x {D}^3: blocked fp32 {t(cb):.3f} ms, pre-split {t(cs):.3f} ms, pooled + winners {t(cp):.3f} ms")
