@@ -955,6 +955,7 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
     unsigned* __restrict__ pool_arg = nullptr) {
   constexpr int TERMS = 2, MR = ZP ? 4 : S_MR, NST = ZP ? NSTEP_Z : NSTEP;
   static_assert(!ZP || NT == 1, "z-paired tiles are for Cout <= 16");
+  static_assert(ZP == SPLIT, "the z-paired tile is launched on pre-split operands only (fp32 operands: conv3_fwd_g_kernel<1, true>)");
   static_assert(!POOL || (NT == 1 && !ZP), "the pooling epilogue is built for the 32-wide tile");
   static_assert(!SPARSE || (SPLIT && ZP && !AMP && TX % 2 == 0 && GTY % 2 == 0 && GTZ % 2 == 0), "pooled operand: the pre-split arm, even brick origins");
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
@@ -1698,17 +1699,6 @@ __global__ __launch_bounds__(S_TPB, 1) void conv3_fwd_s_kernel(
 }
 
 }  // namespace
-// use_amp per call (common.h): the state is the calling thread's, set for the duration of ONE entry-point call.  Defined here for
-// the library: called by KmhAmpCall and the launchers of this file, conv_up2.hip, conv_wgrad.hip and headcom.hip.
-static thread_local bool t_amp_call = false;
-bool kmh_amp_enabled() { return t_amp_call; }
-bool kmh_amp_call_begin(int* terms) {
-  const bool prev = t_amp_call;
-  t_amp_call = (*terms == 1);
-  if (*terms == 1) *terms = 2;
-  return prev;
-}
-void kmh_amp_call_end(bool prev) { t_amp_call = prev; }
 static inline bool use_zpair(int Cout) { return Cout <= 16; }      // the z-paired N tile (and weight packing) serves these
 
 KMH_API size_t kmh_conv3d_pack_bf_bytes(int Cout, int Cin, int transposed, int terms) {
@@ -1803,8 +1793,9 @@ static int launch_fwd_g(const float* x, const float* scale, const float* shift, 
   return finish_stats(stats_ws, g.tx * g.ty * g.tz, Cout, N, stats_out, s);
 }
 
+// amp: the entry point's use_amp flag (common.h: kmh_take_amp) -- the hi x hi instance of the same tile
 template <int NT, bool ZP = false, bool SPLIT = false, bool POOL = false>
-static int launch_fwd_s(const float* x, const float* scale, const float* shift, const bf16x8* wp, const float* bias, float* y,
+static int launch_fwd_s(bool amp, const float* x, const float* scale, const float* shift, const bf16x8* wp, const float* bias, float* y,
                         int N, int D, int H, int W, int Cin, int Cout, int CoutP, int relu_in, int relu_out,
                         const float* ascale, const float* wscale, double* stats_ws, double* stats_out, hipStream_t s,
                         int in_blocked, const float* addend, unsigned* pool_arg = nullptr) {
@@ -1813,7 +1804,7 @@ static int launch_fwd_s(const float* x, const float* scale, const float* shift, 
   long long* trace = trace_begin(s);
 #define KMH_S_ARGS x, scale, shift, wp, bias, y, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, g.tx, g.ty, g.tz, g.tzp, ascale, wscale, \
                    stats_out ? stats_ws : nullptr, in_blocked, addend, g.total, N, trace, pool_arg
-  if (kmh_amp_enabled()) {
+  if (amp) {
     if (int e = allow_lds(conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true>, S_LDS_BYTES)) return e;
     conv3_fwd_s_kernel<NT, ZP, SPLIT, POOL, true><<<dim3(g.wgs), S_TPB, S_LDS_BYTES, s>>>(KMH_S_ARGS);
   } else
@@ -1836,6 +1827,14 @@ static int fwd_g_mode() {
     g_fwd_g_mode.store(m, std::memory_order_relaxed);
   }
   return m;
+}
+
+// KEYMORPH_FWD_S=0 (read once per process): conv3_fwd_g_kernel, the eight-wave kernel, also where conv3_fwd_s_kernel would
+// serve the 64-wide and 32-wide tiles and the pooling epilogue -- bit-identical outputs, kept as the parity arm of
+// tests/test_conv_dispatch_gpu.py.  Any other value, or none: the one-wave kernel.
+static bool fwd_s_on() {
+  static const bool on = !(getenv("KEYMORPH_FWD_S") && atoi(getenv("KEYMORPH_FWD_S")) == 0);
+  return on;
 }
 
 static bool fwd_g_ok(bool mask, bool addend, int N, int D, int H, int W, int Cin, int Cout, int terms) {
@@ -1927,14 +1926,12 @@ KMH_API int kmh_conv3d_fwd_bf_pool(const float* x, const float* scale, const flo
                                    unsigned char* arg, int N, int D, int H, int W, int Cin, int Cout, int relu_in,
                                    int terms, const float* ascale, const float* wscale, void* stats_ws, double* stats_out,
                                    int in_blocked, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if (!kmh_conv3d_fwd_bf_pool_ok(N, D, H, W, Cin, Cout, terms) || !ascale || !wscale || !yp || !arg) return -22;
   if (((uintptr_t)yp & 15) || ((uintptr_t)arg & 3)) return -22;
-  // the one-wave kernel's pooling epilogue (KEYMORPH_FWD_S=0 or KEYMORPH_POOL_G=1: the eight-wave kernel's, the A/B arm;
-  // same pooled values and winners)
-  static const bool pool_g = (getenv("KEYMORPH_FWD_S") && atoi(getenv("KEYMORPH_FWD_S")) == 0) || getenv("KEYMORPH_POOL_G") != nullptr;
-  if (!pool_g && Cin <= S_COEF)
-    return launch_fwd_s<1, false, false, true>(x, scale, shift, (const bf16x8*)packed, nullptr, yp, N, D, H, W, Cin, Cout,
+  // the one-wave kernel's pooling epilogue (KEYMORPH_FWD_S=0: the eight-wave kernel's; same pooled values and winners)
+  if (fwd_s_on() && Cin <= S_COEF)
+    return launch_fwd_s<1, false, false, true>(amp, x, scale, shift, (const bf16x8*)packed, nullptr, yp, N, D, H, W, Cin, Cout,
                                                cout_pad(Cout), relu_in, 1, ascale, wscale, (double*)stats_ws, stats_out,
                                                (hipStream_t)stream, in_blocked, nullptr, (unsigned*)arg);
   return launch_fwd_g<1, false, true>(x, scale, shift, (const bf16x8*)packed, nullptr, yp, N, D, H, W, Cin, Cout,
@@ -1942,8 +1939,7 @@ KMH_API int kmh_conv3d_fwd_bf_pool(const float* x, const float* scale, const flo
                                       (hipStream_t)stream, in_blocked, nullptr, (unsigned*)arg);
 }
 
-static inline int fwd_bf_rows(int Cout, int rows_per_wave) {   // smallest brick height in y of the variants that may run
-  (void)rows_per_wave;
+static inline int fwd_bf_rows(int Cout) {   // smallest brick height in y of the variants that may run
   return use_zpair(Cout) ? 8 : 4;
 }
 
@@ -1951,7 +1947,7 @@ static inline int fwd_bf_rows(int Cout, int rows_per_wave) {   // smallest brick
  * forward: pack(w, Cout, Cin, 0); data gradient: pack(w, Cout_w, Cin_w, 1) and call with Cin = Cout_w, Cout = Cin_w.
  * rows_per_wave: 4 (32x8x2 brick) or 2 (32x4x2 brick, higher occupancy); 0 = library default. */
 KMH_API size_t kmh_conv3d_fwd_bf_stats_ws_bytes(int N, int D, int H, int W, int Cout, int rows_per_wave) {
-  return (size_t)N * ceil_div(W, TX) * ceil_div(H, fwd_bf_rows(Cout, rows_per_wave)) * ceil_div(D, TZ) * Cout * 2 *
+  return (size_t)N * ceil_div(W, TX) * ceil_div(H, fwd_bf_rows(Cout)) * ceil_div(D, TZ) * Cout * 2 *
          sizeof(double);
 }
 
@@ -1966,7 +1962,7 @@ KMH_API int kmh_conv3d_fwd_bf(const float* x, const float* scale, const float* s
                               int Cout, int relu_in, int relu_out, int terms, int rows_per_wave, const float* ascale,
                               const float* wscale, void* stats_ws, double* stats_out, int in_blocked,
                               const float* addend, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   const int CoutP = cout_pad(Cout);
   hipStream_t s = (hipStream_t)stream;
   const bf16x8* wp = (const bf16x8*)packed;
@@ -1979,26 +1975,22 @@ KMH_API int kmh_conv3d_fwd_bf(const float* x, const float* scale, const float* s
   if (in_blocked == 2) {      // pre-split input: see kmh_conv3d_fwd_bf_split_ok
     if (!kmh_conv3d_fwd_bf_split_ok(N, D, H, W, Cin, Cout, terms) || scale || shift || relu_in || addend || !ascale || !wscale)
       return -22;
-    return launch_fwd_s<1, true, true>(x, nullptr, nullptr, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, 0, relu_out, ascale, wscale,
+    return launch_fwd_s<1, true, true>(amp, x, nullptr, nullptr, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, 0, relu_out, ascale, wscale,
                                        (double*)stats_ws, stats_out, s, 2, nullptr);
   }
   if (terms == 2 && (!ascale || !wscale)) return -22;       // fp16 split without range scaling is not accurate
   // deep (32 x 8 x 4) bricks for the z-paired (Cout <= 16) launches on big volumes: less halo traffic, twice the B
   // reuse: +5 % on the 256^3 32->16 data gradient.  (The NT = 1, 4-rows-per-wave variant spills with 128 accumulator
   // registers plus 8 staging descriptors and is 4 % slower: not instantiated.)
-  static const bool no_deep = getenv("KEYMORPH_FWD_NO_DEEP") != nullptr;     // A/B measurements only
-  const bool deep = !no_deep && terms == 2 && Cout <= 32 && D >= 16 && (long long)D * H * W >= (1ll << 21);
+  const bool deep = terms == 2 && Cout <= 32 && D >= 16 && (long long)D * H * W >= (1ll << 21);
   if (fwd_g_ok(mask != nullptr, addend != nullptr, N, D, H, W, Cin, Cout, terms)) {
-    // the one-wave-per-SIMD kernel takes the 64-wide tile and the plain 32-wide one (KEYMORPH_FWD_S=1: only the 64-wide; 3: the
-    // z-paired tile too -- bit-identical, 3.7 % faster alone at 2 x 256^3 and flat inside the step, so not the default;
-    // 0: conv3_fwd_g_kernel for all of them, the A/B arm)
-    static const int fwd_s = getenv("KEYMORPH_FWD_S") ? atoi(getenv("KEYMORPH_FWD_S")) : 2;
-    if (fwd_s >= 3 && Cin <= S_COEF && use_zpair(Cout) && !addend)
-      return launch_fwd_s<1, true>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
+    // the one-wave-per-SIMD kernel takes the 64-wide tile and the plain 32-wide one, the eight-wave kernel the z-paired tile
+    // (the one-wave z-paired tile on fp32 operands was bit-identical, 3.7 % faster alone at 2 x 256^3 and flat inside the step:
+    // retired); KEYMORPH_FWD_S=0: conv3_fwd_g_kernel for all of them
     if (use_zpair(Cout)) return launch_fwd_g<1, true>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
-    if (fwd_s && Cin <= S_COEF && !use_zpair(Cout)) {
-      if (Cout > 32) return launch_fwd_s<2>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
-      if (fwd_s >= 2) return launch_fwd_s<1>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
+    if (fwd_s_on() && Cin <= S_COEF) {
+      if (Cout > 32) return launch_fwd_s<2>(amp, x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
+      return launch_fwd_s<1>(amp, x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
     }
     if (Cout > 32) return launch_fwd_g<2, false>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);
     return launch_fwd_g<1, false>(x, scale, shift, wp, bias, y, N, D, H, W, Cin, Cout, CoutP, relu_in, relu_out, ascale, wscale, (double*)stats_ws, stats_out, s, in_blocked, addend);

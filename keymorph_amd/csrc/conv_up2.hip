@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256, 3) void up2_wgrad_gemm_kernel(const float* __r
   // The column tiles of one (row tile, K slab) read the SAME rows of A.  Dealt round-robin over the XCDs, every XCD's L2 fetched
   // them for itself: 14.75 GB per launch for 7.25 GB of G at 64^3 x 128 x 1728 (PMC), and the launch ran at the HBM rate of THAT.
   // With one contiguous item range per XCD (xcd_remap) the tiles of a slab sit on one XCD and walk the slab together: A comes
-  // from HBM once.  (KEYMORPH_UP2_GEMM_NO_XCD=1: the round-robin order, for A/B runs.)
+  // from HBM once.  (xcd == 0: the round-robin order; the host always passes 1.)
   int item = xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
   const int tn = item % ntn; item /= ntn;
   const int tm = item % ntm;
@@ -809,8 +809,9 @@ __global__ __launch_bounds__(MODE ? 512 : 256, MODE ? 1 : 2) void up2_wgrad_fold
 
 }  // namespace
 
-// XCD-aware workgroup order of the two weight-gradient kernels (KEYMORPH_UP2_GEMM_NO_XCD: off, A/B runs; read once per process)
-static int up2_xcd() { static const int xcd = getenv("KEYMORPH_UP2_GEMM_NO_XCD") ? 0 : 1; return xcd; }
+// XCD-aware workgroup order of the two weight-gradient kernels: always on.  (The kernels keep the argument their retired A/B
+// switch fed; taking it out changes their code and wants a timing of its own.)
+constexpr int kUp2Xcd = 1;
 // C (N, per) = the sum of the ns partial slabs of every sample; returns the launch status
 static int up2_reduce(const void* ws, int ns, long long per, float* C, int N, hipStream_t s) {
   int nb = ceil_div(per, 256);
@@ -840,7 +841,7 @@ KMH_API size_t kmh_up2_wgrad_gemm_ws_bytes(int N, int V, int Cl, int J) {
 KMH_API int kmh_up2_wgrad_gemm(const float* A, const float* B, float* C, int N, int V, int Cl, int J, int terms,
                                const float* ascale, const float* bscale, const float* a_scale, const float* a_shift,
                                void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if ((Cl & 3) || (J & 3) || (terms != 2 && terms != 3) || (terms == 2 && (!ascale || !bscale)) || (!a_scale != !a_shift))
     return -22;
   int ks;
@@ -848,14 +849,13 @@ KMH_API int kmh_up2_wgrad_gemm(const float* A, const float* B, float* C, int N, 
   const int ntn = ceil_div(J, 128), ntm = ceil_div(Cl, 128);
   hipStream_t s = (hipStream_t)stream;
   dim3 g(ntn * ntm * ns, 1, N);
-  const int xcd = up2_xcd();
   if (terms == 2)
-    if (kmh_amp_enabled())
-      up2_wgrad_gemm_kernel<2, true><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
+    if (amp)
+      up2_wgrad_gemm_kernel<2, true><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, kUp2Xcd);
     else
-    up2_wgrad_gemm_kernel<2><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
+    up2_wgrad_gemm_kernel<2><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, kUp2Xcd);
   else
-    up2_wgrad_gemm_kernel<3><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, xcd);
+    up2_wgrad_gemm_kernel<3><<<g, 256, 0, s>>>(A, B, (float*)ws, V, Cl, J, ks, ntn, ntm, ascale, bscale, a_scale, a_shift, kUp2Xcd);
   return up2_reduce(ws, ns, (long long)Cl * J, C, N, s);
 }
 
@@ -903,13 +903,13 @@ KMH_API size_t kmh_up2_wgrad_fold_ws_bytes(int N, int Dl, int Hl, int Wl, int Cl
 template <bool AMP, int MODE>
 static int launch_up2_fold(dim3 g, hipStream_t s, const float* xl, const float* dz, float* ws, int Dl, int Hl, int Wl, int Cl, int Cout,
                            int kt, int tps, int ntm, int nto, const float* ascale, const float* dscale, const float* a_scale,
-                           const float* a_shift, int dz_blocked, int xcd, const float* zero16) {
+                           const float* a_shift, int dz_blocked, const float* zero16) {
   constexpr int lds = wf_lds_bytes<MODE>();
   hipError_t e = hipFuncSetAttribute((const void*)up2_wgrad_fold_kernel<AMP, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
   up2_wgrad_fold_kernel<AMP, MODE><<<g, MODE ? 512 : 256, lds, s>>>(xl, dz, ws, Dl, Hl, Wl, Cl, Cout, ceil_div(Wl, 4), ceil_div(Hl, 4),
                                                                   kt, tps, ntm, nto, ascale, dscale, a_scale, a_shift, dz_blocked,
-                                                                  xcd, zero16);
+                                                                  kUp2Xcd, zero16);
   return 0;
 }
 
@@ -920,7 +920,7 @@ static int launch_up2_fold(dim3 g, hipStream_t s, const float* xl, const float* 
 KMH_API int kmh_up2_wgrad_fold(const float* xl, const float* dz, float* C, int N, int Dl, int Hl, int Wl, int Cl, int Cout,
                                int terms, const float* ascale, const float* dscale, const float* a_scale, const float* a_shift,
                                int dz_blocked, void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: hi x hi only (use_amp), for this call
   if (!ws || ((uintptr_t)ws & 15) || !kmh_up2_wgrad_fold_ok(Cl, Cout, terms) || !ascale || !dscale || (!a_scale != !a_shift) || N <= 0 || N > 65535) return -22;
   int tps, kt;
   const int ns = up2_fold_slabs(N, Dl, Hl, Wl, Cl, Cout, &tps, &kt);
@@ -928,15 +928,13 @@ KMH_API int kmh_up2_wgrad_fold(const float* xl, const float* dz, float* C, int N
   const int nto = (Cout / 8) / (mode == 1 ? 2 : 1), ntm = ceil_div(Cl, 128) / (mode == 2 ? 2 : 1);      // as the grid sees them
   hipStream_t s = (hipStream_t)stream;
   dim3 g(nto * ntm * ns, 1, N);
-  const int xcd = up2_xcd();
   // 256 bytes of zeros behind the slabs: the LDS-DMA source of window voxels outside the volume.  From the caller's workspace,
   // zeroed on the caller's stream: no allocation, no host synchronisation, nothing process-wide (stream capture stays legal).
   const float* zero16 = (const float*)((const char*)ws + up2_fold_slab_bytes(N, Dl, Hl, Wl, Cl, Cout));
   if (hipMemsetAsync((void*)zero16, 0, 256, s) != hipSuccess) return -12;
-  const bool amp = kmh_amp_enabled();
   int rc;
 #define KMH_FOLD(A, M) launch_up2_fold<A, M>(g, s, xl, dz, (float*)ws, Dl, Hl, Wl, Cl, Cout, kt, tps, ntm, nto, ascale, dscale, \
-                                             a_scale, a_shift, dz_blocked, xcd, zero16)
+                                             a_scale, a_shift, dz_blocked, zero16)
   if (mode == 2) rc = amp ? KMH_FOLD(true, 2) : KMH_FOLD(false, 2);
   else if (mode == 1) rc = amp ? KMH_FOLD(true, 1) : KMH_FOLD(false, 1);
   else rc = amp ? KMH_FOLD(true, 0) : KMH_FOLD(false, 0);
@@ -972,7 +970,7 @@ KMH_API size_t kmh_conv3d_up2_dgrad_stats_ws_bytes(int N, int Dl, int Hl, int Wl
 KMH_API int kmh_conv3d_up2_dgrad(const float* dz, const void* packed, float* ds, int N, int Dl, int Hl, int Wl, int Cl,
                                  int Cout, int terms, const float* dscale, const float* wscale, void* stats_ws,
                                  double* stats_out, int in_blocked, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if ((terms != 2 && terms != 3) || (terms == 2 && (!dscale || !wscale)) || (stats_out && !stats_ws)) return -22;
   if (in_blocked && (Cout & 7)) return -22;               // whole 8-channel chunks
   const int CiP = (Cl + 127) & ~127;
@@ -981,7 +979,7 @@ KMH_API int kmh_conv3d_up2_dgrad(const float* dz, const void* packed, float* ds,
   hipStream_t s = (hipStream_t)stream;
   double* sp = stats_out ? (double*)stats_ws : nullptr;
   if (terms == 2)
-    if (kmh_amp_enabled())
+    if (amp)
       conv3_up2_dgrad_kernel<2, true><<<g, DUP_TPB, 0, s>>>(dz, (const bf16x8*)packed, ds, Dl, Hl, Wl, Cl, CiP, Cout, tx, ty, dscale, wscale, sp, in_blocked);
     else
     conv3_up2_dgrad_kernel<2><<<g, DUP_TPB, 0, s>>>(dz, (const bf16x8*)packed, ds, Dl, Hl, Wl, Cl, CiP, Cout, tx, ty, dscale, wscale, sp, in_blocked);
@@ -1018,7 +1016,7 @@ KMH_API int kmh_conv3d_up2_pack_weight(const float* w, void* packed, int Cout, i
 KMH_API int kmh_conv3d_up2_fwd(const float* xl, const float* scale, const float* shift, int Ctot, int cofs,
                                const void* packed, float* y, int N, int Dl, int Hl, int Wl, int Cl, int Cout, int terms,
                                const float* ascale, const float* wscale, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if ((Cl & 7) || (terms != 2 && terms != 3) || (terms == 2 && (!ascale || !wscale))) return -22;
   if ((long long)Dl * Hl * Wl * Cl >= (1ll << 31)) return -22;
   const int CoutP = cout_pad(Cout);
@@ -1026,7 +1024,7 @@ KMH_API int kmh_conv3d_up2_fwd(const float* xl, const float* scale, const float*
   dim3 g(tx * ty * Dl * ceil_div(Cout, 64), 1, N);
   hipStream_t s = (hipStream_t)stream;
   if (terms == 2)
-    if (kmh_amp_enabled())
+    if (amp)
       conv3_up2_fwd_kernel<2, true><<<g, UP_TPB, 0, s>>>(xl, scale, shift, Ctot, cofs, (const bf16x8*)packed, y, Dl, Hl, Wl, Cl,
                                                 Cout, CoutP, tx, ty, ascale, wscale);
     else

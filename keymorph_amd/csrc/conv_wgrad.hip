@@ -11,7 +11,6 @@
 //   conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, AMP, DSPARSE>   producer / consumer waves over a ring of z planes (the default)
 //   conv3_wgrad_bf_kernel<NT, TERMS>                          single-role (bf16x6, odd channel counts, huge volumes)
 //   wgrad_bf_reduce_kernel, wgrad_bf_reduce_fold_kernel
-#include <cstdlib>
 #include "conv_split.h"
 #include <type_traits>
 
@@ -952,14 +951,15 @@ static int launch_wgrad_bf(const WgradBfPlan& p, const float* x, const float* sc
 template <int NT, int TERMS, bool MASK, int PW, bool DSPLIT = false, bool DSPARSE = false>
 static int launch_wgrad_ws(const WgradBfPlan& p, const float* x, const float* scale, const float* shift,
                            const float* dz, const float* dzmask, float* ws, int N, int D, int H, int W, int Cin,
-                           int Cout, int relu_in, const float* xscale, const float* dscale, int dz_blocked, hipStream_t s) {
+                           int Cout, int relu_in, const float* xscale, const float* dscale, int dz_blocked, hipStream_t s,
+                           bool amp) {
   const size_t lds = p.lds_ws;                             // ring x image, two dz stages, the coefficient table
   hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, false, DSPARSE>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
   dim3 g(p.ci_tiles * p.co_groups * p.nslab);
   if constexpr (!MASK && PW == 8 && !DSPARSE) {      // (the pooled operand is not served under use_amp)
-    if (kmh_amp_enabled()) {
+    if (amp) {
       e = hipFuncSetAttribute((const void*)conv3_wgrad_ws_kernel<NT, TERMS, MASK, PW, DSPLIT, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return (int)e;
@@ -980,8 +980,7 @@ static int launch_wgrad_ws(const WgradBfPlan& p, const float* x, const float* sc
 
 // the wave-specialised kernel's preconditions (vector path of the f16x3 mode)
 static bool wgrad_ws_ok(const WgradBfPlan& p, int D, int H, int W, int Cin, int Cout, int terms) {
-  static const bool no_ws = getenv("KEYMORPH_WGRAD_NO_WS") != nullptr;     // A/B measurements only
-  return !no_ws && terms == 2 && p.CP >= 4 && (Cin & 3) == 0 && (Cout & 3) == 0 && p.lds_ws <= 160 * 1024 &&
+  return terms == 2 && p.CP >= 4 && (Cin & 3) == 0 && (Cout & 3) == 0 && p.lds_ws <= 160 * 1024 &&
          (long long)D * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31) &&
          (long long)D * H * W <= (1ll << 24);   // 24-bit multiply-adds index the voxels of one sample
 }
@@ -1014,11 +1013,11 @@ static int wgrad_bf_impl(const float* x, const float* scale, const float* shift,
                          int relu_in, int accumulate, int terms, int append_ones, const float* xscale,
                          const float* dscale, int dz_blocked, const unsigned char* winners, const float* w_fold, double* bhat,
                          void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   hipStream_t s = (hipStream_t)stream;
   if ((w_fold == nullptr) != (bhat == nullptr)) return -22;
   const WgradBfPlan p = wgrad_bf_plan(N, D, H, W, Cin, Cout, terms);
-  if (dz_blocked == 3 && (kmh_amp_enabled() || dzmask || append_ones || !winners || !xscale || !dscale ||
+  if (dz_blocked == 3 && (amp || dzmask || append_ones || !winners || !xscale || !dscale ||
                           ((uintptr_t)dz & 15) || ((uintptr_t)winners & 3) || !kmh_conv3d_wgrad_bf_sparse_ok(N, D, H, W, Cin, Cout, terms)))
     return -22;
   if (dz_blocked && (dzmask || !kmh_conv3d_wgrad_bf_blocked_ok(N, D, H, W, Cin, Cout, terms))) return -22;
@@ -1031,19 +1030,19 @@ static int wgrad_bf_impl(const float* x, const float* scale, const float* shift,
 #define KMH_WG_CALL(NT_, T_) launch_wgrad_bf<NT_, T_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, Cmem, ones_ch, xscale, dscale, s)
   // wave-specialised kernel (producer / consumer waves, double-buffered LDS): vector path of the f16x3 mode
   const bool ws_ok = wgrad_ws_ok(p, D, H, W, Cin, Cout, terms) && !append_ones;
-#define KMH_WS_CALL(NT_, M_, PW_) launch_wgrad_ws<NT_, 2, M_, PW_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, dz_blocked, s)
-  static const int pw = getenv("KEYMORPH_WGRAD_PRODUCERS") ? atoi(getenv("KEYMORPH_WGRAD_PRODUCERS")) : 8;
+  // (8 producer waves without a mask operand, 4 with one)
+#define KMH_WS_CALL(NT_, M_, PW_) launch_wgrad_ws<NT_, 2, M_, PW_>(p, x, scale, shift, dz, dzmask, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, dz_blocked, s, amp)
   if (dz_blocked == 3) {               // the pooled gradient and its winner bytes (the winners travel in the mask operand's place)
     if (!ws_ok) return -22;
     const float* wn = reinterpret_cast<const float*>(winners);
-    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s)
-                   : launch_wgrad_ws<1, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s);
+    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s, amp)
+                   : launch_wgrad_ws<1, 2, false, 8, false, true>(p, x, scale, shift, dz, wn, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s, amp);
   } else if (ws_ok && dz_blocked == 2) {      // pre-split dz records (kmh_maxpool3d_bwd_split)
-    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s)
-                   : launch_wgrad_ws<1, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s);
+    rc = p.NT == 2 ? launch_wgrad_ws<2, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s, amp)
+                   : launch_wgrad_ws<1, 2, false, 8, true>(p, x, scale, shift, dz, nullptr, (float*)ws, N, D, H, W, Cin, Cout, relu_in, xscale, dscale, 0, s, amp);
   } else if (ws_ok) {
-    if (p.NT == 2) rc = dzmask ? KMH_WS_CALL(2, true, 4) : (pw == 8 ? KMH_WS_CALL(2, false, 8) : KMH_WS_CALL(2, false, 4));
-    else rc = dzmask ? KMH_WS_CALL(1, true, 4) : (pw == 8 ? KMH_WS_CALL(1, false, 8) : KMH_WS_CALL(1, false, 4));
+    if (p.NT == 2) rc = dzmask ? KMH_WS_CALL(2, true, 4) : KMH_WS_CALL(2, false, 8);
+    else rc = dzmask ? KMH_WS_CALL(1, true, 4) : KMH_WS_CALL(1, false, 8);
   } else if (p.NT == 2) rc = terms == 2 ? KMH_WG_CALL(2, 2) : KMH_WG_CALL(2, 3);
   else rc = terms == 2 ? KMH_WG_CALL(1, 2) : KMH_WG_CALL(1, 3);
 #undef KMH_WS_CALL

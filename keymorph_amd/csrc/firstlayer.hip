@@ -9,7 +9,6 @@
 // register window (two x halves: 9 instead of 4.5 compute waves per 65 KB of LDS -- a 4-way split adds nothing):
 // per 4 voxels 2 x ds_read_b128 (the x row, and a TRANSPOSED dz row [co][x]) and 12 fp32 FMAs; S needs only the
 // row sum of dz and two end corrections.  Exact fp32, independent of the convolution arithmetic mode.
-#include <cstdlib>
 #include "common.h"
 #include "stats_final.h"
 
@@ -602,12 +601,11 @@ KMH_API int kmh_conv3d_first_layer_wgrad(const float* x, const float* dz, const 
   if (e != hipSuccess) return (int)e;
   const int yt = ceil_div(H, FL_YR);
   const int per = Cout * 54;
-  // matrix-core kernel (round 3) whenever its LDS image fits; KEYMORPH_FIRST_WGRAD_VALU=1 keeps the VALU kernel (A/B runs)
-  static const bool valu_only = getenv("KEYMORPH_FIRST_WGRAD_VALU") != nullptr;
+  // matrix-core kernel (round 3) whenever its LDS image fits, else the VALU kernel
   size_t ds_floats = (size_t)2 * WP * 16;
   if (ds_floats < 2 * 4 * 2 * 64 * 4) ds_floats = 2 * 4 * 2 * 64 * 4;          // room for the final reduction (16 KB of doubles)
   const size_t lds_m = ((size_t)3 * (FM_YR + 2) * XP + ds_floats + 2 * 4 * 16 + 2 * 2 * 16) * sizeof(float);
-  if (!valu_only && lds_m <= 160 * 1024 && FM_YR == FL_YR) {
+  if (lds_m <= 160 * 1024 && FM_YR == FL_YR) {
     hipError_t e2 = hipFuncSetAttribute((const void*)first_wgrad_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
     if (e2 != hipSuccess) return (int)e2;
     first_wgrad_mfma_kernel<<<dim3(yt, D, N), FM_TPB, lds_m, s>>>(x, dz, dzmask, (float*)ws, D, H, W, Cout, yt, c123);

@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256) void tps_assemble_kernel(const float* __restri
 
 // Blocked right-looking LU with partial pivoting, one workgroup per sample.
 // LDS: sP[m][NB+1] (panel, rows k0..n) then sU[NB][ncols] (U12 strip).
-template <int NB, bool MFMA64>
+template <int NB>
 __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aall, int* __restrict__ ipiv_all,
                                                         int* __restrict__ info_all, int n, int lda,
                                                         size_t a_stride, int retry_only = 0) {
@@ -592,11 +592,11 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
       __syncthreads();
       // 6. trailing update A22 -= L21 U12.
       // Round 3: on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), one 16 x 16 tile of A22 per wave and trip: the 4x4
-      // register tiles below read 8 doubles from LDS per 16 multiply-adds and were bound by exactly that (the panel
+      // register tiles of the VALU version (retired) read 8 doubles from LDS per 16 multiply-adds and were bound by exactly that (the panel
       // factorisation, which the round-2 experiments went after, is the smaller part); a matrix-core tile reads 2
       // per 16.  A / B operands: lane l holds L[r0 + (l & 15)][4 s + (l >> 4)] and U[4 s + (l >> 4)][c0 + (l & 15)];
       // result register q of lane l is row (l >> 4) + 4 q, column l & 15.
-      if (MFMA64) {
+      {
         typedef double kmh_d4 __attribute__((ext_vector_type(4)));
         const int t16 = (ncols + 15) / 16;
         const int li = lane & 15, lk = lane >> 4;
@@ -636,34 +636,6 @@ __global__ __launch_bounds__(LU_TPB) void tps_lu_kernel(double* __restrict__ Aal
             }
           }
         }
-      } else {
-      const int tr = (ncols + 3) / 4, tc = (ncols + 3) / 4;  // A22 is ncols x ncols (square)
-      for (int tile = tid; tile < tr * tc; tile += LU_TPB) {
-        const int r0 = (tile / tc) * 4, c0 = (tile % tc) * 4;
-        double acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-#pragma unroll 4
-        for (int k = 0; k < nb; ++k) {
-          double l[4], u[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) l[i] = (r0 + i < ncols) ? sP[(nb + r0 + i) * PS + k] : 0.0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) u[j] = (c0 + j < ncols) ? sU[k * n + c0 + j] : 0.0;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] += l[i] * u[j];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (r0 + i < ncols && c0 + j < ncols)
-              A[(size_t)rowmap[k0 + nb + r0 + i] * lda + k0 + nb + c0 + j] -= acc[i][j];
-      }
       }
     }
     __syncthreads();
@@ -1196,24 +1168,16 @@ static int launch_lu(const FitWs& f, int N, int n, hipStream_t s, int* used_clus
   *used_cluster = 0;
   const size_t lds = ((size_t)n * (NB + 1) + (size_t)NB * n) * sizeof(double) + (size_t)n * sizeof(int);   // + rowmap
   if (lds > 160 * 1024 - 1024) return -22;
-  static const bool valu_trailing = getenv("KEYMORPH_TPS_LU_VALU") != nullptr;      // A/B measurements only
-  if (valu_trailing) {
-    hipError_t e = hipFuncSetAttribute((const void*)tps_lu_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return (int)e;
-    tps_lu_kernel<NB, false><<<N, LU_TPB, lds, s>>>(f.A, f.ipiv, f.info, n, f.lda, f.a_stride);
-    return KMH_LAUNCH_CHECK();
-  }
   // cluster of G workgroups per system when the systems are large enough to pay for the hand-offs and every workgroup of the
-  // launch can be resident at once (one per CU: 136 KB of LDS): KEYMORPH_TPS_LU_CLUSTER=<G> (0 / 1 = one workgroup per system).
+  // launch can be resident at once (one per CU: 136 KB of LDS): at most LU_CLUSTER workgroups per system.
   // The workgroups synchronise through global counters inside an ORDINARY launch, so residency is a matter of the grid size:
   // the grid stays within HALF the device's compute units (queried, not assumed) and the occupancy query must admit the kernel
   // at all.  That leaves room for a neighbour on another stream, but proves nothing about CUs held by other processes or a CU
   // mask -- which is why every wait in the kernel is bounded and a fit that gave up (info = 2) is REDONE on the one-workgroup
   // kernel by the retry pass queued behind it (kmh_tps_fit_fwd): the caller never sees a poisoned result.
-  static const int genv = getenv("KEYMORPH_TPS_LU_CLUSTER") ? atoi(getenv("KEYMORPH_TPS_LU_CLUSTER")) : 8;
+  constexpr int LU_CLUSTER = 8;
   const int cus = device_cus();
-  int G = genv;
+  int G = LU_CLUSTER;
   while (G > 1 && (long long)N * G * 2 > cus) G >>= 1;
   if (G > 1 && n >= 128) {
     hipError_t e = hipFuncSetAttribute((const void*)tps_lu_cluster_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1230,10 +1194,10 @@ static int launch_lu(const FitWs& f, int N, int n, hipStream_t s, int* used_clus
       return KMH_LAUNCH_CHECK();
     }
   }
-  hipError_t e = hipFuncSetAttribute((const void*)tps_lu_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  hipError_t e = hipFuncSetAttribute((const void*)tps_lu_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return (int)e;
-  tps_lu_kernel<NB, true><<<N, LU_TPB, lds, s>>>(f.A, f.ipiv, f.info, n, f.lda, f.a_stride);
+  tps_lu_kernel<NB><<<N, LU_TPB, lds, s>>>(f.A, f.ipiv, f.info, n, f.lda, f.a_stride);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -1244,12 +1208,12 @@ static int launch_lu_retry(const FitWs& f, const float* ctrl, const float* lmbda
                            hipStream_t s) {
   const int n = T + 4;
   const size_t lds = ((size_t)n * (NB + 1) + (size_t)NB * n) * sizeof(double) + (size_t)n * sizeof(int);
-  hipError_t e = hipFuncSetAttribute((const void*)tps_lu_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  hipError_t e = hipFuncSetAttribute((const void*)tps_lu_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return (int)e;
   tps_assemble_kernel<<<dim3(ceil_div(n, 16), ceil_div(n, 16), N), 256, 0, s>>>(ctrl, lmbda, w, f.A, T, f.lda, f.a_stride,
                                                                              f.info);
-  tps_lu_kernel<NB, true><<<N, LU_TPB, lds, s>>>(f.A, f.ipiv, f.info, n, f.lda, f.a_stride, 1);
+  tps_lu_kernel<NB><<<N, LU_TPB, lds, s>>>(f.A, f.ipiv, f.info, n, f.lda, f.a_stride, 1);
   return KMH_LAUNCH_CHECK();
 }
 

@@ -11,7 +11,6 @@
 // TPS backward is the transposed reduction: each lane owns KPT keypoints (6 accumulators
 // each), voxels + their incoming gradient are staged through LDS and broadcast.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -501,13 +500,11 @@ KMH_API int kmh_tps_grid_fwd(const float* theta, const float* ctrl, float* out, 
   const long long nvox = (long long)D * H * W;
   const size_t lds = (size_t)T * 2 * sizeof(float4);
   if (lds > 64 * 1024) return -22;
-  static const bool no_rowq = getenv("KMH_TPS_NO_ROWQ") != nullptr;       // A/B switch (tools/prof_tps.py)
-  static const int tv = getenv("KMH_TPS_TV") ? atoi(getenv("KMH_TPS_TV")) : 8;
   const dim3 g(ceil_div(nvox, (long long)TPB * VPT), N);
-  if (W % 8 == 0 && !no_rowq && tv == 8)
+  if (W % 8 == 0)
     tps_eval_fwd_kernel<false, true, 8><<<dim3(ceil_div(nvox, (long long)TPB * 8), N), TPB, lds, (hipStream_t)stream>>>(
         theta, ctrl, nullptr, out, T, D, H, W, nvox);
-  else if (W % VPT == 0 && !no_rowq)
+  else if (W % VPT == 0)
     tps_eval_fwd_kernel<false, true><<<g, TPB, lds, (hipStream_t)stream>>>(theta, ctrl, nullptr, out, T, D, H, W, nvox);
   else
     tps_eval_fwd_kernel<false, false><<<g, TPB, lds, (hipStream_t)stream>>>(theta, ctrl, nullptr, out, T, D, H, W, nvox);
@@ -545,8 +542,7 @@ KMH_API int kmh_tps_grid_bwd(const float* dgrid, const float* theta, const float
   size_t off = ((size_t)N * nchunk * T * 6 * sizeof(float) + 255) & ~(size_t)255;
   double* affp = (double*)((char*)ws + off);
   float* dmat = (float*)((char*)affp + (size_t)N * AFF_BWD_BLOCKS * 12 * sizeof(double));
-  static const bool no_rowq = getenv("KMH_TPS_NO_ROWQ") != nullptr;
-  if (W % VSTAGE == 0 && !no_rowq)
+  if (W % VSTAGE == 0)
     tps_eval_bwd_kernel<false, true><<<dim3(nchunk, ktiles, N), BWD_TPB, 0, s>>>(dgrid, theta, ctrl, nullptr, partial,
                                                                                T, D, H, W, nvox, nchunk);
   else

@@ -392,7 +392,7 @@ __device__ __forceinline__ void split4(const float4 v, uint2 out[TERMS]) {
     out[t].y = h[2] | (h[3] << 16);
   }
 }
-// AMP (KeyMorph(use_amp=True): the entry point was called with terms == 1, common.h: KmhAmpCall; TERMS == 2 only): the
+// AMP (KeyMorph(use_amp=True): the entry point was called with terms == 1, common.h: kmh_take_amp; TERMS == 2 only): the
 // hi x hi product alone, as the reference's autocast runs this convolution in fp16 (keymorph/model.py:176-191)
 template <int TERMS, bool AMP = false>
 __device__ __forceinline__ f32x16 mfma_split(const bf16x8 a[TERMS], const bf16x8 b[TERMS], f32x16 acc) {
@@ -1455,7 +1455,7 @@ static int head_pack(const float* w, int Cout, int Cin, const HeadBfPlan& p, voi
 
 template <int TERMS>
 static int head_fwd_bf(const float* feat, const float* w, const float* bias, float* pts, float* sums, float* sq, float* scales_out, int N,
-                       int D, int H, int W, int Cin, int Cout, unsigned* mask, void* ws, hipStream_t s) {
+                       int D, int H, int W, int Cin, int Cout, unsigned* mask, void* ws, hipStream_t s, bool amp) {
   const long long V = (long long)D * H * W;
   const HeadBfPlan p = head_bf_plan(N, V, Cout, TERMS);
   double* partial = (double*)ws;
@@ -1469,7 +1469,7 @@ static int head_fwd_bf(const float* feat, const float* w, const float* bias, flo
   const size_t lds = 2 * ((size_t)TERMS * FVT * 128 + FVT * sizeof(float4));   // double buffered
   const bool rows = head_rows_ok(D, H, W);
   if (mask && !rows) return -22;             // kmh_headcom_mask_words said 0 for this geometry
-  const bool amp = TERMS == 2 && kmh_amp_enabled();      // use_amp: one product (the kernels that keep the sign mask)
+  // amp (use_amp, TERMS == 2 only): one product (the kernels that keep the sign mask)
   auto kern = p.nwv == 16 ? (rows ? (amp ? headcom_fwd_bf_kernel<TERMS, true, 16, true> : headcom_fwd_bf_kernel<TERMS, true, 16>)
                                   : headcom_fwd_bf_kernel<TERMS, false, 16>)
                           : (rows ? (amp ? headcom_fwd_bf_kernel<TERMS, true, 4, true> : headcom_fwd_bf_kernel<TERMS, true, 4>)
@@ -1487,7 +1487,7 @@ template <int TERMS>
 static int head_bwd_bf(const float* dpts, const float* dpower, const float* feat, const float* w, const float* bias, const float* sums,
                        float* dfeat, float* dw, float* dbias, int N, int D, int H, int W, int Cin, int Cout,
                        int mask_dfeat, const float* scales_in, float* dfeat_scale2, const unsigned* mask, void* ws,
-                       hipStream_t s) {
+                       hipStream_t s, bool amp) {
   const long long V = (long long)D * H * W;
   if (mask && !head_rows_ok(D, H, W)) return -22;
   const HeadBfPlan p = head_bf_plan(N, V, Cout, TERMS);
@@ -1512,14 +1512,13 @@ static int head_bwd_bf(const float* dpts, const float* dpower, const float* feat
   headcom_coef_kernel<<<ceil_div(N * Cout, 64), 64, 0, s>>>(dpts, dpower, sums, N * Cout, g);
   if (TERMS == 2) head_dh_scale_kernel<<<1, 256, 0, s>>>(g, N * Cout, hs + 4, gate);
 
-  auto launch = [&](auto tag, const HeadBfPlan& pl, const void* img_, const float* hs_, int want) -> int {
+  auto launch = [&](auto tag, const HeadBfPlan& pl, const void* img_, const float* hs_, int want, bool amp) -> int {
     constexpr int T = decltype(tag)::value;
     const __bf16* wk = (const __bf16*)img_;
     const __bf16* wkp = wk + (size_t)T * pl.CoutP * 64;
     const __bf16* wt = wkp + (size_t)T * pl.CoutP * 64;
     if (dfeat && mask) {
       const size_t lds = 2 * ((size_t)T * 64 * 128 + 8 * WBLK * 16);
-      const bool amp = T == 2 && kmh_amp_enabled();
       auto kern = Cin > 32 ? (amp ? headcom_bwd_feat_mask_kernel<T, true, true> : headcom_bwd_feat_mask_kernel<T, true>)
                            : (amp ? headcom_bwd_feat_mask_kernel<T, false, true> : headcom_bwd_feat_mask_kernel<T, false>);
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1538,7 +1537,6 @@ static int head_bwd_bf(const float* dpts, const float* dpower, const float* feat
     }
     if (dw && mask) {
       const size_t lds = 2 * ((size_t)T * 64 * 128);                               // double buffered
-      const bool amp = T == 2 && kmh_amp_enabled();
       auto kern = pl.nwv_w == 8 ? (Cin > 32 ? (amp ? headcom_bwd_w_mask_kernel<T, 8, true, true> : headcom_bwd_w_mask_kernel<T, 8, true>)
                                             : (amp ? headcom_bwd_w_mask_kernel<T, 8, false, true> : headcom_bwd_w_mask_kernel<T, 8, false>))
                                 : (Cin > 32 ? (amp ? headcom_bwd_w_mask_kernel<T, 4, true, true> : headcom_bwd_w_mask_kernel<T, 4, true>)
@@ -1559,13 +1557,13 @@ static int head_bwd_bf(const float* dpts, const float* dpower, const float* feat
     }
     return KMH_LAUNCH_CHECK();
   };
-  rc = launch(std::integral_constant<int, TERMS>{}, p, img, hs, 0);
+  rc = launch(std::integral_constant<int, TERMS>{}, p, img, hs, 0, amp);
   if (rc) return rc;
   if (TERMS == 2) {
     head_scales_one_kernel<<<1, 64, 0, s>>>(hs3);
     rc = head_pack<3>(w, Cout, Cin, p3, img3, hs3, s);
     if (rc) return rc;
-    rc = launch(std::integral_constant<int, 3>{}, p3, img3, hs3, 1);
+    rc = launch(std::integral_constant<int, 3>{}, p3, img3, hs3, 1, false);      // (three terms: no one-product instance)
     if (rc) return rc;
   }
   if (dfeat && dfeat_scale2) kmh_absmax::final_kernel<<<1, 1, 0, s>>>(dfeat_scale2, 0.f);
@@ -1599,20 +1597,20 @@ KMH_API size_t kmh_headcom_mask_words(int N, int D, int H, int W, int Cout) {
 KMH_API int kmh_headcom_fwd_bf(const float* feat, const float* w, const float* bias, float* pts, float* sums, float* sq,
                                float* scales_out, int N, int D, int H, int W, int Cin, int Cout, int terms, unsigned* mask,
                                void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if (Cin > 64 || (Cin & 3) || (terms != 2 && terms != 3)) return -22;
   return terms == 3
-             ? head_fwd_bf<3>(feat, w, bias, pts, sums, sq, scales_out, N, D, H, W, Cin, Cout, mask, ws, (hipStream_t)stream)
-             : head_fwd_bf<2>(feat, w, bias, pts, sums, sq, scales_out, N, D, H, W, Cin, Cout, mask, ws, (hipStream_t)stream);
+             ? head_fwd_bf<3>(feat, w, bias, pts, sums, sq, scales_out, N, D, H, W, Cin, Cout, mask, ws, (hipStream_t)stream, amp)
+             : head_fwd_bf<2>(feat, w, bias, pts, sums, sq, scales_out, N, D, H, W, Cin, Cout, mask, ws, (hipStream_t)stream, amp);
 }
 KMH_API int kmh_headcom_bwd_bf(const float* dpts, const float* dpower, const float* feat, const float* w, const float* bias,
                                const float* sums, float* dfeat, float* dw, float* dbias, int N, int D, int H, int W,
                                int Cin, int Cout, int terms, int mask_dfeat, const float* scales_in,
                                float* dfeat_scale2, const unsigned* mask, void* ws, void* stream) {
-  KmhAmpCall amp_call(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
+  const bool amp = kmh_take_amp(terms);      // terms == 1: the fp16 kernels with hi x hi only (use_amp), for this call
   if (Cin > 64 || (Cin & 3) || (terms != 2 && terms != 3)) return -22;
   return terms == 3 ? head_bwd_bf<3>(dpts, dpower, feat, w, bias, sums, dfeat, dw, dbias, N, D, H, W, Cin, Cout,
-                                     mask_dfeat, scales_in, dfeat_scale2, mask, ws, (hipStream_t)stream)
+                                     mask_dfeat, scales_in, dfeat_scale2, mask, ws, (hipStream_t)stream, amp)
                     : head_bwd_bf<2>(dpts, dpower, feat, w, bias, sums, dfeat, dw, dbias, N, D, H, W, Cin, Cout,
-                                     mask_dfeat, scales_in, dfeat_scale2, mask, ws, (hipStream_t)stream);
+                                     mask_dfeat, scales_in, dfeat_scale2, mask, ws, (hipStream_t)stream, amp);
 }

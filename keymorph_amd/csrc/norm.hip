@@ -1089,14 +1089,11 @@ __global__ __launch_bounds__(BT_TPB) void up2_boxsum_tiled_kernel(const float* _
  * (V_low x 27 Cout) per sample -- one plain matrix product (the host uses the library GEMM). */
 KMH_API int kmh_up2_boxsum(const float* dz, float* G, int N, int Dl, int Hl, int Wl, int Cout, int in_blocked, void* stream) {
   if ((Cout & 3) || (in_blocked && (Cout & 7))) return -22;
-  static const bool plain = getenv("KEYMORPH_BOXSUM_PLAIN") != nullptr;       // A/B runs: the untiled kernel
-  if (!plain) {
-    const int tx = (Wl + BT_X - 1) / BT_X, ty = (Hl + BT_Y - 1) / BT_Y, tz = (Dl + BT_Z - 1) / BT_Z;
-    const int chunks = (Cout + 4 * BT_CQ - 1) / (4 * BT_CQ);
-    if ((long long)tx * ty * tz < (1ll << 31) && chunks < 65536 && N < 65536) {
-      up2_boxsum_tiled_kernel<<<dim3(tx * ty * tz, chunks, N), BT_TPB, 0, (hipStream_t)stream>>>(dz, G, Dl, Hl, Wl, Cout, tx, ty, in_blocked);
-      return KMH_LAUNCH_CHECK();
-    }
+  const int tx = (Wl + BT_X - 1) / BT_X, ty = (Hl + BT_Y - 1) / BT_Y, tz = (Dl + BT_Z - 1) / BT_Z;
+  const int chunks = (Cout + 4 * BT_CQ - 1) / (4 * BT_CQ);
+  if ((long long)tx * ty * tz < (1ll << 31) && chunks < 65536 && N < 65536) {
+    up2_boxsum_tiled_kernel<<<dim3(tx * ty * tz, chunks, N), BT_TPB, 0, (hipStream_t)stream>>>(dz, G, Dl, Hl, Wl, Cout, tx, ty, in_blocked);
+    return KMH_LAUNCH_CHECK();
   }
   const long long total = (long long)Dl * Hl * Wl * 3 * (Cout / 4);
   up2_boxsum_kernel<<<dim3(stream_blocks(total), N), 256, 0, (hipStream_t)stream>>>(dz, G, Dl, Hl, Wl, Cout, in_blocked);
@@ -1200,8 +1197,7 @@ KMH_API int kmh_maxpool3d_bwd(const float* x, const unsigned char* argmax, const
   const bool aligned = (((uintptr_t)add | (uintptr_t)dx | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)argmax & 3) == 0;
   if (argmax && aligned && (C & 3) == 0 && (add_cstride & 3) == 0 && pooled / 4 < (1ll << 31) &&
       (long long)D * H * W < (1ll << 31)) {
-    static const bool pieces32 = getenv("KEYMORPH_POOL_BWD_PLANES") != nullptr;    // A/B runs: the per-plane 32-byte stores
-    if (out_blocked && !add && !pieces32) {
+    if (out_blocked && !add) {
       maxpool_bwd4_rows_kernel<<<dim3(stream_blocks(pooled), N), TPB, 0, (hipStream_t)stream>>>(
           (const unsigned*)argmax, (const float4*)dy, dx, D, H, W, C / 4, Do, Ho, Wo);
       return KMH_LAUNCH_CHECK();

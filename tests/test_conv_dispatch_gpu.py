@@ -495,8 +495,9 @@ def test_forward_kernels_repeat_bit_for_bit_with_other_work_in_between():
 
 
 def test_the_eight_wave_kernel_still_matches(tmp_path):
-    """KEYMORPH_FWD_S=0 keeps conv3_fwd_g_kernel<2,false> / <1,false> as the A/B arm of conv3_fwd_s_kernel: its outputs must
-    stay bit-identical to the default's (the switch is read once per process, so the other arm runs in a child)."""
+    """KEYMORPH_FWD_S=0 keeps conv3_fwd_g_kernel<2,false> / <1,false> as the parity arm of conv3_fwd_s_kernel: its outputs must
+    stay bit-identical to the default's (the switch is read once per process, so the other arm runs in a child; the switch is
+    off / on: "2", like every value that is not 0, is the default)."""
     import os
     import subprocess
     import sys

@@ -601,3 +601,41 @@ def test_bench_plain_run_options_and_output_dump(tmp_path):
     assert got.dtype == np.float32 and got.shape == (n,) and "seeded sample" in notes["big"]
     assert np.all(np.diff(got) >= 0) and got.max() < n + 2            # values of the array at sorted flat indices
     assert np.array_equal(got, np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_library_switches_are_documented_and_driven_by_a_test():
+    """Which kernel the library launches depends on a call's arguments and the dispatch setter; an environment switch read
+    inside csrc/ stays only while a test drives it or it is an instrument.  Every KEYMORPH_* / KMH_* string literal under
+    csrc/ is named in README.md and is either set by a file under tests/ or one of the two listed instruments; the switches
+    retired for lack of a test do not come back in csrc/, README.md or include/."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def text(*parts):
+        out = []
+        for f in sorted(glob.glob(os.path.join(root, *parts), recursive=True)):
+            if os.path.isfile(f) and os.path.abspath(f) != os.path.abspath(__file__):
+                with open(f, errors="replace") as fh:
+                    out.append(fh.read())
+        return "\n".join(out)
+
+    csrc, readme, tests = text("keymorph_amd", "csrc", "*"), text("README.md"), text("tests", "**", "*.py")
+    names = sorted(set(re.findall(r'"((?:KEYMORPH|KMH)_[A-Z0-9_]+)"', csrc)))
+    assert "KEYMORPH_FWD_S" in names and "KMH_SAMPLER_OLD" in names, names          # the scan still finds the getenv calls
+    instruments = {"KMH_G_TRACE", "KEYMORPH_FWD_G"}        # a debug trace; the initial value of kmh_conv3d_fwd_bf_set_dispatch
+
+    def set_by_a_test(n):
+        return re.search(r'setenv\(\s*"%s"|"%s"\s*:|environ\[\s*"%s"\s*\]\s*=|environ,[^)\n]*\b%s=' % (n, n, n, n), tests)
+
+    for n in names:
+        assert re.search(r"\b%s\b" % n, readme), f"{n} is read in csrc/ and not named in README.md"
+        assert n in instruments or set_by_a_test(n), f"{n} is read in csrc/, no test sets it and it is no instrument"
+    retired = ["KEYMORPH_POOL_G", "KEYMORPH_FWD_NO_DEEP", "KEYMORPH_WGRAD_NO_WS", "KEYMORPH_WGRAD_PRODUCERS",
+               "KEYMORPH_UP2_GEMM_NO_XCD", "KEYMORPH_BOXSUM_PLAIN", "KEYMORPH_POOL_BWD_PLANES", "KEYMORPH_FIRST_WGRAD_VALU",
+               "KEYMORPH_TPS_LU_VALU", "KEYMORPH_TPS_LU_CLUSTER", "KMH_TPS_NO_ROWQ", "KMH_TPS_TV"]
+    shipped = csrc + readme + text("include", "*")
+    for n in retired:
+        assert n not in shipped, f"{n} was retired: no test drove it"
+    # the two retired VALUES of the switch that stays (1: the 64-wide tile only, 3: the z-paired one-wave tile)
+    assert not re.search(r"KEYMORPH_FWD_S=[13]", shipped)

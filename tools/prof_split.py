@@ -1,5 +1,5 @@
 """The 32 -> 16 data gradient behind the 256^3 pooling (N = 2): pooling backward + convolution, four operand formats.
-  blocked fp32 scatter -> conv3_fwd_g_kernel<1,true> (round 4) | KEYMORPH_FWD_S=3: conv3_fwd_s_kernel<1,true>
+  blocked fp32 scatter -> conv3_fwd_g_kernel<1,true> (round 4)
   pre-split records    -> conv3_fwd_s_kernel<1,true,true> (round 5)
   pooled + winners     -> conv3_fwd_s_kernel<1,true,true,false,false,true> (round 7): no pooling backward at all
 usage: prof_split.py [D]   (KMH_G_TRACE=1: cycle stamps on stderr)"""

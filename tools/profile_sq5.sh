@@ -4,7 +4,7 @@
 #   tools/profile_sq5.sh r5a  ->  gpurun_out/r5a_sq_counters_fwd_family.txt , gpurun_out/r5a_cycle_stamps.txt
 # Shapes (prof_layer.py D Cin Cout, N = 2): forward = Cin -> Cout, data gradient = Cout -> Cin
 #   128 64 64 : conv3_fwd_s<2> both ways          128 32 32 : conv3_fwd_s<1> both ways
-#   256 16 32 : conv3_fwd_s<1> forward, conv3_fwd_g<1,ZP> data gradient (KEYMORPH_FWD_S=3: conv3_fwd_s<1,ZP>)
+#   256 16 32 : conv3_fwd_s<1> forward, conv3_fwd_g<1,ZP> data gradient
 #   prof_pool.py: conv3_fwd_g<1,false,POOL> (16 -> 32 at 256^3 + pooling)
 set -e
 tag=${1:-r5x}
@@ -31,15 +31,12 @@ run_sq() {   # $1 = label, rest = command
 for shape in "128 64 64" "128 32 32" "256 16 32"; do
   run_sq "python tools/prof_layer.py $shape f16x3 nomask (N = 2)" python tools/prof_layer.py $shape f16x3 nomask
 done
-KEYMORPH_FWD_S=3 run_sq "KEYMORPH_FWD_S=3 python tools/prof_layer.py 256 16 32 f16x3 nomask (N = 2; the one-wave z-paired data gradient)" python tools/prof_layer.py 256 16 32 f16x3 nomask
 run_sq "python tools/prof_pool.py (16 -> 32 at 2 x 256^3 with the pooling epilogue, then without)" python tools/prof_pool.py
 run_sq "python tools/prof_split.py 256 (32 -> 16 data gradient at 2 x 256^3: blocked fp32 operand = conv3_fwd_g<1,ZP>, pre-split = conv3_fwd_s<1,ZP,SPLIT>)" python tools/prof_split.py 256
 for shape in "128 64 64" "128 32 32" "256 16 32"; do
   echo "== KMH_TIME=1 python tools/prof_layer.py $shape f16x3 nomask" >> $out
   KMH_TIME=1 python tools/prof_layer.py $shape f16x3 nomask >> $out 2>&1
 done
-echo "== KEYMORPH_FWD_S=3 KMH_TIME=1 python tools/prof_layer.py 256 16 32 f16x3 nomask" >> $out
-KEYMORPH_FWD_S=3 KMH_TIME=1 python tools/prof_layer.py 256 16 32 f16x3 nomask >> $out 2>&1
 python tools/prof_pool.py >> $out 2>&1
 # cycle stamps of workgroup 0, wave 0 (differences between consecutive stamps; see the stamp() calls of conv3_fwd_g_kernel / conv3_fwd_s_kernel in conv_bf.hip)
 st=gpurun_out/${tag}_cycle_stamps.txt
@@ -47,7 +44,6 @@ st=gpurun_out/${tag}_cycle_stamps.txt
 for shape in "128 64 64" "128 32 32" "256 16 32"; do
   KMH_G_TRACE=1 python tools/prof_layer.py $shape f16x3 nomask 2>&1 | grep KMH_G_TRACE | tail -3 >> $st
 done
-KEYMORPH_FWD_S=3 KMH_G_TRACE=1 python tools/prof_layer.py 256 16 32 f16x3 nomask 2>&1 | grep KMH_G_TRACE | tail -3 >> $st
 KMH_G_TRACE=1 python tools/prof_pool.py 2>&1 | grep KMH_G_TRACE | head -3 >> $st
 KMH_G_TRACE=1 python tools/prof_split.py 256 2>&1 | grep "SPLIT=1" | tail -1 >> $st
 head -c 6000 $out
