@@ -542,6 +542,28 @@ size_t kmh_conv3d_thin_wgrad_ws_bytes(int N, int D, int H, int W, int Cin, int C
 int kmh_conv3d_thin_wgrad(const float* x, const float* dz, const float* dzmask, float* dw, float* db, int N, int D, int H,
                           int W, int Cin, int Cout, void* ws, void* stream);
 
+/* ---- sampling grids as transforms (keymorph_amd/fields.py) ----
+ * A grid (N,D,H,W,3) is xyz, normalised, align_corners=False, and as a function of space its own trilinear interpolant with
+ * border clamping (what kmh_grid_sample3d_fwd does to any volume).  Ids[k,j,i] = ((2i+1)/W - 1, (2j+1)/H - 1, (2k+1)/D - 1).
+ * A lattice of 2^31 voxels or more, or a gathered grid of 2^30 floats or more per sample: -22. */
+int kmh_field_identity(float* out, int N, int D, int H, int W, void* stream);
+/* out (N,Do,Ho,Wo,3) = then (N,D,H,W,3) interpolated at first (N,Do,Ho,Wo,3): bit-identical to sampling the (N,3,D,H,W) copy
+ * of `then` with kmh_grid_sample3d_fwd, read channels-last instead. */
+int kmh_field_compose(const float* first, const float* then, float* out, int N, int Do, int Ho, int Wo, int D, int H, int W,
+                      void* stream);
+/* out[w] = c with grid(c) = Ids[w]: per-voxel Newton steps from c0 = start (N,3,4) applied to Ids[w], each limited to one voxel
+ * per axis and clamped to [-1, 1], until max |residual| <= tol or max_iters steps; a near-singular Jacobian steps through the
+ * linear part of `start`.  converged (N,D,H,W) bytes; unconverged (N) = voxels with converged == 0; max_residual (N) over the
+ * converged voxels; iterations (N) | NULL = Newton steps taken.  A voxel that meets a non-finite value ends flagged, finite and
+ * inside [-1, 1].  Every axis >= 2.  ws = kmh_field_invert_ws_bytes(). */
+size_t kmh_field_invert_ws_bytes(int N, int D, int H, int W);
+int kmh_field_invert(const float* grid, const float* start, float* out, unsigned char* converged, long long* unconverged,
+                     float* max_residual, long long* iterations, int N, int D, int H, int W, float tol, int max_iters, void* ws,
+                     void* stream);
+/* disp (N,3,D,H,W), channels (z,y,x), in voxels = (grid - Ids) * size / 2 (what kmh_jacobian_det reads), and back. */
+int kmh_field_to_displacement(const float* grid, float* disp, int N, int D, int H, int W, void* stream);
+int kmh_field_from_displacement(const float* disp, float* grid, int N, int D, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,12 @@ PROTOS = {
     "kmh_conv3d_thin_dgrad": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f]),
     "kmh_conv3d_thin_wgrad_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "kmh_conv3d_thin_wgrad": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f]),
+    "kmh_field_identity": (_i, [_f, _i, _i, _i, _i, _f]),
+    "kmh_field_compose": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_field_invert_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "kmh_field_invert": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, C.c_float, _i, _f, _f]),
+    "kmh_field_to_displacement": (_i, [_f, _f, _i, _i, _i, _i, _f]),
+    "kmh_field_from_displacement": (_i, [_f, _f, _i, _i, _i, _i, _f]),
 }
 
 _lib = None
