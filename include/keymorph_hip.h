@@ -143,6 +143,20 @@ int kmh_mi_hist(const float* a, const float* b, int N, long long V, int bins, in
 int kmh_mi_final(const void* ws, const float* rng, int N, long long V, int bins, float* mi, float* G, void* stream);
 int kmh_mi_bwd(const float* a, const float* b, const float* rng, const float* G, const float* gout, int N, long long V,
                int bins, float* da, float* db, void* stream);
+/* kmh_mi_hist's ranges alone: rng (N, 4) out, ws 16 N bytes. */
+int kmh_mi_range(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
+                 int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream);
+
+/* ---- mutual information of a fixed volume and a moving volume warped by a matrix, fused (csrc/warp_mi.hip) ---- */
+/* By definition MI(grid_sample3d(moving, affine_grid(mat)), fixed) with the ranges rng = kmh_mi_range(moving, fixed): moving,
+ * fixed (N, D, H, W) float32, mat (N, 3, 4), 8 <= bins <= 64, W >= 2, fewer than 2^30 voxels per sample (else -22).
+ * kmh_warp_mi_hist leaves the joint table in ws (kmh_warp_mi_ws_bytes bytes) in kmh_mi_hist's layout: kmh_mi_final(ws, rng, N,
+ * D H W, bins, mi, G) follows.  kmh_warp_mi_bwd: dmat (N, 3, 4) = gout[n] dMI_n / dmat, deterministic, a batch equals its samples. */
+size_t kmh_warp_mi_ws_bytes(int N, int bins, int D, int H, int W);
+int kmh_warp_mi_hist(const float* moving, const float* fixed, const float* mat, const float* rng, int N, int D, int H, int W,
+                     int bins, void* ws, void* stream);
+int kmh_warp_mi_bwd(const float* moving, const float* fixed, const float* mat, const float* rng, const float* G,
+                    const float* gout, int N, int D, int H, int W, int bins, void* ws, float* dmat, void* stream);
 
 /* ---- a9: AffineTransform.get_flow_field, keymorph/transformations.py:37-79 and
  *      uniform_norm_grid keymorph/utils.py:387-398.  mat (N,3,4) = inverse_transform_matrix[:, :3, :]

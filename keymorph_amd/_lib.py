@@ -69,6 +69,10 @@ PROTOS = {
     "kmh_mi_hist": (_i, [_f, _f, _i, _ll, _i, _i, C.c_float, C.c_float, _i, C.c_float, C.c_float, _f, _f, _f]),
     "kmh_mi_final": (_i, [_f, _f, _i, _ll, _i, _f, _f, _f]),
     "kmh_mi_bwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
+    "kmh_mi_range": (_i, [_f, _f, _i, _ll, _i, _i, C.c_float, C.c_float, _i, C.c_float, C.c_float, _f, _f, _f]),
+    "kmh_warp_mi_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kmh_warp_mi_hist": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
+    "kmh_warp_mi_bwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
     "kmh_affine_build_matrix": (_i, [_f, _f, _f, _f, _f, _i, _f]),
     "kmh_affine_points_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _f]),
     "kmh_com3d_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),

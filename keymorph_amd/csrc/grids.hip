@@ -11,18 +11,12 @@
 // TPS backward is the transposed reduction: each lane owns KPT keypoints (6 accumulators
 // each), voxels + their incoming gradient are staged through LDS and broadcast.
 #include "common.h"
+#include "grid_coords.h"      // lin, lin_step, affine_coord: shared with warp_mi.hip
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int VPT = 4;
-
-// torch.linspace(-1, 1, n)[i] in fp32 (symmetric evaluation: start + i*step below the midpoint,
-// end - (n-1-i)*step above)
-__device__ __forceinline__ float lin(int i, int n, float step) {
-  return (i < n / 2) ? (-1.f + step * (float)i) : (1.f - step * (float)(n - 1 - i));
-}
-__host__ __device__ __forceinline__ float lin_step(int n) { return n > 1 ? 2.f / (float)(n - 1) : 0.f; }
 
 // ---------------------------------------------------------------------------------------------
 // affine
@@ -44,10 +38,7 @@ __global__ __launch_bounds__(TPB) void affine_grid_fwd_kernel(const float* __res
     if (v >= nvox) v = nvox - 1;
     const int x = (int)(v % W), y = (int)((v / W) % H), z = (int)(v / ((long long)W * H));
     const float gz = lin(z, D, sz), gy = lin(y, H, sy), gx = lin(x, W, sx);
-    // rows of M are (z, y, x) outputs; flip -> (x, y, z)
-    r[i * 3 + 2] = M[0] * gz + M[1] * gy + M[2] * gx + M[3];
-    r[i * 3 + 1] = M[4] * gz + M[5] * gy + M[6] * gx + M[7];
-    r[i * 3 + 0] = M[8] * gz + M[9] * gy + M[10] * gx + M[11];
+    affine_coord(M, gz, gy, gx, r[i * 3], r[i * 3 + 1], r[i * 3 + 2]);
   }
   float* o = out + ((long long)n * nvox + v0) * 3;
   if (v0 + VPT <= nvox && (nvox & 3) == 0) {

@@ -28,16 +28,11 @@
 //                     writes MI_n and G.  A sample with s_a = 0 or s_b = 0 (a constant image) gets MI = 0 and G = 0 exactly.
 // mi_bwd_kernel       one lane per voxel: recomputes the taps, gathers the 16 entries of G from LDS, writes da and / or db.
 #include "common.h"
+#include "mi_taps.h"      // the window (taps) and the fixed-point format's constants: shared with warp_mi.hip
 
 namespace {
 constexpr int TPB = 256;
 constexpr int kWaves = TPB / kWave;
-constexpr int kMinBins = 8, kMaxBins = 64;
-constexpr int kFrac = 23;                        // fraction bits of one quantised product
-constexpr int kSteps = 16;                       // steps of 64 voxels per wave between two flushes
-constexpr int kFlushVox = kSteps * kWave;        // voxels per wave between two flushes
-constexpr int kMaxBlocks = 2048;                 // workgroups per sample
-static_assert((unsigned long long)kFlushVox * 3728271ull < (1ull << 32), "a bin of the LDS table must not overflow");
 
 // floats -> unsigned keys of the same order (negative: all bits flipped; else the sign bit set)
 __device__ __forceinline__ unsigned order_key(float x) {
@@ -53,12 +48,6 @@ __device__ __forceinline__ unsigned wave_umax(unsigned v) {
     const unsigned w = (unsigned)__shfl_xor((int)v, o, kWave);
     v = w > v ? w : v;
   }
-  return v;
-}
-
-__device__ __forceinline__ unsigned wave_usum(unsigned v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, kWave);
   return v;
 }
 
@@ -107,33 +96,6 @@ __global__ void mi_scale_kernel(const unsigned* __restrict__ keys, int N, int B,
   }
   rng[i * 2] = lo;
   rng[i * 2 + 1] = hi > lo ? (float)(B - 3) / (hi - lo) : 0.f;      // NaN compares false: s = 0
-}
-
-struct Taps {
-  int k0;
-  float w[4], d[4];
-};
-template <bool DERIV>
-__device__ __forceinline__ Taps taps(float x, float lo, float s, int B) {
-  Taps r;
-  float u = (x - lo) * s + 1.f;
-  u = fminf(fmaxf(u, 1.f), (float)(B - 2));                         // NaN -> 1
-  int k = (int)floorf(u) - 1;
-  k = k < 0 ? 0 : (k > B - 4 ? B - 4 : k);                          // any float addresses inside the table
-  r.k0 = k;
-  const float t = u - (float)(k + 1), o = 1.f - t, t2 = t * t, t3 = t2 * t;
-  constexpr float c6 = 1.f / 6.f;
-  r.w[0] = o * o * o * c6;
-  r.w[1] = (3.f * t3 - 6.f * t2 + 4.f) * c6;
-  r.w[2] = (-3.f * t3 + 3.f * t2 + 3.f * t + 1.f) * c6;
-  r.w[3] = t3 * c6;
-  if (DERIV) {
-    r.d[0] = -0.5f * o * o;
-    r.d[1] = 1.5f * t2 - 2.f * t;
-    r.d[2] = -1.5f * t2 + t + 0.5f;
-    r.d[3] = 0.5f * t2;
-  }
-  return r;
 }
 
 // grid (blocks, N).  The sample's V voxels are R = ceil(V / 64) steps of 64 consecutive voxels, one per lane.  Workgroup blockIdx.x
@@ -323,6 +285,25 @@ KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int 
   nb = (R + per - 1) / per;
   mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
       a, b, rng, V, R, per, bins, hist);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* The ranges of kmh_mi_hist without its histogram: rng (N, 4) = (lo_a, s_a, lo_b, s_b), same kernels, same arguments.  ws: 16 N
+ * bytes.  For a caller that scores many warps of one pair (csrc/warp_mi.hip): the range of a volume bounds every trilinear,
+ * border-padded resampling of it. */
+KMH_API int kmh_mi_range(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
+                         int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream) {
+  if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)N * 16, s);
+  if (e != hipSuccess) return (int)e;
+  unsigned* keys = (unsigned*)ws;
+  if (!has_range_a || !has_range_b) {
+    long long nb = (V + TPB * 16 - 1) / (TPB * 16);
+    if (nb > 256) nb = 256;
+    mi_range_kernel<<<dim3((unsigned)nb, (unsigned)N, 2), TPB, 0, s>>>(a, b, V, has_range_a, has_range_b, keys);
+  }
+  mi_scale_kernel<<<ceil_div(2 * N, 64), 64, 0, s>>>(keys, N, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, rng);
   return KMH_LAUNCH_CHECK();
 }
 

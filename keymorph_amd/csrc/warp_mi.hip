@@ -1,0 +1,275 @@
+// Mutual information of a fixed volume and a moving volume warped by a 3 x 4 matrix, and its gradient with respect to the
+// matrix, without the sampling grid, the warped volume or their gradients ever being stored.
+//
+// By definition (per sample):  warp_mi(moving, fixed, mat) = MI(align_img(affine_grid(mat, dims), moving), fixed) with both
+// ranges given -- the chain kmh_affine_grid_fwd -> kmh_grid_sample3d_fwd -> kmh_mi_hist -> kmh_mi_final.  Every definition is
+// that chain's own: the coordinate is grid_coords.h's (lin, affine_coord_chain: what affine_grid_fwd_kernel writes), the tap, the
+// border clamp and the blend are sampler_taps.h's, the window and the table's constants are mi_taps.h's, and the quantised
+// product and the wave's step into its table (hist_add) repeat mi_hist_kernel's text.  The joint table is an integer sum of
+// the same products, so it is the chain's table bit for bit, and kmh_mi_final turns it into MI and G = ln(p / (pa pb)) unchanged.
+//
+// warp_mi_hist_kernel   mi_hist_kernel's partition (steps of 64 consecutive voxels, one per lane; kSteps steps per wave between
+//                       two flushes; per-wave LDS tables; 64-bit global adds) with a = blend8 of the 8 corners of `moving` at
+//                       the voxel's coordinate instead of a load.  An affine map sends the 64 neighbouring voxels of a step to
+//                       neighbouring source voxels: the coherent case of the lane-contiguous gathers.  kIlp steps' gathers are
+//                       in flight together.
+// warp_mi_bwd_kernel    one lane per voxel recomputes coordinate, tap, corners and a, then
+//                         dMI/da_v = (gout s_a / V) sum_ij G_ij w_a'[i] w_b[j]                          (mi_bwd_kernel)
+//                         da_v/d(gx, gy, gz) = blend_grads * (mx, my, mz), 0 for a NaN coordinate        (grad_row_out)
+//                         dM[r][k] += d(coordinate r) * (gz, gy, gx, 1)[k]                               (affine_grid_bwd_partial)
+//                       fp32 per lane, the workgroup's sum in fp64, one fp64 partial per workgroup and entry.
+// warp_mi_final_kernel  the partials of a sample combined in a fixed order (affine_grid_bwd_final's).
+// The number of workgroups per sample depends on the volume's size alone and every sum has a fixed order: a batch reproduces
+// its samples run singly and a repeat reproduces itself, bit for bit.  No float atomics.
+#include "common.h"
+#include "grid_coords.h"
+#include "mi_taps.h"
+#include "sampler_taps.h"
+
+extern "C" size_t kmh_mi_ws_bytes(int N, int bins);
+
+namespace {
+constexpr int kWaves = TPB / kWave;
+constexpr int kIlp = 4;                          // steps of a wave whose gathers are in flight together
+constexpr int kBwdBlocks = 1024;                 // workgroups per sample of the backward pass, at most
+static_assert(kSteps % kIlp == 0, "a flush interval is a whole number of gather groups");
+
+struct Voxel {
+  Tap t;
+  float gx, gy, gz;      // the sampling coordinate (x, y, z)
+  float pz, py, px;      // the base grid's coordinate
+};
+// voxel v of the fixed lattice -> where it samples `moving`
+__device__ __forceinline__ Voxel voxel_tap(unsigned v, const float (&M)[12], int D, int H, int W, float sz, float sy, float sx) {
+  Voxel r;
+  const unsigned row = v / (unsigned)W;
+  const int x = (int)(v - row * (unsigned)W), z = (int)(row / (unsigned)H), y = (int)(row - (unsigned)z * (unsigned)H);
+  r.pz = lin(z, D, sz); r.py = lin(y, H, sy); r.px = lin(x, W, sx);
+  affine_coord_chain(M, r.pz, r.py, r.px, r.gx, r.gy, r.gz);
+  r.t = make_tap(r.gx, r.gy, r.gz, D, H, W);
+  return r;
+}
+
+// One step of a wave, the text of mi_hist_kernel's inner loop: each valid lane's pair (xa, xb) -> 16 quantised products added to
+// the wave's own B x B table `mine`.  Every lane of the wave calls it together, and at least one of them is valid.
+__device__ __forceinline__ void hist_add(bool valid, float xa, float xb, float lo_a, float s_a, float lo_b, float s_b, int B,
+                                         int lane, unsigned* mine) {
+  unsigned q[16];
+  int key = -1;
+  if (valid) {
+    const Taps ta = taps<false>(xa, lo_a, s_a, B), tb = taps<false>(xb, lo_b, s_b, B);
+    key = ta.k0 * B + tb.k0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[i * 4 + k] = (unsigned)__float2int_rn(ta.w[i] * tb.w[k] * (float)(1 << kFrac));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) q[i] = 0u;
+  }
+  const int first = __shfl(key, __ffsll((long long)__ballot(valid)) - 1, kWave);
+  if (__all(!valid || key == first)) {
+    // one window for the whole wave: 64 lanes * rint(2^23 * 4/9) < 2^28 per sum
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const unsigned sum = wave_usum(q[i]);
+      if (lane == 0 && sum) atomicAdd(mine + first + (i >> 2) * B + (i & 3), sum);
+    }
+  } else if (valid) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (q[i]) atomicAdd(mine + key + (i >> 2) * B + (i & 3), q[i]);
+  }
+}
+
+// grid (blocks, N); R, per as in mi_hist_kernel.  LDS: kWaves tables of B * B.
+__global__ __launch_bounds__(TPB) void warp_mi_hist_kernel(const float* __restrict__ moving, const float* __restrict__ fixed,
+                                                           const float* __restrict__ mat, const float* __restrict__ rng,
+                                                           int D, int H, int W, int R, int per, int B,
+                                                           unsigned long long* __restrict__ hist) {
+  extern __shared__ unsigned tab[];
+  const int n = blockIdx.y, BB = B * B, lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const unsigned V = (unsigned)D * H * W, plane_bytes = V * 4u;
+  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  float M[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) M[i] = mat[n * 12 + i];
+  const float sz = lin_step(D), sy = lin_step(H), sx = lin_step(W);
+  const int beg = per * blockIdx.x;
+  const int end = beg + per < R ? beg + per : R;
+  const __amdgpu_buffer_rsrc_t rm = make_rsrc(moving + (long long)n * V, plane_bytes);
+  fixed += (long long)n * V;
+  hist += (long long)n * BB;
+  for (int e = threadIdx.x; e < kWaves * BB; e += TPB) tab[e] = 0u;
+  __syncthreads();
+  unsigned* mine = tab + wid * BB;
+  for (int c = beg; c < end; c += kSteps * kWaves) {
+#pragma unroll 1
+    for (int it0 = 0; it0 < kSteps; it0 += kIlp) {
+      TapB q[kIlp];
+      float xb[kIlp], cv[kIlp][8];
+      unsigned live = 0u;
+#pragma unroll
+      for (int u = 0; u < kIlp; ++u) {
+        const int j = c + wid * kSteps + it0 + u;
+        const unsigned v = (unsigned)j * kWave + lane;                 // j < R <= 2^24: no overflow
+        const bool valid = j < end && v < V;
+        live |= (valid ? 1u : 0u) << u;
+        const Voxel p = voxel_tap(valid ? v : 0u, M, D, H, W, sz, sy, sx);
+        q[u] = make_tapb(p.t, D, H, W);
+        if (!valid) park(q[u], plane_bytes);
+        xb[u] = fixed[valid ? v : 0u];
+      }
+#pragma unroll
+      for (int u = 0; u < kIlp; ++u) gather8_b(rm, q[u], cv[u]);
+#pragma unroll
+      for (int u = 0; u < kIlp; ++u) {
+        const bool valid = (live >> u) & 1u;
+        if (!__any(valid)) continue;                                  // wave-uniform
+        hist_add(valid, blend8(cv[u], q[u].fx, q[u].fy, q[u].fz), xb[u], lo_a, s_a, lo_b, s_b, B, lane, mine);
+      }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < BB; e += TPB) {
+      unsigned long long sum = 0ull;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) {
+        sum += tab[w * BB + e];
+        tab[w * BB + e] = 0u;
+      }
+      if (sum) atomicAdd(hist + e, sum);
+    }
+    __syncthreads();
+  }
+}
+
+// grid (blocks, N), grid-stride over the sample's voxels, lane-contiguous.  LDS: G of the sample (B * B floats).
+// partial (N, gridDim.x, 12) doubles.
+__global__ __launch_bounds__(TPB) void warp_mi_bwd_kernel(const float* __restrict__ moving, const float* __restrict__ fixed,
+                                                          const float* __restrict__ mat, const float* __restrict__ rng,
+                                                          const float* __restrict__ G, const float* __restrict__ gout, int D,
+                                                          int H, int W, int B, double* __restrict__ partial) {
+  extern __shared__ float g[];
+  __shared__ double red[kWaves];
+  const int n = blockIdx.y, BB = B * B;
+  for (int e = threadIdx.x; e < BB; e += TPB) g[e] = G[(long long)n * BB + e];
+  __syncthreads();
+  const unsigned V = (unsigned)D * H * W, plane_bytes = V * 4u;
+  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  const float ca = gout[n] / (float)V * s_a;
+  float M[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) M[i] = mat[n * 12 + i];
+  const float sz = lin_step(D), sy = lin_step(H), sx = lin_step(W);
+  const __amdgpu_buffer_rsrc_t rm = make_rsrc(moving + (long long)n * V, plane_bytes);
+  fixed += (long long)n * V;
+  float acc[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+  for (long long v = (long long)blockIdx.x * TPB + threadIdx.x; v < V; v += (long long)gridDim.x * TPB) {
+    const Voxel p = voxel_tap((unsigned)v, M, D, H, W, sz, sy, sx);
+    const TapB q = make_tapb(p.t, D, H, W);
+    float cv[8];
+    gather8_b(rm, q, cv);
+    const float xb = fixed[v];
+    const Taps ta = taps<true>(blend8(cv, q.fx, q.fy, q.fz), lo_a, s_a, B), tb = taps<false>(xb, lo_b, s_b, B);
+    const float* row = g + ta.k0 * B + tb.k0;
+    float ga = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float rw = 0.f;                                                // sum_j G_ij w_b[j]
+#pragma unroll
+      for (int j = 0; j < 4; ++j) rw = fmaf(row[i * B + j], tb.w[j], rw);
+      ga = fmaf(ta.d[i], rw, ga);
+    }
+    const float go = ca * ga;                                        // dMI / da_v
+    float dx, dy, dz;
+    blend_grads(cv, q.fx, q.fy, q.fz, dx, dy, dz);
+    const float k = any_nan(p.gx, p.gy, p.gz) ? 0.f : 1.f;
+    const float d[3] = {dz * go * p.t.mz * k, dy * go * p.t.my * k, dx * go * p.t.mx * k};      // (z, y, x) rows
+    const float b[4] = {p.pz, p.py, p.px, 1.f};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r * 4 + c] += d[r] * b[c];
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const double s = block_sum<double>((double)acc[i], red);
+    if (threadIdx.x == 0) partial[((long long)n * gridDim.x + blockIdx.x) * 12 + i] = s;
+  }
+}
+
+// 12 outputs x 16 slices of the per-workgroup partials, combined in a fixed order
+__global__ __launch_bounds__(192) void warp_mi_final_kernel(const double* __restrict__ partial, int nblk,
+                                                            float* __restrict__ dmat) {
+  __shared__ double red[16][12];
+  const int n = blockIdx.x;
+  const int i = threadIdx.x % 12, sl = threadIdx.x / 12;
+  double s = 0;
+  for (int b = sl; b < nblk; b += 16) s += partial[((long long)n * nblk + b) * 12 + i];
+  red[sl][i] = s;
+  __syncthreads();
+  if (sl) return;
+  s = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) s += red[k][i];
+  dmat[n * 12 + i] = (float)s;
+}
+
+// buffer loads address a sample of `moving` with 32-bit byte offsets: fewer than 2^30 voxels
+bool warp_mi_args_ok(const void* moving, const void* fixed, const void* mat, const void* rng, int N, int D, int H, int W,
+                     int B) {
+  return moving && fixed && mat && rng && N >= 1 && N <= 65535 && D >= 1 && H >= 1 && W >= 2 && B >= kMinBins &&
+         B <= kMaxBins && (long long)D * H * W < (1ll << 30);
+}
+int bwd_blocks(long long V) {
+  long long nb = (V + TPB * 16 - 1) / (TPB * 16);
+  return (int)(nb > kBwdBlocks ? kBwdBlocks : nb);
+}
+size_t table_bytes(int N, int bins) { return (kmh_mi_ws_bytes(N, bins) + 255) & ~(size_t)255; }
+}  // namespace
+
+/* Workspace of kmh_warp_mi_hist / kmh_mi_final / kmh_warp_mi_bwd: the joint table in kmh_mi_hist's layout, then the backward
+ * pass's per-workgroup partial sums. */
+KMH_API size_t kmh_warp_mi_ws_bytes(int N, int bins, int D, int H, int W) {
+  if (N < 0 || bins < 0 || D < 1 || H < 1 || W < 1) return 0;
+  return table_bytes(N, bins) + (size_t)N * bwd_blocks((long long)D * H * W) * 12 * sizeof(double);
+}
+
+/* moving, fixed: (N, D, H, W) float32 contiguous; mat (N, 3, 4) as kmh_affine_grid_fwd takes it; rng (N, 4) = (lo_a, s_a, lo_b,
+ * s_b) with a = the warped moving volume (kmh_mi_range of (moving, fixed)).  Leaves the joint table in ws for kmh_mi_final
+ * (same N, bins, V = D H W).  8 <= bins <= 64, W >= 2, fewer than 2^30 voxels per sample. */
+KMH_API int kmh_warp_mi_hist(const float* moving, const float* fixed, const float* mat, const float* rng, int N, int D, int H,
+                             int W, int bins, void* ws, void* stream) {
+  if (!warp_mi_args_ok(moving, fixed, mat, rng, N, D, H, W, bins) || !ws) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, kmh_mi_ws_bytes(N, bins), s);
+  if (e != hipSuccess) return (int)e;
+  unsigned long long* hist = (unsigned long long*)((char*)ws + (size_t)N * 16);
+  constexpr int chunk = kSteps * kWaves;                             // steps per workgroup between two flushes
+  const long long V = (long long)D * H * W;
+  const long long R = (V + kWave - 1) / kWave;
+  long long nb = (R + 2 * chunk - 1) / (2 * chunk);
+  if (nb > kMaxBlocks) nb = kMaxBlocks;
+  long long per = (R + nb - 1) / nb;
+  per = (per + chunk - 1) / chunk * chunk;
+  nb = (R + per - 1) / per;
+  warp_mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
+      moving, fixed, mat, rng, D, H, W, (int)R, (int)per, bins, hist);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* dmat (N, 3, 4) = gout[n] dMI_n / dmat.  G as written by kmh_mi_final for the table of kmh_warp_mi_hist with the same
+ * arguments; ws: kmh_warp_mi_ws_bytes(N, bins, D, H, W) bytes (the table in it is not read). */
+KMH_API int kmh_warp_mi_bwd(const float* moving, const float* fixed, const float* mat, const float* rng, const float* G,
+                            const float* gout, int N, int D, int H, int W, int bins, void* ws, float* dmat, void* stream) {
+  if (!warp_mi_args_ok(moving, fixed, mat, rng, N, D, H, W, bins) || !G || !gout || !ws || !dmat) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  double* partial = (double*)((char*)ws + table_bytes(N, bins));
+  const int nb = bwd_blocks((long long)D * H * W);
+  warp_mi_bwd_kernel<<<dim3(nb, N), TPB, (size_t)bins * bins * sizeof(float), s>>>(moving, fixed, mat, rng, G, gout, D, H, W,
+                                                                                 bins, partial);
+  warp_mi_final_kernel<<<N, 192, 0, s>>>(partial, nb, dmat);
+  return KMH_LAUNCH_CHECK();
+}

@@ -7,3 +7,5 @@ from .pairs import DATA, AFFINE, PairLoader, make_subject         # noqa: F401
 from .groupwise import evaluate_group, save_dict_as_json         # noqa: F401
 from .brain import extract_brain, load_brain_extractor         # noqa: F401
 from .centering import center_to, estimate_translation, translate         # noqa: F401
+from .intensity import (apply_mat, estimate_affine, estimate_rigid, mat_to_voxel, register_intensity,         # noqa: F401
+                        rigid_params_to_voxel, rotation_matrix, voxel_to_mat)

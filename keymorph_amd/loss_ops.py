@@ -447,3 +447,15 @@ class MILoss(torch.nn.Module):
 
     def forward(self, pred, target):
         return -ops.mutual_information(pred, target, self.bins).mean()
+
+
+class WarpMILoss(torch.nn.Module):
+    """-mean over the batch of ops.warp_mutual_information(moving, fixed, mat, bins, ranges): MILoss of the moving volume warped
+    by the (N, 3, 4) matrix `mat` in one fused pass, differentiable in `mat` only."""
+
+    def __init__(self, bins=32):
+        super().__init__()
+        self.bins = bins
+
+    def forward(self, moving, fixed, mat, ranges=None):
+        return -ops.warp_mutual_information(moving, fixed, mat, self.bins, ranges).mean()

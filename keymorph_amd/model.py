@@ -355,6 +355,44 @@ class KeyMorph(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# The intensity baseline beside the keypoint model (scripts/register.py: --registration_model itkelastix | ants, whose code the
+# reference never shipped): multi-resolution mutual-information registration, io.register_intensity, behind KeyMorph's call.
+# ----------------------------------------------------------------------------------------------------------------------
+class IntensityRegistration(nn.Module):
+    """model(img_f, img_m, transform_type="translation" | "rigid" | "affine" | [..], num_resolutions_for_itkelastix=None,
+    **ignored) -> {type: {"grid" (N, D, H, W, 3), "matrix" (N, 3, 4) as ops.affine_grid takes it, "mi" (N,) the mutual
+    information reached, "time"}}.  No parameters.  num_resolutions_for_itkelastix = k means the pyramid 2^(k-1) .. 1
+    (None: 4, 2, 1)."""
+
+    supported_transform_type = ("translation", "rigid", "affine")
+
+    def __init__(self, bins=32, iters=30, lr=0.25):
+        super().__init__()
+        self.bins, self.iters, self.lr = bins, iters, lr
+
+    def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
+        from . import ops
+        from .io.intensity import register_intensity
+        if not isinstance(transform_type, (list, tuple)):
+            transform_type = [transform_type]
+        assert all(s in self.supported_transform_type for s in transform_type), "Invalid transform_type"
+        assert img_f.shape[1] == 1, "Image dimension must be 1"
+        assert img_m.shape[1] == 1, "Image dimension must be 1"
+        shrink = (4, 2, 1)
+        if num_resolutions_for_itkelastix is not None:
+            shrink = tuple(2 ** k for k in range(int(num_resolutions_for_itkelastix) - 1, -1, -1))
+        result_dict = {}
+        for align_type_str in transform_type:
+            start_time = time.time()
+            mat = register_intensity(img_f, img_m, align_type_str, bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
+            with torch.no_grad():
+                grid = ops.affine_grid(mat, img_f.shape[2:])
+                mi = ops.warp_mutual_information(img_m, img_f, mat, self.bins)
+            result_dict[align_type_str] = {"grid": grid, "matrix": mat, "mi": mi, "time": time.time() - start_time}
+        return result_dict
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Brain extractor (keymorph/model.py:533-659; notebooks/[B] Brain Extraction.ipynb): the preprocessing step users run before
 # they register their own scans.  Same constructors and state_dict keys as the reference (block{0..8}.conv1.{weight,bias},
 # conv.{weight,bias}; InstanceNorm holds no parameters and no buffers), so its checkpoints load with strict=True.

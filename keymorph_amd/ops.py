@@ -734,6 +734,114 @@ def _mi_table(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None):
 
 
 # --------------------------------------------------------------------------
+# mutual information of a fixed volume and a moving volume warped by a matrix, fused (csrc/warp_mi.hip states the definition)
+# --------------------------------------------------------------------------
+def _warp_mi_check(moving, fixed, mat, bins, ranges, who="warp_mutual_information"):
+    tensors = [("moving", moving), ("fixed", fixed)] + ([("mat", mat)] if mat is not None else []) \
+        + ([("ranges", ranges)] if ranges is not None else [])
+    for name, t in tensors:
+        if not isinstance(t, Tensor) or not t.is_cuda:
+            raise _lib.KeymorphHipError(f"{who}: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
+                                        "(no CPU fallback)")
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.KeymorphHipError(f"{who}: {name} is on {t.device} but the current device is "
+                                        f"cuda:{torch.cuda.current_device()}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+    if moving.shape != fixed.shape:
+        raise ValueError(f"{who}: shapes differ: {tuple(moving.shape)} vs {tuple(fixed.shape)}")
+    if moving.dim() != 5 or moving.shape[1] != 1 or moving.numel() == 0:
+        raise ValueError(f"{who}: expected two non-empty (N, 1, D, H, W) volumes, got {tuple(moving.shape)}")
+    if moving.shape[4] < 2 or moving[0].numel() >= 1 << 30:
+        raise ValueError(f"{who}: needs W >= 2 and fewer than 2^30 voxels per sample, got {tuple(moving.shape)}")
+    if int(bins) != bins or not MI_MIN_BINS <= bins <= MI_MAX_BINS:
+        raise ValueError(f"{who}: bins must be an integer in [{MI_MIN_BINS}, {MI_MAX_BINS}], got {bins}")
+    N = moving.shape[0]
+    if mat is not None and tuple(mat.shape) != (N, 3, 4):
+        raise ValueError(f"{who}: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
+    if ranges is not None and tuple(ranges.shape) != (N, 4):
+        raise ValueError(f"{who}: ranges must be ({N}, 4) as mi_ranges returns them, got {tuple(ranges.shape)}")
+    return int(bins)
+
+
+def _mi_ranges(moving, fixed, bins):
+    lib = _lib.load()
+    N, V = moving.shape[0], moving[0].numel()
+    ws = torch.empty(16 * N, dtype=torch.uint8, device=moving.device)
+    rng = torch.empty((N, 4), dtype=torch.float32, device=moving.device)
+    check(lib.kmh_mi_range(_p(moving), _p(fixed), N, V, bins, 0, 0.0, 0.0, 0, 0.0, 0.0, _p(ws), _p(rng), _stream()),
+          "kmh_mi_range")
+    return rng
+
+
+def mi_ranges(moving: Tensor, fixed: Tensor, bins: int = 32) -> Tensor:
+    """(N, 4) float32 on the device, (lo, s) of `moving` then of `fixed` per sample, s = (bins - 3) / (max - min) or 0 for a
+    constant volume: what warp_mutual_information takes as `ranges`.  Trilinear sampling with border padding cannot leave a
+    volume's [min, max], so one call serves every warp of the pair.  No host synchronisation."""
+    bins = _warp_mi_check(moving, fixed, None, bins, None, "mi_ranges")
+    return _mi_ranges(moving.detach().contiguous(), fixed.detach().contiguous(), bins)
+
+
+class _WarpMI(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, moving, fixed, mat, rng, bins):
+        lib = _lib.load()
+        N, _, D, H, W = moving.shape
+        dev = moving.device
+        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=dev)
+        mi = torch.empty((N,), dtype=torch.float32, device=dev)
+        G = torch.empty((N, bins, bins), dtype=torch.float32, device=dev)
+        if _lib.profiler.enabled:  # the fixed volume once, the moving volume about once (8 corners, coherent)
+            _lib.profiler.meta = {"bytes": 8.0 * N * D * H * W}
+        check(lib.kmh_warp_mi_hist(_p(moving), _p(fixed), _p(mat), _p(rng), N, D, H, W, bins, _p(ws), _stream()),
+              "kmh_warp_mi_hist")
+        check(lib.kmh_mi_final(_p(ws), _p(rng), N, D * H * W, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+        ctx.save_for_backward(moving, fixed, mat, rng, G)
+        ctx.bins = bins
+        ctx.mark_non_differentiable(G)
+        return mi, G
+
+    @staticmethod
+    def backward(ctx, gout, _gG):
+        if not ctx.needs_input_grad[2]:
+            return None, None, None, None, None
+        lib = _lib.load()
+        moving, fixed, mat, rng, G = ctx.saved_tensors
+        gout = _prep(gout)
+        N, _, D, H, W = moving.shape
+        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, ctx.bins, D, H, W)), dtype=torch.uint8, device=moving.device)
+        dmat = torch.empty_like(mat)
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": 8.0 * N * D * H * W}
+        check(lib.kmh_warp_mi_bwd(_p(moving), _p(fixed), _p(mat), _p(rng), _p(G), _p(gout), N, D, H, W, ctx.bins, _p(ws),
+                                  _p(dmat), _stream()), "kmh_warp_mi_bwd")
+        return None, None, dmat, None, None
+
+
+def _warp_mi(moving, fixed, mat, bins, ranges):
+    bins = _warp_mi_check(moving, fixed, mat, bins, ranges)
+    moving, fixed = moving.detach().contiguous(), fixed.detach().contiguous()
+    rng = _mi_ranges(moving, fixed, bins) if ranges is None else ranges.detach().contiguous()
+    return _WarpMI.apply(moving, fixed, mat.contiguous(), rng, bins)
+
+
+def warp_mutual_information(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None) -> Tensor:
+    """Mutual information (nats) of `fixed` and `moving` warped by `mat`, per sample -> (N,), in one pass: by definition
+    mutual_information(align_img(affine_grid(mat, dims), moving), fixed, range_a=range of moving, range_b=range of fixed) sample by
+    sample, with the same joint table bit for bit, but neither the grid nor the warped volume is stored.  moving, fixed:
+    (N, 1, D, H, W) float32 on the current GPU (data: no gradient); mat (N, 3, 4) as affine_grid takes it, differentiable;
+    ranges: mi_ranges(moving, fixed, bins), computed here when None.  Two calls give bit-identical values and gradients; a batch
+    equals its samples run one by one."""
+    return _warp_mi(moving, fixed, mat, bins, ranges)[0]
+
+
+def _warp_mi_table(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None):
+    """(MI (N,), G (N, bins, bins)) of warp_mutual_information without autograd: _mi_table's counterpart."""
+    mi, G = _warp_mi(moving, fixed, mat.detach(), bins, ranges)
+    return mi, G
+
+
+# --------------------------------------------------------------------------
 # trilinear resize (F.interpolate(mode="trilinear", align_corners=False); keymorph/model.py:576-588)
 # --------------------------------------------------------------------------
 def resize_out_size(n_in: int, scale_factor: float) -> int:
