@@ -146,6 +146,8 @@ int kmh_mi_bwd(const float* a, const float* b, const float* rng, const float* G,
 /* kmh_mi_hist's ranges alone: rng (N, 4) out, ws 16 N bytes. */
 int kmh_mi_range(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
                  int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream);
+/* kmh_mi_hist with the ranges given on the device: rng (N, 4) in, as kmh_mi_range wrote it; kmh_mi_final and kmh_mi_bwd follow. */
+int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws, void* stream);
 
 /* ---- mutual information of a fixed volume and a moving volume warped by a matrix, fused (csrc/warp_mi.hip) ---- */
 /* By definition MI(grid_sample3d(moving, affine_grid(mat)), fixed) with the ranges rng = kmh_mi_range(moving, fixed): moving,
@@ -577,6 +579,23 @@ int kmh_field_invert(const float* grid, const float* start, float* out, unsigned
 /* disp (N,3,D,H,W), channels (z,y,x), in voxels = (grid - Ids) * size / 2 (what kmh_jacobian_det reads), and back. */
 int kmh_field_to_displacement(const float* grid, float* disp, int N, int D, int H, int W, void* stream);
 int kmh_field_from_displacement(const float* disp, float* grid, int N, int D, int H, int W, void* stream);
+
+/* ---- free-form deformation: a grid from a lattice of cubic B-spline control points (csrc/bspline.hip states the definition) ----
+ * ctrl (N,3,Cz,Cy,Cx), channel k = displacement of grid component k (x,y,z), normalised; an axis of S voxels and C >= 4 control
+ * points has C - 3 cells over [-1, 1].  out (N,D,H,W,3) = base + the spline, base = Ids of the fields section (mat NULL) or what
+ * kmh_affine_grid_fwd writes for mat (N,3,4).  kmh_bspline_grid_bwd: dctrl = the transposed operator applied to dgrid, no
+ * atomics, bit-identical from run to run, a batch equals its samples; ws = kmh_bspline_grid_ws_bytes() bytes.
+ * -22: a C below 4, an empty shape, N outside 1..65535, 2^31 voxels or control points per channel or more. */
+int kmh_bspline_grid_fwd(const float* ctrl, const float* mat, float* out, int N, int D, int H, int W, int Cz, int Cy, int Cx,
+                         void* stream);
+size_t kmh_bspline_grid_ws_bytes(int N, int D, int H, int W, int Cz, int Cy, int Cx);
+int kmh_bspline_grid_bwd(const float* dgrid, float* dctrl, int N, int D, int H, int W, int Cz, int Cy, int Cx, void* ws,
+                         void* stream);
+/* out[n] = sum over the three lattice axes of the mean of (q[i-1] - 2 q[i] + q[i+1])^2 over that axis' differenced tensor,
+ * q (N,3,Cz,Cy,Cx) with every C >= 4; dq = gout[n] d out[n] / dq.  Fixed-order sums; ws = kmh_bspline_bending_ws_bytes(N). */
+size_t kmh_bspline_bending_ws_bytes(int N);
+int kmh_bspline_bending_fwd(const float* q, float* out, int N, int Cz, int Cy, int Cx, void* ws, void* stream);
+int kmh_bspline_bending_bwd(const float* q, const float* gout, float* dq, int N, int Cz, int Cy, int Cx, void* stream);
 
 #ifdef __cplusplus
 }

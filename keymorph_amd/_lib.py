@@ -70,6 +70,7 @@ PROTOS = {
     "kmh_mi_final": (_i, [_f, _f, _i, _ll, _i, _f, _f, _f]),
     "kmh_mi_bwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
     "kmh_mi_range": (_i, [_f, _f, _i, _ll, _i, _i, C.c_float, C.c_float, _i, C.c_float, C.c_float, _f, _f, _f]),
+    "kmh_mi_hist_ranges": (_i, [_f, _f, _f, _i, _ll, _i, _f, _f]),
     "kmh_warp_mi_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_warp_mi_hist": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
     "kmh_warp_mi_bwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
@@ -167,6 +168,12 @@ PROTOS = {
     "kmh_field_invert": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, C.c_float, _i, _f, _f]),
     "kmh_field_to_displacement": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "kmh_field_from_displacement": (_i, [_f, _f, _i, _i, _i, _i, _f]),
+    "kmh_bspline_grid_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_bspline_grid_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "kmh_bspline_grid_bwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f]),
+    "kmh_bspline_bending_ws_bytes": (_sz, [_i]),
+    "kmh_bspline_bending_fwd": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
+    "kmh_bspline_bending_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
 }
 
 _lib = None

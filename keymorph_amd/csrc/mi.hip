@@ -260,6 +260,19 @@ KMH_API size_t kmh_mi_ws_bytes(int N, int bins) {
   return (size_t)N * 16 + (size_t)N * bins * bins * sizeof(unsigned long long);
 }
 
+static void mi_hist_launch(const float* a, const float* b, const float* rng, int N, long long V, int bins,
+                           unsigned long long* hist, hipStream_t s) {
+  constexpr int chunk = kSteps * kWaves;                             // steps per workgroup between two flushes
+  const long long R = (V + kWave - 1) / kWave;
+  long long nb = (R + 2 * chunk - 1) / (2 * chunk);
+  if (nb > kMaxBlocks) nb = kMaxBlocks;
+  long long per = (R + nb - 1) / nb;
+  per = (per + chunk - 1) / chunk * chunk;
+  nb = (R + per - 1) / per;
+  mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
+      a, b, rng, V, R, per, bins, hist);
+}
+
 /* a, b: (N, V) float32 contiguous.  has_range_x != 0: image x uses the range (lo_x, hi_x) instead of its own minimum and maximum.
  * rng: (N, 4) floats out = (lo_a, s_a, lo_b, s_b).  ws: kmh_mi_ws_bytes(N, bins) bytes, holds the joint table for kmh_mi_final. */
 KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
@@ -276,15 +289,19 @@ KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int 
     mi_range_kernel<<<dim3((unsigned)nb, (unsigned)N, 2), TPB, 0, s>>>(a, b, V, has_range_a, has_range_b, keys);
   }
   mi_scale_kernel<<<ceil_div(2 * N, 64), 64, 0, s>>>(keys, N, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, rng);
-  constexpr int chunk = kSteps * kWaves;                             // steps per workgroup between two flushes
-  const long long R = (V + kWave - 1) / kWave;
-  long long nb = (R + 2 * chunk - 1) / (2 * chunk);
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  long long per = (R + nb - 1) / nb;
-  per = (per + chunk - 1) / chunk * chunk;
-  nb = (R + per - 1) / per;
-  mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
-      a, b, rng, V, R, per, bins, hist);
+  mi_hist_launch(a, b, rng, N, V, bins, hist, s);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* kmh_mi_hist with the ranges GIVEN on the device: rng (N, 4) in, as kmh_mi_range or kmh_mi_hist wrote it (values outside a range
+ * are taken at its ends).  For a caller that scores many warps of one pair without the host ever reading a range. */
+KMH_API int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws,
+                               void* stream) {
+  if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, kmh_mi_ws_bytes(N, bins), s);
+  if (e != hipSuccess) return (int)e;
+  mi_hist_launch(a, b, rng, N, V, bins, (unsigned long long*)((char*)ws + (size_t)N * 16), s);
   return KMH_LAUNCH_CHECK();
 }
 

@@ -1,0 +1,85 @@
+"""Deformable intensity registration on the GPU: a cubic B-spline free-form deformation (ops.bspline_grid) on top of an affine
+matrix, fitted by multi-resolution Mattes mutual information under Adam with a bending penalty on the control lattice -- the
+deformable counterpart of io.register_intensity, what elastix and ANTs are used for beside KeyMorph's thin-plate splines.
+
+Conventions.  ctrl (N, 3, Cz, Cy, Cx) is what ops.bspline_grid takes: channel k is the displacement of grid component k, in the
+grid's order (x, y, z) and normalised units, on the lattice ops.bspline_lattice_shape(dims, control_spacing).  Normalised
+displacements on a normalised lattice mean the same thing at every pyramid level, so ONE parameter tensor serves all levels
+without refitting; per level it is stepped in that level's voxels (q_l = ctrl (W_l, H_l, D_l) / 2), so that the learning rate and
+the bending weight are in voxels as register_intensity's are.  `mat` (N, 3, 4) is what ops.affine_grid takes."""
+import torch
+
+from .intensity import mat_to_voxel, register_intensity, voxel_to_mat
+
+
+def _per_channel(q, factors):
+    """q (N, 3, ...) times one Python scalar per channel (x, y, z): no tensor is made from a host list."""
+    return torch.stack([q[:, k] * float(factors[k]) for k in range(3)], dim=1)
+
+
+def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
+    """align_img(ops.bspline_grid(ctrl, dims, mat), x, mode): x (N, C, D, H, W) resampled through the free-form deformation."""
+    from .. import ops
+    from ..utils import align_img
+    return align_img(ops.bspline_grid(ctrl, x.shape[2:], mat), x, mode)
+
+
+def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1):
+    """ctrl (N, 3, Cz, Cy, Cx) on the lattice ops.bspline_lattice_shape(dims, control_spacing) such that
+    apply_bspline(moving, ctrl, mat) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual
+    information.  mat (N, 3, 4): the affine part, data; None: register_intensity(fixed, moving, "affine", bins=bins,
+    shrink=shrink) is run first (read it back from there if you need it, or pass your own).
+
+    Over the trilinear pyramid (size // shrink per level; a level with an axis shorter than 16 is skipped) `iters` Adam steps per
+    level, `lr` in voxels of the level, on
+        sum_n [ -mutual_information(align_img(bspline_grid(ctrl_l, ldims, mat_l), m_l), f_l, bins, ranges)
+                + bending * bspline_bending(q_l) ],
+    q_l the control displacements in voxels of the level (it starts at the previous level's answer), ctrl_l = q_l (2 / W_l,
+    2 / H_l, 2 / D_l), mat_l the matrix of the same voxel-space map at the level's size, and the intensity ranges from
+    ops.mi_ranges once per level.  The loss is a sum, so every sample is optimised on its own.  The penalty is what keeps the
+    border control points, which see few voxels, from chasing interpolation blur.
+
+    Nothing inside the loop waits for the GPU."""
+    from .. import ops
+    from ..utils import align_img, resize_trilinear
+    if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
+        raise ValueError(f"register_bspline: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
+                         f"{tuple(moving.shape)}")
+    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
+    if mat is not None and tuple(mat.shape) != (N, 3, 4):
+        raise ValueError(f"register_bspline: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
+    lattice = ops.bspline_lattice_shape(dims, control_spacing)
+    with torch.inference_mode(False), torch.enable_grad():
+        fixed = fixed.clone() if fixed.is_inference() else fixed.detach()
+        moving = moving.clone() if moving.is_inference() else moving.detach()
+        if mat is None:
+            mat = register_intensity(fixed, moving, "affine", bins=bins, shrink=shrink)
+        mat = mat.clone() if mat.is_inference() else mat.detach()
+        q = torch.zeros((N, 3, *lattice), dtype=torch.float32, device=fixed.device)      # voxels of the full size, (x, y, z)
+        with torch.no_grad():
+            L, t = mat_to_voxel(mat, dims)
+        for sh in shrink:
+            ldims = tuple(n // int(sh) for n in dims)
+            if min(ldims) < 16:
+                continue
+            ratio = [n / l for n, l in zip(dims, ldims)]              # (z, y, x)
+            with torch.no_grad():
+                f_l, m_l = (fixed, moving) if ldims == dims else (resize_trilinear(fixed, size=ldims),
+                                                                  resize_trilinear(moving, size=ldims))
+                rng = ops.mi_ranges(m_l, f_l, bins)
+                L_l = torch.stack([torch.stack([L[:, k, j] * (ratio[j] / ratio[k]) for j in range(3)], dim=1) for k in range(3)],
+                                  dim=1)
+                t_l = torch.stack([t[:, k] / ratio[k] for k in range(3)], dim=1)
+                mat_l = voxel_to_mat(L_l, t_l, ldims)
+                q_l = _per_channel(q, [1.0 / ratio[2 - k] for k in range(3)])
+            q_l.requires_grad_(True)
+            to_norm = [2.0 / ldims[2 - k] for k in range(3)]
+            opt = torch.optim.Adam([q_l], lr=lr)
+            for _ in range(iters):
+                opt.zero_grad(set_to_none=True)
+                warped = align_img(ops.bspline_grid(_per_channel(q_l, to_norm), ldims, mat_l), m_l)
+                loss = (bending * ops.bspline_bending(q_l) - ops.mutual_information(warped, f_l, bins, ranges=rng)).sum()
+                loss.backward()
+                opt.step()
+            q = _per_channel(q_l.detach(), [ratio[2 - k] for k in range(3)])
+        return _per_channel(q, [2.0 / dims[2 - k] for k in range(3)])

@@ -459,3 +459,11 @@ class WarpMILoss(torch.nn.Module):
 
     def forward(self, moving, fixed, mat, ranges=None):
         return -ops.warp_mutual_information(moving, fixed, mat, self.bins, ranges).mean()
+
+
+class BendingLoss(torch.nn.Module):
+    """Mean over the batch of ops.bspline_bending(q): the squared second differences of a (N, 3, Cz, Cy, Cx) control lattice along
+    its three axes, the smoothness penalty of a free-form deformation (ops.bspline_grid)."""
+
+    def forward(self, q):
+        return ops.bspline_bending(q).mean()

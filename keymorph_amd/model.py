@@ -359,16 +359,20 @@ class KeyMorph(nn.Module):
 # reference never shipped): multi-resolution mutual-information registration, io.register_intensity, behind KeyMorph's call.
 # ----------------------------------------------------------------------------------------------------------------------
 class IntensityRegistration(nn.Module):
-    """model(img_f, img_m, transform_type="translation" | "rigid" | "affine" | [..], num_resolutions_for_itkelastix=None,
-    **ignored) -> {type: {"grid" (N, D, H, W, 3), "matrix" (N, 3, 4) as ops.affine_grid takes it, "mi" (N,) the mutual
-    information reached, "time"}}.  No parameters.  num_resolutions_for_itkelastix = k means the pyramid 2^(k-1) .. 1
-    (None: 4, 2, 1)."""
+    """model(img_f, img_m, transform_type="translation" | "rigid" | "affine" | "bspline" | [..],
+    num_resolutions_for_itkelastix=None, **ignored) -> {type: {"grid" (N, D, H, W, 3), "matrix" (N, 3, 4) as ops.affine_grid
+    takes it, "mi" (N,) the mutual information reached, "time"}}.  No parameters.  num_resolutions_for_itkelastix = k means the
+    pyramid 2^(k-1) .. 1 (None: 4, 2, 1).
+    "bspline": the free-form deformation of io.register_bspline on top of the affine answer; its entry has "ctrl"
+    (N, 3, Cz, Cy, Cx) in addition, "matrix" is the affine it started from, "grid" = ops.bspline_grid(ctrl, dims, matrix) and
+    "mi" = ops.mutual_information of the warped pair."""
 
-    supported_transform_type = ("translation", "rigid", "affine")
+    supported_transform_type = ("translation", "rigid", "affine", "bspline")
 
-    def __init__(self, bins=32, iters=30, lr=0.25):
+    def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1):
         super().__init__()
         self.bins, self.iters, self.lr = bins, iters, lr
+        self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
         from . import ops
@@ -384,6 +388,18 @@ class IntensityRegistration(nn.Module):
         result_dict = {}
         for align_type_str in transform_type:
             start_time = time.time()
+            if align_type_str == "bspline":
+                from .io.bspline import register_bspline
+                from .utils import align_img
+                mat = register_intensity(img_f, img_m, "affine", bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
+                ctrl = register_bspline(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending,
+                                        bins=self.bins, shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr)
+                with torch.no_grad():
+                    grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
+                    mi = ops.mutual_information(align_img(grid, img_m), img_f, self.bins)
+                result_dict[align_type_str] = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": mi,
+                                               "time": time.time() - start_time}
+                continue
             mat = register_intensity(img_f, img_m, align_type_str, bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
             with torch.no_grad():
                 grid = ops.affine_grid(mat, img_f.shape[2:])

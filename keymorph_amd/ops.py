@@ -391,6 +391,106 @@ def tps_grid(theta: Tensor, ctrl: Tensor, shape: Sequence[int]) -> Tensor:
     return _TpsGrid.apply(theta, ctrl, D, H, W)
 
 
+# --------------------------------------------------------------------------
+# free-form deformation: cubic B-spline control lattice -> grid, and the lattice's bending penalty (csrc/bspline.hip)
+# --------------------------------------------------------------------------
+def bspline_lattice_shape(shape: Sequence[int], spacing: int) -> Tuple[int, int, int]:
+    """(Cz, Cy, Cx) of the control lattice with one cell per `spacing` voxels: ceil(n / spacing) + 3 per axis."""
+    spacing = int(spacing)
+    dims = tuple(int(n) for n in shape)
+    if len(dims) != 3 or min(dims) < 1 or spacing < 1:
+        raise ValueError(f"bspline_lattice_shape: expected three positive sizes and a positive spacing, got {tuple(shape)}, {spacing}")
+    return tuple(-(-n // spacing) + 3 for n in dims)
+
+
+def _lattice_check(t, name, who):
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise _lib.KeymorphHipError(f"{who}: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
+    if t.device.index != torch.cuda.current_device():
+        raise _lib.KeymorphHipError(f"{who}: {name} is on {t.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+    if t.dim() != 5 or t.shape[0] < 1 or t.shape[1] != 3 or min(t.shape[2:]) < 4:
+        raise ValueError(f"{who}: {name} must be (N, 3, Cz, Cy, Cx) with every C >= 4, got {tuple(t.shape)}")
+
+
+class _BsplineGrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctrl, mat, D, H, W):
+        lib = _lib.load()
+        N, _, Cz, Cy, Cx = ctrl.shape
+        out = torch.empty((N, D, H, W, 3), dtype=torch.float32, device=ctrl.device)
+        if _lib.profiler.enabled:  # 12 B written per voxel
+            _lib.profiler.meta = {"bytes": 12.0 * N * D * H * W}
+        check(lib.kmh_bspline_grid_fwd(_p(ctrl), _p(mat), _p(out), N, D, H, W, Cz, Cy, Cx, _stream()), "kmh_bspline_grid_fwd")
+        ctx.dims = (N, D, H, W, Cz, Cy, Cx)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        N, D, H, W, Cz, Cy, Cx = ctx.dims
+        g = _prep(g)
+        dctrl = torch.empty((N, 3, Cz, Cy, Cx), dtype=torch.float32, device=g.device)
+        ws = workspace(int(lib.kmh_bspline_grid_ws_bytes(*ctx.dims)), g.device, "bspline_bwd")
+        if _lib.profiler.enabled:  # 12 B read per voxel
+            _lib.profiler.meta = {"bytes": 12.0 * N * D * H * W}
+        check(lib.kmh_bspline_grid_bwd(_p(g), _p(dctrl), *ctx.dims, _p(ws), _stream()), "kmh_bspline_grid_bwd")
+        return dctrl, None, None, None, None
+
+
+def bspline_grid(ctrl: Tensor, shape: Sequence[int], mat: Optional[Tensor] = None) -> Tensor:
+    """The sampling grid (N, D, H, W, 3) of a free-form deformation: ctrl (N, 3, Cz, Cy, Cx) float32 on the current GPU, every
+    C >= 4, channel k = the displacement of grid component k, in the grid's own order (x, y, z) and normalised units, at the
+    control points of a uniform cubic B-spline lattice with C - 3 cells over [-1, 1] per axis:
+    voxel centre g = (2 i + 1) / S - 1, u = (g + 1) (C - 3) / 2, cell = floor(u), t = u - cell, weights B0..B3(t) on control points
+    cell .. cell + 3, and out = base + sum_{c,b,a} Bz_c By_b Bx_a ctrl[:, :, cz + c, cy + b, cx + a].
+    base = fields.identity_grid (mat None) or exactly ops.affine_grid(mat, shape) for mat (N, 3, 4).  Differentiable in ctrl only
+    (mat is data: one that requires grad raises); two calls give bit-identical grids and gradients, a batch equals its samples."""
+    _lattice_check(ctrl, "ctrl", "bspline_grid")
+    dims = tuple(int(s) for s in shape)
+    if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] >= 1 << 31:
+        raise ValueError(f"bspline_grid: shape must be three positive sizes (D, H, W) with fewer than 2^31 voxels, got {tuple(shape)}")
+    if mat is not None:
+        if not isinstance(mat, Tensor) or not mat.is_cuda or mat.device != ctrl.device:
+            raise _lib.KeymorphHipError("bspline_grid: mat is not on ctrl's GPU (no CPU fallback)")
+        if mat.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("bspline_grid: mat requires grad, and bspline_grid is differentiable in ctrl only: pass mat.detach()")
+        if mat.dtype != torch.float32 or tuple(mat.shape) != (ctrl.shape[0], 3, 4):
+            raise ValueError(f"bspline_grid: mat must be float32 ({ctrl.shape[0]}, 3, 4), got {mat.dtype} {tuple(mat.shape)}")
+        mat = mat.detach().contiguous()
+    return _BsplineGrid.apply(ctrl.contiguous(), mat, *dims)
+
+
+class _BsplineBending(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q):
+        N, _, Cz, Cy, Cx = q.shape
+        out = torch.empty((N,), dtype=torch.float32, device=q.device)
+        lib = _lib.load()
+        ws = workspace(int(lib.kmh_bspline_bending_ws_bytes(N)), q.device, "bspline_bending")
+        check(lib.kmh_bspline_bending_fwd(_p(q), _p(out), N, Cz, Cy, Cx, _p(ws), _stream()), "kmh_bspline_bending_fwd")
+        ctx.save_for_backward(q)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (q,) = ctx.saved_tensors
+        N, _, Cz, Cy, Cx = q.shape
+        g = _prep(g)
+        dq = torch.empty_like(q)
+        check(_lib.load().kmh_bspline_bending_bwd(_p(q), _p(g), _p(dq), N, Cz, Cy, Cx, _stream()), "kmh_bspline_bending_bwd")
+        return dq
+
+
+def bspline_bending(q: Tensor) -> Tensor:
+    """(N,): per sample, the sum over the three lattice axes of the mean of (q[i - 1] - 2 q[i] + q[i + 1])^2 over that axis'
+    differenced tensor; q (N, 3, Cz, Cy, Cx) float32 on the current GPU, every C >= 4, any units.  0 for a lattice that is linear
+    in its indices.  Differentiable; fixed-order sums (bit-identical runs, a batch equals its samples)."""
+    _lattice_check(q, "q", "bspline_bending")
+    return _BsplineBending.apply(q.contiguous())
+
+
 class _TpsPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, ctrl, pts):
@@ -651,28 +751,32 @@ def lc2(us: Tensor, mr: Tensor, patch: int, radii: Sequence[int], alpha: float =
 MI_MIN_BINS, MI_MAX_BINS = 8, 64
 
 
-def _mi_forward(a, b, bins, range_a, range_b):
-    """(mi (N,), rng (N, 4), G (N, bins, bins)) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise."""
+def _mi_forward(a, b, bins, range_a, range_b, ranges=None):
+    """(mi (N,), rng (N, 4), G (N, bins, bins)) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise.
+    ranges: a checked (N, 4) device tensor as mi_ranges returns it, used instead of range_a / range_b."""
     lib = _lib.load()
     N, V = a.shape[0], a[0].numel()
     dev = a.device
     ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=dev)
-    rng = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    rng = torch.empty((N, 4), dtype=torch.float32, device=dev) if ranges is None else ranges
     mi = torch.empty((N,), dtype=torch.float32, device=dev)
     G = torch.empty((N, bins, bins), dtype=torch.float32, device=dev)
     ra, rb = range_a or (0.0, 0.0), range_b or (0.0, 0.0)
     if _lib.profiler.enabled:  # 8 B read per voxel
         _lib.profiler.meta = {"bytes": 8.0 * N * V}
-    check(lib.kmh_mi_hist(_p(a), _p(b), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None), rb[0],
-                          rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_hist")
+    if ranges is not None:
+        check(lib.kmh_mi_hist_ranges(_p(a), _p(b), _p(rng), N, V, bins, _p(ws), _stream()), "kmh_mi_hist_ranges")
+    else:
+        check(lib.kmh_mi_hist(_p(a), _p(b), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None), rb[0],
+                              rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_hist")
     check(lib.kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
     return mi, rng, G
 
 
 class _MI(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, bins, range_a, range_b):
-        mi, rng, G = _mi_forward(a, b, bins, range_a, range_b)
+    def forward(ctx, a, b, bins, range_a, range_b, ranges=None):
+        mi, rng, G = _mi_forward(a, b, bins, range_a, range_b, ranges)
         ctx.save_for_backward(a, b, rng, G)
         ctx.bins = bins
         return mi
@@ -688,7 +792,7 @@ class _MI(torch.autograd.Function):
         if _lib.profiler.enabled:  # 8 B read and 4 B written per voxel and gradient
             _lib.profiler.meta = {"bytes": (8.0 + 4.0 * ((da is not None) + (db is not None))) * N * V}
         check(lib.kmh_mi_bwd(_p(a), _p(b), _p(rng), _p(G), _p(gout), N, V, ctx.bins, _p(da), _p(db), _stream()), "kmh_mi_bwd")
-        return da, db, None, None, None
+        return da, db, None, None, None, None
 
 
 def _mi_check(a, b, bins, range_a, range_b):
@@ -717,12 +821,24 @@ def _mi_check(a, b, bins, range_a, range_b):
     return a.contiguous(), b.contiguous(), int(bins), out[0], out[1]
 
 
-def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None) -> Tensor:
+def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges: Optional[Tensor] = None) -> Tensor:
     """Mutual information (nats) of two (N, 1, D, H, W) float32 volumes on the current GPU, per sample -> (N,), differentiable in
     both.  Parzen-window joint histogram with the cubic B-spline and Mattes' padding: per sample and image, u = (x - lo) s + 1 with
     s = (bins - 3) / (hi - lo) over the image's own minimum and maximum (no gradient through them), or over `range_x = (lo, hi)`
     (values outside are taken at the range's ends); a constant image has s = 0, MI = 0 and zero gradients.  Two calls give
-    bit-identical values and gradients; a batch equals its samples run one by one."""
+    bit-identical values and gradients; a batch equals its samples run one by one.  `ranges`: instead of range_a / range_b, the
+    (N, 4) device tensor mi_ranges(a0, b) returns, per sample, for a volume a0 whose range bounds a's (a = a warp of a0): the
+    host never reads a range (io.register_bspline)."""
+    if ranges is not None:
+        if range_a is not None or range_b is not None:
+            raise ValueError("mutual_information: give either range_a / range_b or ranges, not both")
+        a, b, bins, _, _ = _mi_check(a, b, bins, None, None)
+        if not isinstance(ranges, Tensor) or not ranges.is_cuda or ranges.device != a.device:
+            raise _lib.KeymorphHipError("mutual_information: ranges is not on the inputs' GPU (no CPU fallback)")
+        if ranges.dtype != torch.float32 or tuple(ranges.shape) != (a.shape[0], 4):
+            raise ValueError(f"mutual_information: ranges must be float32 ({a.shape[0]}, 4) as mi_ranges returns them, got "
+                             f"{ranges.dtype} {tuple(ranges.shape)}")
+        return _MI.apply(a, b, bins, None, None, ranges.detach().contiguous())
     return _MI.apply(*_mi_check(a, b, bins, range_a, range_b))
 
 
