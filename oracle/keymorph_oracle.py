@@ -57,7 +57,7 @@ def center_of_mass(feat: Tensor, indexing: str = "ij") -> Tensor:
 
     feat (n, K, *spatial) -> (n, K, dim) in [-1, 1].
     """
-    v = feat.clamp_min(0)
+    v = F.relu(feat)  # keymorph/layers.py:97: no gradient at exact zeros (clamp_min(0) passes it there)
     nd = v.dim() - 2
     out = []
     for ax in range(nd):  # ax 0 = z (or y in 2D) ... last = x

@@ -337,6 +337,8 @@ def test_tps_points_fwd_bwd():
 @pytest.mark.parametrize("kind", ["affine", "rigid"])
 @pytest.mark.parametrize("weighted", [False, True])
 def test_matrix_fit_fwd_bwd(kind, weighted):
+    """one generic, well-conditioned cloud against the fp32 oracle; reflections, equal singular values, rank edges, K past the
+    workgroup, offsets and the other weightings are in tests/test_fits_edges_gpu.py, against fp64"""
     g = gen(10)
     K = 50
     pf = torch.rand(2, K, 3, generator=g) * 1.6 - 0.8
