@@ -597,6 +597,18 @@ size_t kmh_bspline_bending_ws_bytes(int N);
 int kmh_bspline_bending_fwd(const float* q, float* out, int N, int Cz, int Cy, int Cx, void* ws, void* stream);
 int kmh_bspline_bending_bwd(const float* q, const float* gout, float* dq, int N, int Cz, int Cy, int Cx, void* stream);
 
+/* ---- local normalised cross-correlation (csrc/lncc.hip states the definition) ---- */
+/* a, b: (N, D, H, W) float32 contiguous, fewer than 2^31 voxels per sample; window odd in [3, 15], truncated at the border.
+ * out[n] = mean over the voxels of cross^2 / (va vb + eps) of the window sums.  kmh_lncc_bwd: da = gout[n] d out[n] / da, db
+ * likewise, either may be NULL.  ws: kmh_lncc_ws_bytes bytes (one float per tile and sample, and the backward's five coefficient
+ * fields: 2.5 times the two inputs); the backward reads nothing the forward left there.  No atomics: runs repeat bit for bit and
+ * a batch equals its samples.  -22 for an even or out-of-range window, N < 1, an empty volume or a null pointer. */
+size_t kmh_lncc_ws_bytes(int N, int D, int H, int W, int window);
+int kmh_lncc_fwd(const float* a, const float* b, int N, int D, int H, int W, int window, float eps, float* out, void* ws,
+                 void* stream);
+int kmh_lncc_bwd(const float* a, const float* b, const float* gout, int N, int D, int H, int W, int window, float eps,
+                 float* da, float* db, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

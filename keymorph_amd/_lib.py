@@ -174,6 +174,9 @@ PROTOS = {
     "kmh_bspline_bending_ws_bytes": (_sz, [_i]),
     "kmh_bspline_bending_fwd": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
     "kmh_bspline_bending_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_lncc_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kmh_lncc_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f]),
+    "kmh_lncc_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f, _f]),
 }
 
 _lib = None

@@ -24,7 +24,8 @@ def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
     return align_img(ops.bspline_grid(ctrl, x.shape[2:], mat), x, mode)
 
 
-def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1):
+def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
+                     metric="mi", window=9):
     """ctrl (N, 3, Cz, Cy, Cx) on the lattice ops.bspline_lattice_shape(dims, control_spacing) such that
     apply_bspline(moving, ctrl, mat) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual
     information.  mat (N, 3, 4): the affine part, data; None: register_intensity(fixed, moving, "affine", bins=bins,
@@ -39,6 +40,10 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     ops.mi_ranges once per level.  The loss is a sum, so every sample is optimised on its own.  The penalty is what keeps the
     border control points, which see few voxels, from chasing interpolation blur.
 
+    metric="lncc": the similarity is ops.local_ncc(warped, f_l, window) instead of the mutual information (no ranges are
+    computed): the local metric of ANTs and VoxelMorph, for one modality under a smooth bias field, which a global histogram
+    cannot see.  The default affine start stays register_intensity's.
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     from ..utils import align_img, resize_trilinear
@@ -48,6 +53,8 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     if mat is not None and tuple(mat.shape) != (N, 3, 4):
         raise ValueError(f"register_bspline: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
+    if metric not in ("mi", "lncc"):
+        raise ValueError(f"register_bspline: metric must be 'mi' or 'lncc', got {metric!r}")
     lattice = ops.bspline_lattice_shape(dims, control_spacing)
     with torch.inference_mode(False), torch.enable_grad():
         fixed = fixed.clone() if fixed.is_inference() else fixed.detach()
@@ -66,7 +73,7 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
             with torch.no_grad():
                 f_l, m_l = (fixed, moving) if ldims == dims else (resize_trilinear(fixed, size=ldims),
                                                                   resize_trilinear(moving, size=ldims))
-                rng = ops.mi_ranges(m_l, f_l, bins)
+                rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
                 L_l = torch.stack([torch.stack([L[:, k, j] * (ratio[j] / ratio[k]) for j in range(3)], dim=1) for k in range(3)],
                                   dim=1)
                 t_l = torch.stack([t[:, k] / ratio[k] for k in range(3)], dim=1)
@@ -78,7 +85,11 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
             for _ in range(iters):
                 opt.zero_grad(set_to_none=True)
                 warped = align_img(ops.bspline_grid(_per_channel(q_l, to_norm), ldims, mat_l), m_l)
-                loss = (bending * ops.bspline_bending(q_l) - ops.mutual_information(warped, f_l, bins, ranges=rng)).sum()
+                if metric == "mi":
+                    sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
+                else:
+                    sim = ops.local_ncc(warped, f_l, window)
+                loss = (bending * ops.bspline_bending(q_l) - sim).sum()
                 loss.backward()
                 opt.step()
             q = _per_channel(q_l.detach(), [ratio[2 - k] for k in range(3)])

@@ -461,6 +461,19 @@ class WarpMILoss(torch.nn.Module):
         return -ops.warp_mutual_information(moving, fixed, mat, self.bins, ranges).mean()
 
 
+class LNCCLoss(torch.nn.Module):
+    """-mean over the batch of ops.local_ncc(pred, target, window, eps): the squared local normalised cross-correlation over
+    truncated window^3 cubes of (N, 1, D, H, W) float32 pairs; lower is better, differentiable in both inputs.  The mono-modal
+    similarity that survives a smooth bias field: LNCCLoss()(align_img(grid, img_m), img_f)."""
+
+    def __init__(self, window=9, eps=1e-5):
+        super().__init__()
+        self.window, self.eps = window, eps
+
+    def forward(self, pred, target):
+        return -ops.local_ncc(pred, target, self.window, self.eps).mean()
+
+
 class BendingLoss(torch.nn.Module):
     """Mean over the batch of ops.bspline_bending(q): the squared second differences of a (N, 3, Cz, Cy, Cx) control lattice along
     its three axes, the smoothness penalty of a free-form deformation (ops.bspline_grid)."""

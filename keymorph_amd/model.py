@@ -365,13 +365,19 @@ class IntensityRegistration(nn.Module):
     pyramid 2^(k-1) .. 1 (None: 4, 2, 1).
     "bspline": the free-form deformation of io.register_bspline on top of the affine answer; its entry has "ctrl"
     (N, 3, Cz, Cy, Cx) in addition, "matrix" is the affine it started from, "grid" = ops.bspline_grid(ctrl, dims, matrix) and
-    "mi" = ops.mutual_information of the warped pair."""
+    "mi" = ops.mutual_information of the warped pair.  metric="lncc": the "bspline" entry is fitted by local normalised
+    cross-correlation over window^3 cubes (io.register_bspline(metric="lncc")) and has "lncc" (N,) = ops.local_ncc of the warped pair
+    in addition; the matrix stages stay on mutual information."""
 
     supported_transform_type = ("translation", "rigid", "affine", "bspline")
 
-    def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1):
+    def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
+                 metric="mi", window=9):
         super().__init__()
+        if metric not in ("mi", "lncc"):
+            raise ValueError(f"IntensityRegistration: metric must be 'mi' or 'lncc', got {metric!r}")
         self.bins, self.iters, self.lr = bins, iters, lr
+        self.metric, self.window = metric, window
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
@@ -393,12 +399,17 @@ class IntensityRegistration(nn.Module):
                 from .utils import align_img
                 mat = register_intensity(img_f, img_m, "affine", bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
                 ctrl = register_bspline(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending,
-                                        bins=self.bins, shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr)
+                                        bins=self.bins, shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr,
+                                        metric=self.metric, window=self.window)
                 with torch.no_grad():
                     grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
-                    mi = ops.mutual_information(align_img(grid, img_m), img_f, self.bins)
-                result_dict[align_type_str] = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": mi,
-                                               "time": time.time() - start_time}
+                    warped = align_img(grid, img_m)
+                    mi = ops.mutual_information(warped, img_f, self.bins)
+                    lncc = ops.local_ncc(warped, img_f, self.window) if self.metric == "lncc" else None
+                result_dict[align_type_str] = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": mi}
+                if lncc is not None:
+                    result_dict[align_type_str]["lncc"] = lncc
+                result_dict[align_type_str]["time"] = time.time() - start_time
                 continue
             mat = register_intensity(img_f, img_m, align_type_str, bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
             with torch.no_grad():

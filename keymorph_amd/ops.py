@@ -958,6 +958,70 @@ def _warp_mi_table(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, r
 
 
 # --------------------------------------------------------------------------
+# local normalised cross-correlation (csrc/lncc.hip states the definition)
+# --------------------------------------------------------------------------
+LNCC_MIN_WINDOW, LNCC_MAX_WINDOW = 3, 15
+
+
+class _LNCC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, window, eps):
+        lib = _lib.load()
+        N, _, D, H, W = a.shape
+        ws = workspace(int(lib.kmh_lncc_ws_bytes(N, D, H, W, window)), a.device, "lncc")
+        out = torch.empty((N,), dtype=torch.float32, device=a.device)
+        if _lib.profiler.enabled:  # 8 B read per voxel
+            _lib.profiler.meta = {"bytes": 8.0 * a.numel()}
+        check(lib.kmh_lncc_fwd(_p(a), _p(b), N, D, H, W, window, eps, _p(out), _p(ws), _stream()), "kmh_lncc_fwd")
+        ctx.save_for_backward(a, b)
+        ctx.window, ctx.eps = window, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        a, b = ctx.saved_tensors
+        gout = _prep(gout)
+        N, _, D, H, W = a.shape
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        ws = workspace(int(lib.kmh_lncc_ws_bytes(N, D, H, W, ctx.window)), a.device, "lncc")
+        if _lib.profiler.enabled:  # per voxel: 8 B read and 20 B of fields written, 20 + 8 B read and 4 B written per gradient
+            _lib.profiler.meta = {"bytes": (56.0 + 4.0 * ((da is not None) + (db is not None))) * a.numel()}
+        check(lib.kmh_lncc_bwd(_p(a), _p(b), _p(gout), N, D, H, W, ctx.window, ctx.eps, _p(da), _p(db), _p(ws), _stream()),
+              "kmh_lncc_bwd")
+        return da, db, None, None
+
+
+def local_ncc(a: Tensor, b: Tensor, window: int = 9, eps: float = 1e-5) -> Tensor:
+    """Local normalised cross-correlation of two (N, 1, D, H, W) float32 volumes on the current GPU, per sample -> (N,) in [0, 1]
+    (higher is better), differentiable in both: the mean over the voxels of cross^2 / (va vb + eps) with cross, va, vb the
+    covariance and the variances (times the count) over the in-bounds part of the window^3 cube around the voxel -- windows are
+    truncated at the border, so the value does not change when a constant is added to a volume.  window odd in [3, 15]; eps is
+    meant for volumes scaled to about [0, 1].  Two calls give bit-identical values and gradients; a batch equals its samples run
+    one by one."""
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, Tensor) or not t.is_cuda:
+            raise _lib.KeymorphHipError(f"local_ncc: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
+                                        "(no CPU fallback)")
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.KeymorphHipError(f"local_ncc: {name} is on {t.device} but the current device is "
+                                        f"cuda:{torch.cuda.current_device()}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"local_ncc: {name} must be float32, got {t.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"local_ncc: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0 or a[0].numel() >= 1 << 31:
+        raise ValueError(f"local_ncc: expected two non-empty (N, 1, D, H, W) volumes of fewer than 2^31 voxels each, got "
+                         f"{tuple(a.shape)}")
+    if int(window) != window or not LNCC_MIN_WINDOW <= window <= LNCC_MAX_WINDOW or window % 2 == 0:
+        raise ValueError(f"local_ncc: window must be an odd integer in [{LNCC_MIN_WINDOW}, {LNCC_MAX_WINDOW}], got {window}")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"local_ncc: eps must be >= 0, got {eps}")
+    return _LNCC.apply(a.contiguous(), b.contiguous(), int(window), float(eps))
+
+
+# --------------------------------------------------------------------------
 # trilinear resize (F.interpolate(mode="trilinear", align_corners=False); keymorph/model.py:576-588)
 # --------------------------------------------------------------------------
 def resize_out_size(n_in: int, scale_factor: float) -> int:
