@@ -20,14 +20,11 @@
 // The second and third pass are one kernel (an axis contraction with the untouched axes flattened either side); their inputs
 // are 14 % and 2 % of dgrid at 256^3 with spacing 8.  Every pass accumulates in double and stores floats.
 #include "common.h"
-#include "grid_coords.h"      // lin, lin_step, affine_coord_chain: the base of a grid with a matrix is kmh_affine_grid_fwd's
+#include "grid_coords.h"      // lin, lin_step, affine_coord_chain: the base of a grid with a matrix is kmh_affine_grid_fwd's; ident
 
 namespace {
 
 constexpr int TPB = 256;
-
-// fields.hip's lattice identity, the same expression: (2 i + 1) / S - 1 as one rounded division of exact integers
-__device__ __forceinline__ float ident(int i, int S) { return (float)(2 * i + 1 - S) / (float)S; }
 
 struct LatW { int cell; float w[4]; };
 

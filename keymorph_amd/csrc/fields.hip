@@ -11,12 +11,10 @@
 // compose: HBM-bound, 12 B in + 12 B out per voxel plus the gathers (8 taps of 12 B from L2 / Infinity Cache).
 // invert: per-voxel Newton in registers, one gather round per step; bound by the latency of those rounds.
 // displacement: streaming, 24 B per voxel.
+#include "grid_coords.h"      // ident: the voxel-centre lattice, shared with bspline.hip
 #include "sampler_taps.h"
 
 namespace {
-
-// lattice identity along an axis of size S: (2 i + 1) / S - 1, as ONE rounded division of exact integers
-__device__ __forceinline__ float ident(int i, int S) { return (float)(2 * i + 1 - S) / (float)S; }
 
 struct Vox { int i, j, k; };
 __device__ __forceinline__ Vox vox_of(long long v, int H, int W) {

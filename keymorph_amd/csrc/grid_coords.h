@@ -1,6 +1,7 @@
 // The implicit identity grid and the affine map applied to it, shared by grids.hip (which writes the coordinates out) and
 // warp_mi.hip (which samples at them without ever storing them): both have to round identically, because one ulp of a
 // coordinate moves floor() to the neighbouring cell at lattice points (sampler_taps.h), so the expressions exist once, here.
+// Likewise the voxel-centre lattice (ident) of fields.hip and bspline.hip.
 #pragma once
 #include "common.h"
 
@@ -12,6 +13,9 @@ __device__ __forceinline__ float lin(int i, int n, float step) {
   return (i < n / 2) ? (-1.f + step * (float)i) : (1.f - step * (float)(n - 1 - i));
 }
 __host__ __device__ __forceinline__ float lin_step(int n) { return n > 1 ? 2.f / (float)(n - 1) : 0.f; }
+
+// the voxel-centre lattice (fields.identity_grid) along an axis of size S: (2 i + 1) / S - 1, as ONE rounded division of exact integers
+__device__ __forceinline__ float ident(int i, int S) { return (float)(2 * i + 1 - S) / (float)S; }
 
 // rows of M (3 x 4) are (z, y, x) outputs; the result is flipped to the (x, y, z) order grid_sample expects.
 // affine_coord is affine_grid_fwd_kernel's statement: under -ffp-contract=fast the compiler turns each row into

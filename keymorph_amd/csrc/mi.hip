@@ -28,7 +28,7 @@
 //                     writes MI_n and G.  A sample with s_a = 0 or s_b = 0 (a constant image) gets MI = 0 and G = 0 exactly.
 // mi_bwd_kernel       one lane per voxel: recomputes the taps, gathers the 16 entries of G from LDS, writes da and / or db.
 #include "common.h"
-#include "mi_taps.h"      // the window (taps) and the fixed-point format's constants: shared with warp_mi.hip
+#include "mi_taps.h"      // the window (taps), the fixed-point format's constants and the workspace's layout: shared with warp_mi.hip
 
 namespace {
 constexpr int TPB = 256;
@@ -132,6 +132,7 @@ __global__ __launch_bounds__(TPB) void mi_hist_kernel(const float* __restrict__ 
     for (int it = 0; it < kSteps; ++it) {
       const bool valid = (live >> it) & 1u;
       if (!__any(valid)) continue;                                    // wave-uniform
+      // hist_add's text (mi_taps.h), kept inline: as a call this kernel is rescheduled and measured slower (mi_taps.h has the figures)
       unsigned q[16];
       int key = -1;
       if (valid) {
@@ -257,20 +258,31 @@ bool mi_args_ok(const void* a, const void* b, int N, long long V, int B) {
 /* Workspace of kmh_mi_hist / kmh_mi_final: per sample four range keys and the B x B table of 64-bit sums. */
 KMH_API size_t kmh_mi_ws_bytes(int N, int bins) {
   if (N < 0 || bins < 0) return 0;
-  return (size_t)N * 16 + (size_t)N * bins * bins * sizeof(unsigned long long);
+  return ws_bytes(N, bins);
 }
 
-static void mi_hist_launch(const float* a, const float* b, const float* rng, int N, long long V, int bins,
-                           unsigned long long* hist, hipStream_t s) {
-  constexpr int chunk = kSteps * kWaves;                             // steps per workgroup between two flushes
-  const long long R = (V + kWave - 1) / kWave;
-  long long nb = (R + 2 * chunk - 1) / (2 * chunk);
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  long long per = (R + nb - 1) / nb;
-  per = (per + chunk - 1) / chunk * chunk;
-  nb = (R + per - 1) / per;
-  mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
-      a, b, rng, V, R, per, bins, hist);
+// The range stage: clears the first `clear` bytes of ws (the keys, or the keys and the table behind them), then rng (N, 4) from
+// each image's own minimum and maximum or from the caller's range.
+static hipError_t mi_range_launch(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a,
+                                  float hi_a, int has_range_b, float lo_b, float hi_b, void* ws, size_t clear, float* rng,
+                                  hipStream_t s) {
+  hipError_t e = hipMemsetAsync(ws, 0, clear, s);
+  if (e != hipSuccess) return e;
+  unsigned* keys = (unsigned*)ws;
+  if (!has_range_a || !has_range_b) {
+    long long nb = (V + TPB * 16 - 1) / (TPB * 16);
+    if (nb > 256) nb = 256;
+    mi_range_kernel<<<dim3((unsigned)nb, (unsigned)N, 2), TPB, 0, s>>>(a, b, V, has_range_a, has_range_b, keys);
+  }
+  mi_scale_kernel<<<ceil_div(2 * N, 64), 64, 0, s>>>(keys, N, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, rng);
+  return hipSuccess;
+}
+
+static void mi_hist_launch(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws,
+                           hipStream_t s) {
+  const HistSteps p = hist_steps(V, kWaves);
+  mi_hist_kernel<<<dim3((unsigned)p.nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
+      a, b, rng, V, p.R, p.per, bins, ws_table(ws, N));
 }
 
 /* a, b: (N, V) float32 contiguous.  has_range_x != 0: image x uses the range (lo_x, hi_x) instead of its own minimum and maximum.
@@ -279,17 +291,9 @@ KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int 
                         int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, kmh_mi_ws_bytes(N, bins), s);
+  hipError_t e = mi_range_launch(a, b, N, V, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, ws, ws_bytes(N, bins), rng, s);
   if (e != hipSuccess) return (int)e;
-  unsigned* keys = (unsigned*)ws;
-  unsigned long long* hist = (unsigned long long*)((char*)ws + (size_t)N * 16);
-  if (!has_range_a || !has_range_b) {
-    long long nb = (V + TPB * 16 - 1) / (TPB * 16);
-    if (nb > 256) nb = 256;
-    mi_range_kernel<<<dim3((unsigned)nb, (unsigned)N, 2), TPB, 0, s>>>(a, b, V, has_range_a, has_range_b, keys);
-  }
-  mi_scale_kernel<<<ceil_div(2 * N, 64), 64, 0, s>>>(keys, N, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, rng);
-  mi_hist_launch(a, b, rng, N, V, bins, hist, s);
+  mi_hist_launch(a, b, rng, N, V, bins, ws, s);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -299,9 +303,9 @@ KMH_API int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng,
                                void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, kmh_mi_ws_bytes(N, bins), s);
+  hipError_t e = hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
   if (e != hipSuccess) return (int)e;
-  mi_hist_launch(a, b, rng, N, V, bins, (unsigned long long*)((char*)ws + (size_t)N * 16), s);
+  mi_hist_launch(a, b, rng, N, V, bins, ws, s);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -311,16 +315,9 @@ KMH_API int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng,
 KMH_API int kmh_mi_range(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
                          int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, (size_t)N * 16, s);
+  hipError_t e = mi_range_launch(a, b, N, V, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, ws, (size_t)N * kKeyBytes, rng,
+                                 (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
-  unsigned* keys = (unsigned*)ws;
-  if (!has_range_a || !has_range_b) {
-    long long nb = (V + TPB * 16 - 1) / (TPB * 16);
-    if (nb > 256) nb = 256;
-    mi_range_kernel<<<dim3((unsigned)nb, (unsigned)N, 2), TPB, 0, s>>>(a, b, V, has_range_a, has_range_b, keys);
-  }
-  mi_scale_kernel<<<ceil_div(2 * N, 64), 64, 0, s>>>(keys, N, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, rng);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -328,8 +325,8 @@ KMH_API int kmh_mi_range(const float* a, const float* b, int N, long long V, int
  * where p > 0, else 0: what kmh_mi_bwd reads. */
 KMH_API int kmh_mi_final(const void* ws, const float* rng, int N, long long V, int bins, float* mi, float* G, void* stream) {
   if (!mi_args_ok(ws, rng, N, V, bins) || !mi || !G) return -22;
-  const unsigned long long* hist = (const unsigned long long*)((const char*)ws + (size_t)N * 16);
-  mi_final_kernel<<<N, TPB, (size_t)(bins * bins + 2 * bins) * sizeof(double), (hipStream_t)stream>>>(hist, rng, V, bins, mi, G);
+  mi_final_kernel<<<N, TPB, (size_t)(bins * bins + 2 * bins) * sizeof(double), (hipStream_t)stream>>>(ws_table(ws, N), rng, V, bins,
+                                                                                                      mi, G);
   return KMH_LAUNCH_CHECK();
 }
 

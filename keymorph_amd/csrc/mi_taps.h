@@ -1,7 +1,15 @@
 // What both joint-histogram units need (mi.hip: two volumes in memory; warp_mi.hip: the first one sampled from a moving volume
-// through a matrix on the fly): the Parzen window and the constants of the fixed-point table.  mi.hip states the definition; both
-// units must produce the same integer table from the same pair of values, so the window exists once.  (The wave's step into its
-// LDS table stays in each kernel's own text: mi_hist_kernel's machine code is as it was.)
+// through a matrix on the fly): the Parzen window (taps) and the constants of the fixed-point table, the wave's step into its LDS
+// table (hist_add), and the host side of the format: the workspace's layout (ws_bytes, ws_table) and the partition of a sample's
+// voxels into steps and workgroups (hist_steps).  mi.hip states the definition; both units must produce the same integer table from
+// the same pair of values, so these exist once.
+// One exception, decided by measurement: mi_hist_kernel keeps hist_add's text inline.  As a call (force-inlined all the same) the
+// compiler reschedules that kernel (12530 -> 12299 instructions) and it runs slower.  MI355X, medians of 30 calls in ms, separate
+// processes in the order inline, call, inline, call (profiles/metric_core_kernel_identity.md):
+//   128^3  min/max pass 0.1611 0.1635 0.1622 0.1633   ranges given 0.1522 0.1535 0.1520 0.1526   masked 0.1476 0.1475 0.1478 0.1482
+//   256^3  min/max pass 0.6309 0.6313 0.6304 0.6322   ranges given 0.5828 0.5842 0.5822 0.5828   masked 0.4340 0.4357 0.4340 0.4313
+// The call's mean exceeds the inline mean by more than the two inline runs differ in four of the six.  warp_mi_hist_kernel's
+// machine code is the same with hist_add here or in its own unit.
 #pragma once
 #include "common.h"
 
@@ -44,5 +52,57 @@ __device__ __forceinline__ Taps taps(float x, float lo, float s, int B) {
     r.d[3] = 0.5f * t2;
   }
   return r;
+}
+
+// One step of a wave (mi_hist_kernel repeats this text, see above): each valid lane's pair (xa, xb) -> 16 quantised products added to the wave's own B x B table `mine`.  Every
+// lane of the wave calls it together, and at least one of them is valid.
+__device__ __forceinline__ void hist_add(bool valid, float xa, float xb, float lo_a, float s_a, float lo_b, float s_b, int B,
+                                         int lane, unsigned* mine) {
+  unsigned q[16];
+  int key = -1;
+  if (valid) {
+    const Taps ta = taps<false>(xa, lo_a, s_a, B), tb = taps<false>(xb, lo_b, s_b, B);
+    key = ta.k0 * B + tb.k0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[i * 4 + k] = (unsigned)__float2int_rn(ta.w[i] * tb.w[k] * (float)(1 << kFrac));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) q[i] = 0u;
+  }
+  const int first = __shfl(key, __ffsll((long long)__ballot(valid)) - 1, kWave);
+  if (__all(!valid || key == first)) {
+    // one window for the whole wave: 64 lanes * rint(2^23 * 4/9) < 2^28 per sum
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const unsigned sum = wave_usum(q[i]);
+      if (lane == 0 && sum) atomicAdd(mine + first + (i >> 2) * B + (i & 3), sum);
+    }
+  } else if (valid) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (q[i]) atomicAdd(mine + key + (i >> 2) * B + (i & 3), q[i]);
+  }
+}
+
+// The workspace of the histogram entry points: per sample four range keys (kKeyBytes), then the (N, B, B) table of 64-bit sums.
+constexpr size_t kKeyBytes = 16;
+inline size_t ws_bytes(int N, int bins) { return (size_t)N * kKeyBytes + (size_t)N * bins * bins * sizeof(unsigned long long); }
+inline unsigned long long* ws_table(const void* ws, int N) { return (unsigned long long*)((char*)ws + (size_t)N * kKeyBytes); }
+
+// A sample's V voxels are R steps of 64 consecutive voxels; workgroup x of nb owns steps [x * per, + per), `per` a whole number of
+// flush intervals (kSteps steps for each of the workgroup's `waves` waves), about two intervals per workgroup, at most kMaxBlocks.
+struct HistSteps { long long R, nb, per; };
+inline HistSteps hist_steps(long long V, int waves) {
+  const int chunk = kSteps * waves;                                  // steps per workgroup between two flushes
+  HistSteps p;
+  p.R = (V + kWave - 1) / kWave;
+  p.nb = (p.R + 2 * chunk - 1) / (2 * chunk);
+  if (p.nb > kMaxBlocks) p.nb = kMaxBlocks;
+  p.per = (p.R + p.nb - 1) / p.nb;
+  p.per = (p.per + chunk - 1) / chunk * chunk;
+  p.nb = (p.R + p.per - 1) / p.per;
+  return p;
 }
 }  // namespace

@@ -4,8 +4,8 @@
 // By definition (per sample):  warp_mi(moving, fixed, mat) = MI(align_img(affine_grid(mat, dims), moving), fixed) with both
 // ranges given -- the chain kmh_affine_grid_fwd -> kmh_grid_sample3d_fwd -> kmh_mi_hist -> kmh_mi_final.  Every definition is
 // that chain's own: the coordinate is grid_coords.h's (lin, affine_coord_chain: what affine_grid_fwd_kernel writes), the tap, the
-// border clamp and the blend are sampler_taps.h's, the window and the table's constants are mi_taps.h's, and the quantised
-// product and the wave's step into its table (hist_add) repeat mi_hist_kernel's text.  The joint table is an integer sum of
+// border clamp and the blend are sampler_taps.h's, and the window, the table's constants, the quantised product and the wave's
+// step into its table (hist_add) are mi_taps.h's, whose text mi_hist_kernel repeats.  The joint table is an integer sum of
 // the same products, so it is the chain's table bit for bit, and kmh_mi_final turns it into MI and G = ln(p / (pa pb)) unchanged.
 //
 // warp_mi_hist_kernel   mi_hist_kernel's partition (steps of 64 consecutive voxels, one per lane; kSteps steps per wave between
@@ -25,8 +25,6 @@
 #include "grid_coords.h"
 #include "mi_taps.h"
 #include "sampler_taps.h"
-
-extern "C" size_t kmh_mi_ws_bytes(int N, int bins);
 
 namespace {
 constexpr int kWaves = TPB / kWave;
@@ -48,38 +46,6 @@ __device__ __forceinline__ Voxel voxel_tap(unsigned v, const float (&M)[12], int
   affine_coord_chain(M, r.pz, r.py, r.px, r.gx, r.gy, r.gz);
   r.t = make_tap(r.gx, r.gy, r.gz, D, H, W);
   return r;
-}
-
-// One step of a wave, the text of mi_hist_kernel's inner loop: each valid lane's pair (xa, xb) -> 16 quantised products added to
-// the wave's own B x B table `mine`.  Every lane of the wave calls it together, and at least one of them is valid.
-__device__ __forceinline__ void hist_add(bool valid, float xa, float xb, float lo_a, float s_a, float lo_b, float s_b, int B,
-                                         int lane, unsigned* mine) {
-  unsigned q[16];
-  int key = -1;
-  if (valid) {
-    const Taps ta = taps<false>(xa, lo_a, s_a, B), tb = taps<false>(xb, lo_b, s_b, B);
-    key = ta.k0 * B + tb.k0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q[i * 4 + k] = (unsigned)__float2int_rn(ta.w[i] * tb.w[k] * (float)(1 << kFrac));
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) q[i] = 0u;
-  }
-  const int first = __shfl(key, __ffsll((long long)__ballot(valid)) - 1, kWave);
-  if (__all(!valid || key == first)) {
-    // one window for the whole wave: 64 lanes * rint(2^23 * 4/9) < 2^28 per sum
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const unsigned sum = wave_usum(q[i]);
-      if (lane == 0 && sum) atomicAdd(mine + first + (i >> 2) * B + (i & 3), sum);
-    }
-  } else if (valid) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (q[i]) atomicAdd(mine + key + (i >> 2) * B + (i & 3), q[i]);
-  }
 }
 
 // grid (blocks, N); R, per as in mi_hist_kernel.  LDS: kWaves tables of B * B.
@@ -227,7 +193,7 @@ int bwd_blocks(long long V) {
   long long nb = (V + TPB * 16 - 1) / (TPB * 16);
   return (int)(nb > kBwdBlocks ? kBwdBlocks : nb);
 }
-size_t table_bytes(int N, int bins) { return (kmh_mi_ws_bytes(N, bins) + 255) & ~(size_t)255; }
+size_t table_bytes(int N, int bins) { return (ws_bytes(N, bins) + 255) & ~(size_t)255; }
 }  // namespace
 
 /* Workspace of kmh_warp_mi_hist / kmh_mi_final / kmh_warp_mi_bwd: the joint table in kmh_mi_hist's layout, then the backward
@@ -244,19 +210,11 @@ KMH_API int kmh_warp_mi_hist(const float* moving, const float* fixed, const floa
                              int W, int bins, void* ws, void* stream) {
   if (!warp_mi_args_ok(moving, fixed, mat, rng, N, D, H, W, bins) || !ws) return -22;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, kmh_mi_ws_bytes(N, bins), s);
+  hipError_t e = hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
   if (e != hipSuccess) return (int)e;
-  unsigned long long* hist = (unsigned long long*)((char*)ws + (size_t)N * 16);
-  constexpr int chunk = kSteps * kWaves;                             // steps per workgroup between two flushes
-  const long long V = (long long)D * H * W;
-  const long long R = (V + kWave - 1) / kWave;
-  long long nb = (R + 2 * chunk - 1) / (2 * chunk);
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  long long per = (R + nb - 1) / nb;
-  per = (per + chunk - 1) / chunk * chunk;
-  nb = (R + per - 1) / per;
-  warp_mi_hist_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
-      moving, fixed, mat, rng, D, H, W, (int)R, (int)per, bins, hist);
+  const HistSteps p = hist_steps((long long)D * H * W, kWaves);
+  warp_mi_hist_kernel<<<dim3((unsigned)p.nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
+      moving, fixed, mat, rng, D, H, W, (int)p.R, (int)p.per, bins, ws_table(ws, N));
   return KMH_LAUNCH_CHECK();
 }
 

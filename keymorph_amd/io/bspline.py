@@ -9,12 +9,8 @@ without refitting; per level it is stepped in that level's voxels (q_l = ctrl (W
 the bending weight are in voxels as register_intensity's are.  `mat` (N, 3, 4) is what ops.affine_grid takes."""
 import torch
 
-from .intensity import mat_to_voxel, register_intensity, voxel_to_mat
-
-
-def _per_channel(q, factors):
-    """q (N, 3, ...) times one Python scalar per channel (x, y, z): no tensor is made from a host list."""
-    return torch.stack([q[:, k] * float(factors[k]) for k in range(3)], dim=1)
+from ._pyramid import as_data, levels, scale_axes
+from .intensity import _conjugate, mat_to_voxel, register_intensity, voxel_to_mat
 
 
 def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
@@ -46,7 +42,7 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
 
     Nothing inside the loop waits for the GPU."""
     from .. import ops
-    from ..utils import align_img, resize_trilinear
+    from ..utils import align_img
     if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
         raise ValueError(f"register_bspline: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
                          f"{tuple(moving.shape)}")
@@ -57,34 +53,24 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
         raise ValueError(f"register_bspline: metric must be 'mi' or 'lncc', got {metric!r}")
     lattice = ops.bspline_lattice_shape(dims, control_spacing)
     with torch.inference_mode(False), torch.enable_grad():
-        fixed = fixed.clone() if fixed.is_inference() else fixed.detach()
-        moving = moving.clone() if moving.is_inference() else moving.detach()
+        fixed, moving = as_data(fixed), as_data(moving)
         if mat is None:
             mat = register_intensity(fixed, moving, "affine", bins=bins, shrink=shrink)
-        mat = mat.clone() if mat.is_inference() else mat.detach()
+        mat = as_data(mat)
         q = torch.zeros((N, 3, *lattice), dtype=torch.float32, device=fixed.device)      # voxels of the full size, (x, y, z)
         with torch.no_grad():
             L, t = mat_to_voxel(mat, dims)
-        for sh in shrink:
-            ldims = tuple(n // int(sh) for n in dims)
-            if min(ldims) < 16:
-                continue
-            ratio = [n / l for n, l in zip(dims, ldims)]              # (z, y, x)
+        for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):            # ratio in (z, y, x), q's channels in (x, y, z)
             with torch.no_grad():
-                f_l, m_l = (fixed, moving) if ldims == dims else (resize_trilinear(fixed, size=ldims),
-                                                                  resize_trilinear(moving, size=ldims))
                 rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
-                L_l = torch.stack([torch.stack([L[:, k, j] * (ratio[j] / ratio[k]) for j in range(3)], dim=1) for k in range(3)],
-                                  dim=1)
-                t_l = torch.stack([t[:, k] / ratio[k] for k in range(3)], dim=1)
-                mat_l = voxel_to_mat(L_l, t_l, ldims)
-                q_l = _per_channel(q, [1.0 / ratio[2 - k] for k in range(3)])
+                mat_l = voxel_to_mat(_conjugate(L, ratio), scale_axes(t, ratio, divide=True), ldims)
+                q_l = scale_axes(q, [1.0 / r for r in reversed(ratio)])
             q_l.requires_grad_(True)
-            to_norm = [2.0 / ldims[2 - k] for k in range(3)]
+            to_norm = [2.0 / n for n in reversed(ldims)]
             opt = torch.optim.Adam([q_l], lr=lr)
             for _ in range(iters):
                 opt.zero_grad(set_to_none=True)
-                warped = align_img(ops.bspline_grid(_per_channel(q_l, to_norm), ldims, mat_l), m_l)
+                warped = align_img(ops.bspline_grid(scale_axes(q_l, to_norm), ldims, mat_l), m_l)
                 if metric == "mi":
                     sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
                 else:
@@ -92,5 +78,5 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
                 loss = (bending * ops.bspline_bending(q_l) - sim).sum()
                 loss.backward()
                 opt.step()
-            q = _per_channel(q_l.detach(), [ratio[2 - k] for k in range(3)])
-        return _per_channel(q, [2.0 / dims[2 - k] for k in range(3)])
+            q = scale_axes(q_l.detach(), list(reversed(ratio)))
+        return scale_axes(q, [2.0 / n for n in reversed(dims)])

@@ -4,6 +4,8 @@ translation is applied to the unmasked image (linear) and to the mask (nearest).
 SimpleITK; here it is ops.mutual_information under Adam, over a trilinear pyramid."""
 import torch
 
+from ._pyramid import levels, scale_axes
+
 
 def translate(x, t, mode="bilinear"):
     """x (N, C, D, H, W) shifted by t (N, 3) voxels in (z, y, x) order: out[v] = x[v + t], border values outside; differentiable in
@@ -16,13 +18,12 @@ def translate(x, t, mode="bilinear"):
         raise ValueError(f"translate: expected x (N, C, D, H, W) and t (N, 3), got {tuple(x.shape)} and {tuple(t.shape)}")
     if mode not in ("bilinear", "nearest"):
         raise ValueError(f"translate: mode must be 'bilinear' or 'nearest', got {mode!r}")
-    # the matrix from Python scalars only: a tensor built from a host list would be a host-to-device copy, which waits for the
-    # stream, on every step of estimate_translation's loop
+    # the matrix from Python scalars only (scale_axes says why): this runs on every step of estimate_translation's loop
     t = t.float()
     lin = t.new_zeros((x.shape[0], 3, 3))
     for k, n in enumerate(x.shape[2:]):
         lin[:, k, k] = (n - 1) / n
-    off = torch.stack([t[:, k] * (2.0 / n) for k, n in enumerate(x.shape[2:])], dim=1)
+    off = scale_axes(t, [2.0 / n for n in x.shape[2:]])
     mat = torch.cat([lin, off.unsqueeze(-1)], dim=2)
     return align_img(ops.affine_grid(mat, x.shape[2:]), x, mode)
 
@@ -41,32 +42,21 @@ def estimate_translation(fixed, moving, bins=32, shrink=(4, 2, 1), iters=30, lr=
     of that level on -MI(translate(moving_l, t_l), fixed_l); t is carried from level to level in full-resolution voxels.  Every
     sample is optimised on its own (the loss is the sum over the batch); nothing inside the loop waits for the GPU."""
     from .. import ops
-    from ..utils import resize_trilinear
     if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
         raise ValueError(f"estimate_translation: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
                          f"{tuple(moving.shape)}")
     fixed, moving = fixed.detach(), moving.detach()
-    dims = tuple(fixed.shape[2:])
     with torch.no_grad():
         t = _centroid(moving) - _centroid(fixed)
-    for sh in shrink:
-        ldims = tuple(n // int(sh) for n in dims)
-        if min(ldims) < 16:
-            continue
-        if ldims == dims:
-            f_l, m_l = fixed, moving
-        else:
-            with torch.no_grad():
-                f_l, m_l = resize_trilinear(fixed, size=ldims), resize_trilinear(moving, size=ldims)
-        ratio = [n / l for n, l in zip(dims, ldims)]
-        t_l = torch.stack([t[:, k] / ratio[k] for k in range(3)], dim=1).requires_grad_(True)
+    for _, f_l, m_l, ratio in levels(fixed, moving, shrink):
+        t_l = scale_axes(t, ratio, divide=True).requires_grad_(True)
         opt = torch.optim.Adam([t_l], lr=lr)
         for _ in range(iters):
             opt.zero_grad(set_to_none=True)
             loss = -ops.mutual_information(translate(m_l, t_l), f_l, bins).sum()
             loss.backward()
             opt.step()
-        t = torch.stack([t_l.detach()[:, k] * ratio[k] for k in range(3)], dim=1)
+        t = scale_axes(t_l.detach(), ratio)
     return t
 
 

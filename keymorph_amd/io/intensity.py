@@ -8,6 +8,8 @@ the volume's centre, L (N, 3, 3), t (N, 3) voxels, rows and columns in (z, y, x)
 takes.  translate(x, t) of io.centering is the case L = I."""
 import torch
 
+from ._pyramid import as_data, levels, scale_axes
+
 
 def _dims3(dims):
     d = tuple(int(n) for n in dims)
@@ -99,7 +101,6 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
 
     Nothing inside the loop waits for the GPU."""
     from .. import ops
-    from ..utils import resize_trilinear
     from .centering import _centroid
     if transform not in _STAGES:
         raise ValueError(f"register_intensity: transform must be one of {sorted(_STAGES)}, got {transform!r}")
@@ -111,28 +112,21 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
         raise ValueError(f"register_intensity: spacing must be three positive numbers, got {spacing}")
     dims = tuple(fixed.shape[2:])
     with torch.inference_mode(False), torch.enable_grad():
-        fixed = fixed.clone() if fixed.is_inference() else fixed.detach()
-        moving = moving.clone() if moving.is_inference() else moving.detach()
-        levels = []
+        fixed, moving = as_data(fixed), as_data(moving)
+        pyramid = []
         with torch.no_grad():
             t = _centroid(moving) - _centroid(fixed)
-            for sh in shrink:
-                ldims = tuple(n // int(sh) for n in dims)
-                if min(ldims) < 16:
-                    continue
-                f_l, m_l = (fixed, moving) if ldims == dims else (resize_trilinear(fixed, size=ldims),
-                                                                  resize_trilinear(moving, size=ldims))
-                ratio = [n / l for n, l in zip(dims, ldims)]
+            for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):
                 sp = [s * r for s, r in zip(spacing, ratio)]
                 h = max(s * (n - 1) / 2 for s, n in zip(sp, ldims)) / min(sp)
-                levels.append((ldims, f_l, m_l, ops.mi_ranges(m_l, f_l, bins), ratio, sp, h))
+                pyramid.append((ldims, f_l, m_l, ops.mi_ranges(m_l, f_l, bins), ratio, sp, h))
         omega = torch.zeros_like(t)
         A = None
         for stage in _STAGES[transform]:
             if stage == "affine":
                 A = rotation_matrix(omega).detach()
-            for ldims, f_l, m_l, rng, ratio, sp, h in levels:
-                t_l = torch.stack([t[:, k] / ratio[k] for k in range(3)], dim=1).requires_grad_(True)
+            for ldims, f_l, m_l, rng, ratio, sp, h in pyramid:
+                t_l = scale_axes(t, ratio, divide=True).requires_grad_(True)
                 params = [t_l]
                 if stage == "translation":                     # L does not move in this stage: once per level, no graph
                     with torch.no_grad():
@@ -158,7 +152,7 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
                     loss = -ops.warp_mutual_information(m_l, f_l, level_mat(), bins, rng).sum()
                     loss.backward()
                     opt.step()
-                t = torch.stack([t_l.detach()[:, k] * ratio[k] for k in range(3)], dim=1)
+                t = scale_axes(t_l.detach(), ratio)
                 if stage == "rigid":
                     omega = q.detach() / h
                 elif stage == "affine":

@@ -394,28 +394,27 @@ class IntensityRegistration(nn.Module):
         result_dict = {}
         for align_type_str in transform_type:
             start_time = time.time()
-            if align_type_str == "bspline":
+            bspline = align_type_str == "bspline"
+            mat = register_intensity(img_f, img_m, "affine" if bspline else align_type_str, bins=self.bins, shrink=shrink,
+                                     iters=self.iters, lr=self.lr)
+            if bspline:
                 from .io.bspline import register_bspline
                 from .utils import align_img
-                mat = register_intensity(img_f, img_m, "affine", bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
                 ctrl = register_bspline(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending,
                                         bins=self.bins, shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr,
                                         metric=self.metric, window=self.window)
                 with torch.no_grad():
                     grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
                     warped = align_img(grid, img_m)
-                    mi = ops.mutual_information(warped, img_f, self.bins)
-                    lncc = ops.local_ncc(warped, img_f, self.window) if self.metric == "lncc" else None
-                result_dict[align_type_str] = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": mi}
-                if lncc is not None:
-                    result_dict[align_type_str]["lncc"] = lncc
-                result_dict[align_type_str]["time"] = time.time() - start_time
-                continue
-            mat = register_intensity(img_f, img_m, align_type_str, bins=self.bins, shrink=shrink, iters=self.iters, lr=self.lr)
-            with torch.no_grad():
-                grid = ops.affine_grid(mat, img_f.shape[2:])
-                mi = ops.warp_mutual_information(img_m, img_f, mat, self.bins)
-            result_dict[align_type_str] = {"grid": grid, "matrix": mat, "mi": mi, "time": time.time() - start_time}
+                    res = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": ops.mutual_information(warped, img_f, self.bins)}
+                    if self.metric == "lncc":
+                        res["lncc"] = ops.local_ncc(warped, img_f, self.window)
+            else:
+                with torch.no_grad():
+                    res = {"grid": ops.affine_grid(mat, img_f.shape[2:]), "matrix": mat,
+                           "mi": ops.warp_mutual_information(img_m, img_f, mat, self.bins)}
+            res["time"] = time.time() - start_time
+            result_dict[align_type_str] = res
         return result_dict
 
 

@@ -29,16 +29,39 @@ def _p(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _prep(t: Tensor, name: str = "tensor") -> Tensor:
-    if not t.is_cuda:
-        raise _lib.KeymorphHipError(
-            f"{name} is on {t.device}: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
+def _need_gpu(who: Optional[str], name: str, t) -> None:
+    """t is a tensor on the current GPU, or KeymorphHipError.  who: the public function named in the message (None: none)."""
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        what = f"{who}: {name}" if who else name
+        raise _lib.KeymorphHipError(f"{what} is not on the GPU: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
     if t.device.index != torch.cuda.current_device():
         # the C ABI launches on the CURRENT device's stream and never calls hipSetDevice: a tensor that lives on
         # another GPU would be touched by kernels queued on the wrong device
         raise _lib.KeymorphHipError(
-            f"{name} is on {t.device} but the current device is cuda:{torch.cuda.current_device()}: "
+            f"{who + ': ' if who else ''}{name} is on {t.device} but the current device is cuda:{torch.cuda.current_device()}: "
             "call torch.cuda.set_device(...) (one process per GPU) before using keymorph_amd ops")
+
+
+def _need_gpu_f32(who: str, name: str, t) -> None:
+    """_need_gpu, then float32 or ValueError: for the ops that state their dtype instead of converting (_prep converts)."""
+    _need_gpu(who, name, t)
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+
+
+def _need_volume_pair(who: str, a: Tensor, b: Tensor, max_voxels: Optional[int] = None, min_w: int = 1) -> None:
+    """a, b: two non-empty (N, 1, D, H, W) tensors of one shape, W >= min_w, fewer than max_voxels voxels per sample, or
+    ValueError."""
+    if a.shape != b.shape:
+        raise ValueError(f"{who}: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0:
+        raise ValueError(f"{who}: expected two non-empty (N, 1, D, H, W) volumes, got {tuple(a.shape)}")
+    if a.shape[4] < min_w or (max_voxels is not None and a.numel() // a.shape[0] >= max_voxels):
+        raise ValueError(f"{who}: needs W >= {min_w} and fewer than {max_voxels} voxels per sample, got {tuple(a.shape)}")
+
+
+def _prep(t: Tensor, name: str = "tensor") -> Tensor:
+    _need_gpu(None, name, t)
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
@@ -404,12 +427,7 @@ def bspline_lattice_shape(shape: Sequence[int], spacing: int) -> Tuple[int, int,
 
 
 def _lattice_check(t, name, who):
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise _lib.KeymorphHipError(f"{who}: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
-    if t.device.index != torch.cuda.current_device():
-        raise _lib.KeymorphHipError(f"{who}: {name} is on {t.device} but the current device is cuda:{torch.cuda.current_device()}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+    _need_gpu_f32(who, name, t)
     if t.dim() != 5 or t.shape[0] < 1 or t.shape[1] != 3 or min(t.shape[2:]) < 4:
         raise ValueError(f"{who}: {name} must be (N, 3, Cz, Cy, Cx) with every C >= 4, got {tuple(t.shape)}")
 
@@ -452,8 +470,7 @@ def bspline_grid(ctrl: Tensor, shape: Sequence[int], mat: Optional[Tensor] = Non
     if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] >= 1 << 31:
         raise ValueError(f"bspline_grid: shape must be three positive sizes (D, H, W) with fewer than 2^31 voxels, got {tuple(shape)}")
     if mat is not None:
-        if not isinstance(mat, Tensor) or not mat.is_cuda or mat.device != ctrl.device:
-            raise _lib.KeymorphHipError("bspline_grid: mat is not on ctrl's GPU (no CPU fallback)")
+        _need_gpu("bspline_grid", "mat", mat)
         if mat.requires_grad and torch.is_grad_enabled():
             raise RuntimeError("bspline_grid: mat requires grad, and bspline_grid is differentiable in ctrl only: pass mat.detach()")
         if mat.dtype != torch.float32 or tuple(mat.shape) != (ctrl.shape[0], 3, 4):
@@ -751,16 +768,28 @@ def lc2(us: Tensor, mr: Tensor, patch: int, radii: Sequence[int], alpha: float =
 MI_MIN_BINS, MI_MAX_BINS = 8, 64
 
 
+def _need_bins(who: str, bins) -> int:
+    if int(bins) != bins or not MI_MIN_BINS <= bins <= MI_MAX_BINS:
+        raise ValueError(f"{who}: bins must be an integer in [{MI_MIN_BINS}, {MI_MAX_BINS}], got {bins}")
+    return int(bins)
+
+
+def _mi_final(ws, rng, N, V, bins):
+    """(mi (N,), G (N, bins, bins)) from the joint table a histogram pass (kmh_mi_hist*, kmh_warp_mi_hist) left in ws."""
+    mi = torch.empty((N,), dtype=torch.float32, device=ws.device)
+    G = torch.empty((N, bins, bins), dtype=torch.float32, device=ws.device)
+    check(_lib.load().kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+    return mi, G
+
+
 def _mi_forward(a, b, bins, range_a, range_b, ranges=None):
     """(mi (N,), rng (N, 4), G (N, bins, bins)) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise.
     ranges: a checked (N, 4) device tensor as mi_ranges returns it, used instead of range_a / range_b."""
     lib = _lib.load()
-    N, V = a.shape[0], a[0].numel()
+    N, V = a.shape[0], a.numel() // a.shape[0]
     dev = a.device
     ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=dev)
     rng = torch.empty((N, 4), dtype=torch.float32, device=dev) if ranges is None else ranges
-    mi = torch.empty((N,), dtype=torch.float32, device=dev)
-    G = torch.empty((N, bins, bins), dtype=torch.float32, device=dev)
     ra, rb = range_a or (0.0, 0.0), range_b or (0.0, 0.0)
     if _lib.profiler.enabled:  # 8 B read per voxel
         _lib.profiler.meta = {"bytes": 8.0 * N * V}
@@ -769,7 +798,7 @@ def _mi_forward(a, b, bins, range_a, range_b, ranges=None):
     else:
         check(lib.kmh_mi_hist(_p(a), _p(b), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None), rb[0],
                               rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_hist")
-    check(lib.kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+    mi, G = _mi_final(ws, rng, N, V, bins)
     return mi, rng, G
 
 
@@ -786,7 +815,7 @@ class _MI(torch.autograd.Function):
         lib = _lib.load()
         a, b, rng, G = ctx.saved_tensors
         gout = _prep(gout)
-        N, V = a.shape[0], a[0].numel()
+        N, V = a.shape[0], a.numel() // a.shape[0]
         da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         if _lib.profiler.enabled:  # 8 B read and 4 B written per voxel and gradient
@@ -797,20 +826,9 @@ class _MI(torch.autograd.Function):
 
 def _mi_check(a, b, bins, range_a, range_b):
     for name, t in (("a", a), ("b", b)):
-        if not isinstance(t, Tensor) or not t.is_cuda:
-            raise _lib.KeymorphHipError(f"mutual_information: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
-                                        "(no CPU fallback)")
-        if t.device.index != torch.cuda.current_device():
-            raise _lib.KeymorphHipError(f"mutual_information: {name} is on {t.device} but the current device is "
-                                        f"cuda:{torch.cuda.current_device()}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"mutual_information: {name} must be float32, got {t.dtype}")
-    if a.shape != b.shape:
-        raise ValueError(f"mutual_information: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
-    if a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0:
-        raise ValueError(f"mutual_information: expected two non-empty (N, 1, D, H, W) volumes, got {tuple(a.shape)}")
-    if int(bins) != bins or not MI_MIN_BINS <= bins <= MI_MAX_BINS:
-        raise ValueError(f"mutual_information: bins must be an integer in [{MI_MIN_BINS}, {MI_MAX_BINS}], got {bins}")
+        _need_gpu_f32("mutual_information", name, t)
+    _need_volume_pair("mutual_information", a, b)
+    bins = _need_bins("mutual_information", bins)
     out = []
     for name, r in (("range_a", range_a), ("range_b", range_b)):
         if r is not None:
@@ -818,7 +836,7 @@ def _mi_check(a, b, bins, range_a, range_b):
                 raise ValueError(f"mutual_information: {name} must be (lo, hi) with lo <= hi, got {r}")
             r = (float(r[0]), float(r[1]))
         out.append(r)
-    return a.contiguous(), b.contiguous(), int(bins), out[0], out[1]
+    return a.contiguous(), b.contiguous(), bins, out[0], out[1]
 
 
 def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges: Optional[Tensor] = None) -> Tensor:
@@ -833,11 +851,10 @@ def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range
         if range_a is not None or range_b is not None:
             raise ValueError("mutual_information: give either range_a / range_b or ranges, not both")
         a, b, bins, _, _ = _mi_check(a, b, bins, None, None)
-        if not isinstance(ranges, Tensor) or not ranges.is_cuda or ranges.device != a.device:
-            raise _lib.KeymorphHipError("mutual_information: ranges is not on the inputs' GPU (no CPU fallback)")
-        if ranges.dtype != torch.float32 or tuple(ranges.shape) != (a.shape[0], 4):
-            raise ValueError(f"mutual_information: ranges must be float32 ({a.shape[0]}, 4) as mi_ranges returns them, got "
-                             f"{ranges.dtype} {tuple(ranges.shape)}")
+        _need_gpu_f32("mutual_information", "ranges", ranges)
+        if tuple(ranges.shape) != (a.shape[0], 4):
+            raise ValueError(f"mutual_information: ranges must be ({a.shape[0]}, 4) as mi_ranges returns them, got "
+                             f"{tuple(ranges.shape)}")
         return _MI.apply(a, b, bins, None, None, ranges.detach().contiguous())
     return _MI.apply(*_mi_check(a, b, bins, range_a, range_b))
 
@@ -856,33 +873,20 @@ def _warp_mi_check(moving, fixed, mat, bins, ranges, who="warp_mutual_informatio
     tensors = [("moving", moving), ("fixed", fixed)] + ([("mat", mat)] if mat is not None else []) \
         + ([("ranges", ranges)] if ranges is not None else [])
     for name, t in tensors:
-        if not isinstance(t, Tensor) or not t.is_cuda:
-            raise _lib.KeymorphHipError(f"{who}: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
-                                        "(no CPU fallback)")
-        if t.device.index != torch.cuda.current_device():
-            raise _lib.KeymorphHipError(f"{who}: {name} is on {t.device} but the current device is "
-                                        f"cuda:{torch.cuda.current_device()}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
-    if moving.shape != fixed.shape:
-        raise ValueError(f"{who}: shapes differ: {tuple(moving.shape)} vs {tuple(fixed.shape)}")
-    if moving.dim() != 5 or moving.shape[1] != 1 or moving.numel() == 0:
-        raise ValueError(f"{who}: expected two non-empty (N, 1, D, H, W) volumes, got {tuple(moving.shape)}")
-    if moving.shape[4] < 2 or moving[0].numel() >= 1 << 30:
-        raise ValueError(f"{who}: needs W >= 2 and fewer than 2^30 voxels per sample, got {tuple(moving.shape)}")
-    if int(bins) != bins or not MI_MIN_BINS <= bins <= MI_MAX_BINS:
-        raise ValueError(f"{who}: bins must be an integer in [{MI_MIN_BINS}, {MI_MAX_BINS}], got {bins}")
+        _need_gpu_f32(who, name, t)
+    _need_volume_pair(who, moving, fixed, max_voxels=1 << 30, min_w=2)     # buffer loads: 32-bit byte offsets into a sample
+    bins = _need_bins(who, bins)
     N = moving.shape[0]
     if mat is not None and tuple(mat.shape) != (N, 3, 4):
         raise ValueError(f"{who}: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
     if ranges is not None and tuple(ranges.shape) != (N, 4):
         raise ValueError(f"{who}: ranges must be ({N}, 4) as mi_ranges returns them, got {tuple(ranges.shape)}")
-    return int(bins)
+    return bins
 
 
 def _mi_ranges(moving, fixed, bins):
     lib = _lib.load()
-    N, V = moving.shape[0], moving[0].numel()
+    N, V = moving.shape[0], moving.numel() // moving.shape[0]
     ws = torch.empty(16 * N, dtype=torch.uint8, device=moving.device)
     rng = torch.empty((N, 4), dtype=torch.float32, device=moving.device)
     check(lib.kmh_mi_range(_p(moving), _p(fixed), N, V, bins, 0, 0.0, 0.0, 0, 0.0, 0.0, _p(ws), _p(rng), _stream()),
@@ -903,15 +907,12 @@ class _WarpMI(torch.autograd.Function):
     def forward(ctx, moving, fixed, mat, rng, bins):
         lib = _lib.load()
         N, _, D, H, W = moving.shape
-        dev = moving.device
-        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=dev)
-        mi = torch.empty((N,), dtype=torch.float32, device=dev)
-        G = torch.empty((N, bins, bins), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=moving.device)
         if _lib.profiler.enabled:  # the fixed volume once, the moving volume about once (8 corners, coherent)
             _lib.profiler.meta = {"bytes": 8.0 * N * D * H * W}
         check(lib.kmh_warp_mi_hist(_p(moving), _p(fixed), _p(mat), _p(rng), N, D, H, W, bins, _p(ws), _stream()),
               "kmh_warp_mi_hist")
-        check(lib.kmh_mi_final(_p(ws), _p(rng), N, D * H * W, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+        mi, G = _mi_final(ws, rng, N, D * H * W, bins)
         ctx.save_for_backward(moving, fixed, mat, rng, G)
         ctx.bins = bins
         ctx.mark_non_differentiable(G)
@@ -1001,19 +1002,8 @@ def local_ncc(a: Tensor, b: Tensor, window: int = 9, eps: float = 1e-5) -> Tenso
     meant for volumes scaled to about [0, 1].  Two calls give bit-identical values and gradients; a batch equals its samples run
     one by one."""
     for name, t in (("a", a), ("b", b)):
-        if not isinstance(t, Tensor) or not t.is_cuda:
-            raise _lib.KeymorphHipError(f"local_ncc: {name} is not on the GPU: keymorph_amd ops run only on an AMD GPU "
-                                        "(no CPU fallback)")
-        if t.device.index != torch.cuda.current_device():
-            raise _lib.KeymorphHipError(f"local_ncc: {name} is on {t.device} but the current device is "
-                                        f"cuda:{torch.cuda.current_device()}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"local_ncc: {name} must be float32, got {t.dtype}")
-    if a.shape != b.shape:
-        raise ValueError(f"local_ncc: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
-    if a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0 or a[0].numel() >= 1 << 31:
-        raise ValueError(f"local_ncc: expected two non-empty (N, 1, D, H, W) volumes of fewer than 2^31 voxels each, got "
-                         f"{tuple(a.shape)}")
+        _need_gpu_f32("local_ncc", name, t)
+    _need_volume_pair("local_ncc", a, b, max_voxels=1 << 31)
     if int(window) != window or not LNCC_MIN_WINDOW <= window <= LNCC_MAX_WINDOW or window % 2 == 0:
         raise ValueError(f"local_ncc: window must be an odd integer in [{LNCC_MIN_WINDOW}, {LNCC_MAX_WINDOW}], got {window}")
     if not float(eps) >= 0.0:
@@ -1136,10 +1126,7 @@ def resize_trilinear3d(x: Tensor, size=None, scale_factor=None, channels_last: b
 # connected components / clean_mask (keymorph/model.py:622-659)
 # --------------------------------------------------------------------------
 def _mask_bytes(mask: Tensor, name: str) -> Tensor:
-    if not mask.is_cuda:
-        raise _lib.KeymorphHipError(f"{name} is on {mask.device}: keymorph_amd ops run only on an AMD GPU (no CPU fallback)")
-    if mask.device.index != torch.cuda.current_device():
-        raise _lib.KeymorphHipError(f"{name} is on {mask.device} but the current device is cuda:{torch.cuda.current_device()}")
+    _need_gpu(None, name, mask)
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
     elif mask.dtype != torch.uint8:

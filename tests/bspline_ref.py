@@ -132,9 +132,18 @@ def displacement_error(ctrl, truth, dims):
 
 
 # ---- the driver's schedule ------------------------------------------------------------------------------------------------------
+def mi_similarity(warped, f_l, level):
+    """The mutual information of register_bspline's default metric; the ranges are the level's own pair's, found once."""
+    if "ranges" not in level:
+        level["ranges"] = W.own_ranges(level["moving"], f_l)
+    return torch.stack([mi_ref.mi_sample(warped[k], f_l[k], level["bins"], *level["ranges"][k]) for k in range(len(warped))])
+
+
 def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-             dtype=F64):
-    """keymorph_amd.io.register_bspline with a given matrix, on the CPU in `dtype`: the same levels, parameters, loss and Adam."""
+             dtype=F64, similarity=mi_similarity):
+    """keymorph_amd.io.register_bspline with a given matrix, on the CPU in `dtype`: the same levels, parameters, loss and Adam.
+    similarity(warped, f_l, level) -> (N,), higher is better; level = {"moving": m_l, "bins": bins}, a dict of the level's own
+    that the callable may keep things in."""
     fixed, moving, mat = fixed.detach().to(dtype), moving.detach().to(dtype), mat.detach().to(F64)
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     n = torch.tensor([float(d) for d in dims], dtype=F64)
@@ -150,7 +159,7 @@ def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, bins=32
         else:
             f_l = F.interpolate(fixed, size=ldims, mode="trilinear", align_corners=False)
             m_l = F.interpolate(moving, size=ldims, mode="trilinear", align_corners=False)
-        ranges = W.own_ranges(m_l, f_l)
+        level = {"moving": m_l, "bins": bins}
         ratio = torch.tensor([d / l for d, l in zip(dims, ldims)], dtype=F64)
         mat_l = W.voxel_to_mat(L * ratio[None, None, :] / ratio[None, :, None], t / ratio[None, :], ldims).to(dtype)
         rx = ratio.flip(0).to(dtype)[None, :, None, None, None]
@@ -161,8 +170,7 @@ def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, bins=32
             opt.zero_grad(set_to_none=True)
             warped = F.grid_sample(m_l, bspline_grid(q_l * to_norm, ldims, mat_l), mode="bilinear", padding_mode="border",
                                    align_corners=False)
-            mi = torch.stack([mi_ref.mi_sample(warped[k], f_l[k], bins, ranges[k][0], ranges[k][1]) for k in range(N)])
-            (bending_weight * bending(q_l) - mi).sum().backward()
+            (bending_weight * bending(q_l) - similarity(warped, f_l, level)).sum().backward()
             opt.step()
         q = q_l.detach() * rx
     return q * torch.tensor([2.0 / dims[2], 2.0 / dims[1], 2.0 / dims[0]], dtype=dtype)[None, :, None, None, None]

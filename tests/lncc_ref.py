@@ -135,40 +135,12 @@ def biased_pair():
 def register(fixed, moving, mat, metric="lncc", window=9, control_spacing=8, bending_weight=0.05, bins=32, shrink=(4, 2, 1),
              iters=60, lr=0.1, dtype=F64):
     """keymorph_amd.io.register_bspline(metric=...) with a given matrix, on the CPU in `dtype`.  "mi" is bspline_ref.register
-    itself; "lncc" is the same levels, parameters and Adam with the similarity exchanged."""
+    itself; "lncc" is the same schedule with the similarity exchanged."""
     if metric == "mi":
         return B.register(fixed, moving, mat, control_spacing, bending_weight, bins, shrink, iters, lr, dtype)
     assert metric == "lncc"
-    fixed, moving, mat = fixed.detach().to(dtype), moving.detach().to(dtype), mat.detach().to(F64)
-    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
-    n = torch.tensor([float(d) for d in dims], dtype=F64)
-    L = mat[:, :, :3] * n[None, :, None] / (n - 1)[None, None, :]
-    t = mat[:, :, 3] * n[None, :] / 2
-    q = torch.zeros((N, 3, *B.lattice_shape(dims, control_spacing)), dtype=dtype)
-    for sh in shrink:
-        ldims = tuple(d // int(sh) for d in dims)
-        if min(ldims) < 16:
-            continue
-        if ldims == dims:
-            f_l, m_l = fixed, moving
-        else:
-            f_l = F.interpolate(fixed, size=ldims, mode="trilinear", align_corners=False)
-            m_l = F.interpolate(moving, size=ldims, mode="trilinear", align_corners=False)
-        ratio = torch.tensor([d / l for d, l in zip(dims, ldims)], dtype=F64)
-        mat_l = W.voxel_to_mat(L * ratio[None, None, :] / ratio[None, :, None], t / ratio[None, :], ldims).to(dtype)
-        rx = ratio.flip(0).to(dtype)[None, :, None, None, None]
-        to_norm = torch.tensor([2.0 / ldims[2], 2.0 / ldims[1], 2.0 / ldims[0]], dtype=dtype)[None, :, None, None, None]
-        q_l = (q / rx).requires_grad_(True)
-        opt = torch.optim.Adam([q_l], lr=lr)
-        for _ in range(iters):
-            opt.zero_grad(set_to_none=True)
-            warped = F.grid_sample(m_l, B.bspline_grid(q_l * to_norm, ldims, mat_l), mode="bilinear", padding_mode="border",
-                                   align_corners=False)
-            sim = lncc_map(warped, f_l, window).mean(dim=(1, 2, 3, 4))
-            (bending_weight * B.bending(q_l) - sim).sum().backward()
-            opt.step()
-        q = q_l.detach() * rx
-    return q * torch.tensor([2.0 / dims[2], 2.0 / dims[1], 2.0 / dims[0]], dtype=dtype)[None, :, None, None, None]
+    return B.register(fixed, moving, mat, control_spacing, bending_weight, bins, shrink, iters, lr, dtype,
+                      similarity=lambda warped, f_l, level: lncc_map(warped, f_l, window).mean(dim=(1, 2, 3, 4)))
 
 
 # what biased_run returns in fp64, as tests/test_lncc_cpu.py measures and asserts it (voxels): for a GPU test to print beside its own
