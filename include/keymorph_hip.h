@@ -597,6 +597,30 @@ size_t kmh_bspline_bending_ws_bytes(int N);
 int kmh_bspline_bending_fwd(const float* q, float* out, int N, int Cz, int Cy, int Cx, void* ws, void* stream);
 int kmh_bspline_bending_bwd(const float* q, const float* gout, float* dq, int N, int Cz, int Cy, int Cx, void* stream);
 
+/* ---- diffeomorphic grids: a stationary velocity field exponentiated by scaling and squaring (csrc/svf.hip states the definition) ---- */
+/* kmh_bspline_disp_fwd: out (N,D,H,W,3) = the spline of kmh_bspline_grid_fwd WITHOUT its base (same limits, same -22);
+ * kmh_bspline_grid_bwd is its transpose too.
+ * Displacements u, first, add, out, g, du and grids are (N,D,H,W,3) float32 contiguous, xyz, normalised, on the voxel-centre lattice;
+ * N in [1, 65535] and D*H*W*3 < 2^30 (one buffer descriptor per sample), else -22 before anything is launched.
+ * kmh_svf_compose: out[w] = add[w] + U(first[w]), U = the border-clamped trilinear interpolant of u (the sampler's coordinate,
+ *   clamp and NaN rule).  first == NULL: first = Ids + u, add = u -- one squaring step, bit-identical to sampling u at
+ *   identity + u and adding u.  out must not be u.
+ * kmh_svf_finish_fwd: out = Ids + u (mat NULL), else kmh_affine_grid_fwd's grid + L (s * u), L = mat[:, :3], s = S / (S - 1) per
+ *   axis (every axis >= 2).  out may be u.  kmh_svf_finish_bwd: du = the transpose applied to dgrid; amax_out (N unsigned, zeroed by
+ *   the caller, or NULL) receives the bits of the largest finite |du| of each sample.
+ * kmh_svf_square_bwd: the transpose of a squaring step, du from g (du may be g): the per-voxel part directly, the scattered part
+ *   in 64-bit fixed point with integer atomics, scaled per sample by amax_in (N unsigned: what kmh_svf_finish_bwd or the previous
+ *   call published) -- order independent, so runs repeat bit for bit and a batch equals its samples.  amax_out as above.
+ *   ws: kmh_svf_square_bwd_ws_bytes bytes (32 per voxel), cleared by the call. */
+int kmh_bspline_disp_fwd(const float* ctrl, float* out, int N, int D, int H, int W, int Cz, int Cy, int Cx, void* stream);
+int kmh_svf_compose(const float* u, const float* first, const float* add, float* out, int N, int D, int H, int W, void* stream);
+int kmh_svf_finish_fwd(const float* u, const float* mat, float* out, int N, int D, int H, int W, void* stream);
+int kmh_svf_finish_bwd(const float* dgrid, const float* mat, float* du, unsigned* amax_out, int N, int D, int H, int W,
+                       void* stream);
+size_t kmh_svf_square_bwd_ws_bytes(int N, int D, int H, int W);
+int kmh_svf_square_bwd(const float* u, const float* g, float* du, const unsigned* amax_in, unsigned* amax_out, int N, int D, int H,
+                       int W, void* ws, void* stream);
+
 /* ---- local normalised cross-correlation (csrc/lncc.hip states the definition) ---- */
 /* a, b: (N, D, H, W) float32 contiguous, fewer than 2^31 voxels per sample; window odd in [3, 15], truncated at the border.
  * out[n] = mean over the voxels of cross^2 / (va vb + eps) of the window sums.  kmh_lncc_bwd: da = gout[n] d out[n] / da, db

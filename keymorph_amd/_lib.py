@@ -174,6 +174,12 @@ PROTOS = {
     "kmh_bspline_bending_ws_bytes": (_sz, [_i]),
     "kmh_bspline_bending_fwd": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
     "kmh_bspline_bending_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_bspline_disp_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_svf_compose": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_svf_finish_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_svf_finish_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_svf_square_bwd_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "kmh_svf_square_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f]),
     "kmh_lncc_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_lncc_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f]),
     "kmh_lncc_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f, _f]),

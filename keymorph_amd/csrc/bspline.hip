@@ -10,6 +10,7 @@
 // u is a ratio of integers, u = (2i + 1) K / (2S), so cell and the numerator of t are computed exactly (lat_w) and t is ONE
 // rounded division: a voxel centre that sits on a knot gets t = 0 of the right-hand cell, never a value either side of it.
 //
+// (kmh_bspline_disp_fwd: the sum alone, without the base -- what ops.svf_grid exponentiates.)
 // Forward: a workgroup owns a tile of TY x TX voxels of one z-slice.  The z-contraction of the few lattice rows the tile touches
 // goes to LDS once (Q[k][b][a] = sum_c Bz_c ctrl[k, cz + c, b, a]), each lane takes runs of four voxels along x, contracts y for
 // the run's cell (48 LDS reads, reused while the cell does not change) and x per voxel; the kernel is bound by its 12 B store.
@@ -64,9 +65,11 @@ constexpr int FWD_Q_FLOATS = 8192;            // LDS floats for Q (3 channels x 
 // lattice rows (columns) that T consecutive voxels of an axis can touch: floor((T - 1) K / S) + 1 cells, + 3
 static long long lat_span(int T, int S, int C) { return (long long)(T - 1) * (C - 3) / S + 5; }
 
-__global__ __launch_bounds__(TPB) void bspline_grid_fwd_kernel(const float* __restrict__ ctrl, const float* __restrict__ mat,
-                                                               float* __restrict__ out, int D, int H, int W, int Cz, int Cy,
-                                                               int Cx, int TY, int TX, int tiles_y, int tiles_x) {
+// DISP: the spline alone (kmh_bspline_disp_fwd: no base is added, mat is not read) -- the same code with the base left out
+template <bool DISP>
+__global__ __launch_bounds__(TPB) void bspline_fwd_kernel(const float* __restrict__ ctrl, const float* __restrict__ mat,
+                                                          float* __restrict__ out, int D, int H, int W, int Cz, int Cy, int Cx,
+                                                          int TY, int TX, int tiles_y, int tiles_x) {
   extern __shared__ __attribute__((aligned(16))) float sQ[];
   __shared__ LatW sWx[FWD_TX], sWy[FWD_TY];
   __shared__ float sM[12];
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(TPB) void bspline_grid_fwd_kernel(const float* __re
   const int nyv = H - y0 < TY ? H - y0 : TY, nxv = W - x0 < TX ? W - x0 : TX;
   for (int i = tid; i < nxv; i += TPB) sWx[i] = lat_w(x0 + i, W, Cx);
   for (int i = tid; i < nyv; i += TPB) sWy[i] = lat_w(y0 + i, H, Cy);
-  if (mat && tid < 12) sM[tid] = mat[n * 12 + tid];
+  if (!DISP && mat && tid < 12) sM[tid] = mat[n * 12 + tid];
   const LatW wz = lat_w(z, D, Cz);
   const int cx_lo = lat_cell(x0, W, Cx), cy_lo = lat_cell(y0, H, Cy);
   const int nx = lat_cell(x0 + nxv - 1, W, Cx) + 4 - cx_lo, ny = lat_cell(y0 + nyv - 1, H, Cy) + 4 - cy_lo;
@@ -121,7 +124,9 @@ __global__ __launch_bounds__(TPB) void bspline_grid_fwd_kernel(const float* __re
         }
         const int x = x0 + rx + i;
         float b3[3];      // the base, (x, y, z)
-        if (mat) {
+        if (DISP) {
+          b3[0] = b3[1] = b3[2] = 0.f;
+        } else if (mat) {
           affine_coord_chain(M, bz, by, lin(x, W, sx), b3[0], b3[1], b3[2]);
         } else {
           b3[0] = ident(x, W); b3[1] = by; b3[2] = bz;
@@ -129,7 +134,7 @@ __global__ __launch_bounds__(TPB) void bspline_grid_fwd_kernel(const float* __re
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           const float d = fmaf(wx.w[3], P[3][k], fmaf(wx.w[2], P[2][k], fmaf(wx.w[1], P[1][k], wx.w[0] * P[0][k])));
-          r[i * 3 + k] = b3[k] + d;
+          r[i * 3 + k] = DISP ? d : b3[k] + d;
         }
       }
     }
@@ -383,8 +388,9 @@ static BwdPlan bwd_plan(int N, int D, int H, int W, int Cy, int Cx) {
 
 }  // namespace
 
-KMH_API int kmh_bspline_grid_fwd(const float* ctrl, const float* mat, float* out, int N, int D, int H, int W, int Cz, int Cy,
-                                 int Cx, void* stream) {
+// out = base + spline (disp false) or the spline alone (disp true, mat unused): one launch plan for both
+static int bspline_fwd_launch(bool disp, const float* ctrl, const float* mat, float* out, int N, int D, int H, int W, int Cz, int Cy,
+                              int Cx, void* stream) {
   if (!bspline_args_ok(N, D, H, W, Cz, Cy, Cx) || !ctrl || !out) return -22;
   // the largest tile whose lattice rows x columns fit the LDS budget (a one-voxel tile touches 4 x 4: always fits)
   int TX = W < FWD_TX ? W : FWD_TX, TY = H < FWD_TY ? H : FWD_TY;
@@ -395,9 +401,23 @@ KMH_API int kmh_bspline_grid_fwd(const float* ctrl, const float* mat, float* out
   const int tiles_x = ceil_div(W, TX), tiles_y = ceil_div(H, TY);
   const long long blocks = (long long)tiles_x * tiles_y * D;      // <= the number of voxels < 2^31
   const size_t lds = (size_t)(lat_span(TY, H, Cy) * lat_span(TX, W, Cx) * 3) * sizeof(float);
-  bspline_grid_fwd_kernel<<<dim3((unsigned)blocks, (unsigned)N), TPB, lds, (hipStream_t)stream>>>(ctrl, mat, out, D, H, W, Cz, Cy,
-                                                                                                 Cx, TY, TX, tiles_y, tiles_x);
+  const dim3 g((unsigned)blocks, (unsigned)N);
+  if (disp)
+    bspline_fwd_kernel<true><<<g, TPB, lds, (hipStream_t)stream>>>(ctrl, mat, out, D, H, W, Cz, Cy, Cx, TY, TX, tiles_y, tiles_x);
+  else
+    bspline_fwd_kernel<false><<<g, TPB, lds, (hipStream_t)stream>>>(ctrl, mat, out, D, H, W, Cz, Cy, Cx, TY, TX, tiles_y, tiles_x);
   return KMH_LAUNCH_CHECK();
+}
+
+KMH_API int kmh_bspline_grid_fwd(const float* ctrl, const float* mat, float* out, int N, int D, int H, int W, int Cz, int Cy,
+                                 int Cx, void* stream) {
+  return bspline_fwd_launch(false, ctrl, mat, out, N, D, H, W, Cz, Cy, Cx, stream);
+}
+
+/* The spline alone, out (N, D, H, W, 3) = sum B ctrl: kmh_bspline_grid_fwd without its base (a displacement that is a small
+   fraction of a voxel keeps all its bits); kmh_bspline_grid_bwd is the transpose of both. */
+KMH_API int kmh_bspline_disp_fwd(const float* ctrl, float* out, int N, int D, int H, int W, int Cz, int Cy, int Cx, void* stream) {
+  return bspline_fwd_launch(true, ctrl, nullptr, out, N, D, H, W, Cz, Cy, Cx, stream);
 }
 
 /* Workspace of kmh_bspline_grid_bwd: the x-contracted (N, D, H, Cx, 3) and the y-contracted (N, D, Cy, Cx, 3) intermediates. */

@@ -10,3 +10,4 @@ from .centering import center_to, estimate_translation, translate         # noqa
 from .intensity import (apply_mat, estimate_affine, estimate_rigid, mat_to_voxel, register_intensity,         # noqa: F401
                         rigid_params_to_voxel, rotation_matrix, voxel_to_mat)
 from .bspline import apply_bspline, register_bspline         # noqa: F401
+from .svf import apply_svf, register_svf, svf_grid         # noqa: F401

@@ -1,0 +1,93 @@
+"""Diffeomorphic intensity registration on the GPU: register_bspline's schedule with the control lattice read as a stationary
+VELOCITY field and exponentiated by scaling and squaring (ops.svf_grid) -- the transform model of ANTs SyN and VoxelMorph's
+diffeomorphic variant.  Two things follow that a free-form lattice cannot give: the map does not fold however weak the bending
+penalty is (each squaring step composes a near-identity map with itself), and its inverse costs nothing: exp(-v), the grid that
+carries a FIXED-space volume or label map into moving space.
+
+Conventions.  ctrl (N, 3, Cz, Cy, Cx) is what ops.svf_grid takes: register_bspline's lattice, units and channel order, read as
+velocities.  `mat` (N, 3, 4) is what ops.affine_grid takes; the grid is the matrix applied to the deformed point."""
+import torch
+
+from ._pyramid import as_data, levels, scale_axes
+from .intensity import _conjugate, mat_to_voxel, register_intensity, voxel_to_mat
+
+
+def svf_grid(ctrl, dims, mat=None, steps=6, inverse=False):
+    """ops.svf_grid(ctrl, dims, steps, mat), or with inverse=True the grid of the inverse map: P + U^-(P), U^- the displacement of
+    -ctrl and P the identity lattice (mat None) or ops.affine_grid of the matrix inverted in voxel space -- align_img of it
+    resamples a FIXED-space volume into moving space.  The inverse is not differentiable.  Content that the forward map moves out
+    of the field of view has no inverse: near the border the two do not compose to the identity."""
+    from .. import fields, ops
+    if not inverse:
+        return ops.svf_grid(ctrl, dims, steps, mat)
+    if ctrl.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("svf_grid: inverse=True is not differentiable: pass ctrl.detach() or call it under torch.no_grad()")
+    with torch.no_grad():
+        if mat is None:
+            return ops.svf_grid(-ctrl.detach(), dims, steps)
+        dims = tuple(int(n) for n in dims)
+        um = ops.svf_displacement(-ctrl.detach(), dims, steps)
+        L, t = mat_to_voxel(mat.detach(), dims)
+        inv = ops.affine_inverse(torch.cat([L, t[:, :, None]], dim=2))
+        P = ops.affine_grid(voxel_to_mat(inv[:, :, :3].contiguous(), inv[:, :, 3].contiguous(), dims), dims)
+        return ops.svf_compose(um, P)
+
+
+def apply_svf(x, ctrl, mat=None, steps=6, inverse=False, mode="bilinear"):
+    """align_img(svf_grid(ctrl, dims, mat, steps, inverse), x, mode): x (N, C, D, H, W) resampled through the diffeomorphism (a
+    moving-space volume into fixed space) or, inverse=True, through its inverse (a fixed-space volume into moving space)."""
+    from ..utils import align_img
+    return align_img(svf_grid(ctrl, x.shape[2:], mat, steps, inverse), x, mode)
+
+
+def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps=6, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
+                 metric="mi", window=9):
+    """ctrl (N, 3, Cz, Cy, Cx), a lattice of velocities on ops.bspline_lattice_shape(dims, control_spacing), such that
+    apply_svf(moving, ctrl, mat, steps) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape).  This is
+    register_bspline's schedule with ops.svf_grid(., steps) in place of ops.bspline_grid: the same pyramid, per-level units (the
+    lattice is stepped in voxels of the level), Adam, bending penalty on the lattice, both metrics ("mi", "lncc"), and the same
+    default affine start (register_intensity) when mat is None.  The loss is a sum, so every sample is optimised on its own, and
+    every kernel under it sums in a fixed or order-independent way: a batch equals its samples, bit for bit.
+
+    Nothing inside the loop waits for the GPU."""
+    from .. import ops
+    from ..utils import align_img
+    if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
+        raise ValueError(f"register_svf: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
+                         f"{tuple(moving.shape)}")
+    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
+    if mat is not None and tuple(mat.shape) != (N, 3, 4):
+        raise ValueError(f"register_svf: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
+    if metric not in ("mi", "lncc"):
+        raise ValueError(f"register_svf: metric must be 'mi' or 'lncc', got {metric!r}")
+    if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= ops.SVF_MAX_STEPS:
+        raise ValueError(f"register_svf: steps must be an integer in 0 .. {ops.SVF_MAX_STEPS}, got {steps!r}")
+    lattice = ops.bspline_lattice_shape(dims, control_spacing)
+    with torch.inference_mode(False), torch.enable_grad():
+        fixed, moving = as_data(fixed), as_data(moving)
+        if mat is None:
+            mat = register_intensity(fixed, moving, "affine", bins=bins, shrink=shrink)
+        mat = as_data(mat)
+        q = torch.zeros((N, 3, *lattice), dtype=torch.float32, device=fixed.device)      # voxels of the full size, (x, y, z)
+        with torch.no_grad():
+            L, t = mat_to_voxel(mat, dims)
+        for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):            # ratio in (z, y, x), q's channels in (x, y, z)
+            with torch.no_grad():
+                rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
+                mat_l = voxel_to_mat(_conjugate(L, ratio), scale_axes(t, ratio, divide=True), ldims)
+                q_l = scale_axes(q, [1.0 / r for r in reversed(ratio)])
+            q_l.requires_grad_(True)
+            to_norm = [2.0 / n for n in reversed(ldims)]
+            opt = torch.optim.Adam([q_l], lr=lr)
+            for _ in range(iters):
+                opt.zero_grad(set_to_none=True)
+                warped = align_img(ops.svf_grid(scale_axes(q_l, to_norm), ldims, steps, mat_l), m_l)
+                if metric == "mi":
+                    sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
+                else:
+                    sim = ops.local_ncc(warped, f_l, window)
+                loss = (bending * ops.bspline_bending(q_l) - sim).sum()
+                loss.backward()
+                opt.step()
+            q = scale_axes(q_l.detach(), list(reversed(ratio)))
+        return scale_axes(q, [2.0 / n for n in reversed(dims)])

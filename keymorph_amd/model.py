@@ -359,7 +359,7 @@ class KeyMorph(nn.Module):
 # reference never shipped): multi-resolution mutual-information registration, io.register_intensity, behind KeyMorph's call.
 # ----------------------------------------------------------------------------------------------------------------------
 class IntensityRegistration(nn.Module):
-    """model(img_f, img_m, transform_type="translation" | "rigid" | "affine" | "bspline" | [..],
+    """model(img_f, img_m, transform_type="translation" | "rigid" | "affine" | "bspline" | "svf" | [..],
     num_resolutions_for_itkelastix=None, **ignored) -> {type: {"grid" (N, D, H, W, 3), "matrix" (N, 3, 4) as ops.affine_grid
     takes it, "mi" (N,) the mutual information reached, "time"}}.  No parameters.  num_resolutions_for_itkelastix = k means the
     pyramid 2^(k-1) .. 1 (None: 4, 2, 1).
@@ -367,18 +367,23 @@ class IntensityRegistration(nn.Module):
     (N, 3, Cz, Cy, Cx) in addition, "matrix" is the affine it started from, "grid" = ops.bspline_grid(ctrl, dims, matrix) and
     "mi" = ops.mutual_information of the warped pair.  metric="lncc": the "bspline" entry is fitted by local normalised
     cross-correlation over window^3 cubes (io.register_bspline(metric="lncc")) and has "lncc" (N,) = ops.local_ncc of the warped pair
-    in addition; the matrix stages stay on mutual information."""
+    in addition; the matrix stages stay on mutual information.
+    "svf": the diffeomorphism of io.register_svf (the same lattice, schedule, metric and constructor arguments as "bspline", read
+    as velocities and exponentiated in svf_steps squarings) on top of the affine answer; its entry is the "bspline" one with
+    "grid" = ops.svf_grid(ctrl, dims, svf_steps, matrix) and, in addition, "inverse_grid" = io.svf_grid(ctrl, dims, matrix,
+    svf_steps, inverse=True), the grid that resamples a fixed-space volume into moving space."""
 
-    supported_transform_type = ("translation", "rigid", "affine", "bspline")
+    supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf")
 
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
-                 metric="mi", window=9):
+                 metric="mi", window=9, svf_steps=6):
         super().__init__()
         if metric not in ("mi", "lncc"):
             raise ValueError(f"IntensityRegistration: metric must be 'mi' or 'lncc', got {metric!r}")
         self.bins, self.iters, self.lr = bins, iters, lr
         self.metric, self.window = metric, window
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
+        self.svf_steps = svf_steps
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
         from . import ops
@@ -394,19 +399,29 @@ class IntensityRegistration(nn.Module):
         result_dict = {}
         for align_type_str in transform_type:
             start_time = time.time()
-            bspline = align_type_str == "bspline"
+            svf = align_type_str == "svf"
+            bspline = svf or align_type_str == "bspline"                       # the deformable stages: a lattice on top of the affine answer
             mat = register_intensity(img_f, img_m, "affine" if bspline else align_type_str, bins=self.bins, shrink=shrink,
                                      iters=self.iters, lr=self.lr)
             if bspline:
                 from .io.bspline import register_bspline
+                from .io.svf import register_svf, svf_grid
                 from .utils import align_img
-                ctrl = register_bspline(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending,
-                                        bins=self.bins, shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr,
-                                        metric=self.metric, window=self.window)
+                common = dict(control_spacing=self.control_spacing, bending=self.bending, bins=self.bins, shrink=shrink,
+                              iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window)
+                if svf:
+                    ctrl = register_svf(img_f, img_m, mat, steps=self.svf_steps, **common)
+                else:
+                    ctrl = register_bspline(img_f, img_m, mat, **common)
                 with torch.no_grad():
-                    grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
+                    if svf:
+                        grid = ops.svf_grid(ctrl, img_f.shape[2:], self.svf_steps, mat)
+                    else:
+                        grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
                     warped = align_img(grid, img_m)
                     res = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": ops.mutual_information(warped, img_f, self.bins)}
+                    if svf:
+                        res["inverse_grid"] = svf_grid(ctrl, img_f.shape[2:], mat, self.svf_steps, inverse=True)
                     if self.metric == "lncc":
                         res["lncc"] = ops.local_ncc(warped, img_f, self.window)
             else:

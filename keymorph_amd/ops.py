@@ -508,6 +508,125 @@ def bspline_bending(q: Tensor) -> Tensor:
     return _BsplineBending.apply(q.contiguous())
 
 
+# --------------------------------------------------------------------------
+# diffeomorphic grids: a lattice of velocities exponentiated by scaling and squaring (csrc/svf.hip)
+# --------------------------------------------------------------------------
+SVF_MAX_STEPS = 12
+
+
+def _svf_forward(ctrl, mat, dims, steps, keep):
+    """(grid or u_K, [u_0 .. u_{K-1}] if keep).  mat False: the displacement u_K is returned as it is (no finish)."""
+    lib = _lib.load()
+    N, _, Cz, Cy, Cx = ctrl.shape
+    D, H, W = dims
+    small = ctrl * (2.0 ** -steps) if steps else ctrl                 # a power of two: exact
+    u = torch.empty((N, D, H, W, 3), dtype=torch.float32, device=ctrl.device)
+    check(lib.kmh_bspline_disp_fwd(_p(small), _p(u), N, D, H, W, Cz, Cy, Cx, _stream()), "kmh_bspline_disp_fwd")
+    us = []
+    for _ in range(steps):
+        nxt = torch.empty_like(u)
+        if _lib.profiler.enabled:  # 12 B read + 12 B written per voxel, the gathers from cache
+            _lib.profiler.meta = {"bytes": 24.0 * N * D * H * W}
+        check(lib.kmh_svf_compose(_p(u), None, None, _p(nxt), N, D, H, W, _stream()), "kmh_svf_compose")
+        if keep:
+            us.append(u)
+        u = nxt
+    if mat is not False:
+        check(lib.kmh_svf_finish_fwd(_p(u), _p(mat), _p(u), N, D, H, W, _stream()), "kmh_svf_finish_fwd")
+    return u, us
+
+
+class _SvfGrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctrl, mat, steps, D, H, W):
+        grid, us = _svf_forward(ctrl, mat, (D, H, W), steps, True)
+        ctx.save_for_backward(*us)
+        ctx.mat, ctx.steps, ctx.dims = mat, steps, (ctrl.shape[0], D, H, W, *ctrl.shape[2:])
+        return grid
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        us, steps, mat = ctx.saved_tensors, ctx.steps, ctx.mat
+        N, D, H, W, Cz, Cy, Cx = ctx.dims
+        g = _prep(g)
+        du = torch.empty_like(g)
+        amax = torch.zeros((steps + 1, N), dtype=torch.int32, device=g.device)      # float bits of the largest finite |cotangent|
+        check(lib.kmh_svf_finish_bwd(_p(g), _p(mat), _p(du), _p(amax[steps]), N, D, H, W, _stream()), "kmh_svf_finish_bwd")
+        if steps:
+            ws = workspace(int(lib.kmh_svf_square_bwd_ws_bytes(N, D, H, W)), g.device, "svf_bwd")
+            for k in range(steps - 1, -1, -1):
+                if _lib.profiler.enabled:  # 32 cleared + 36 + 32 + 24 B per voxel, and 24 eight-byte atomics
+                    _lib.profiler.meta = {"bytes": 124.0 * N * D * H * W}
+                check(lib.kmh_svf_square_bwd(_p(us[k]), _p(du), _p(du), _p(amax[k + 1]), _p(amax[k]) if k else None, N, D, H, W,
+                                             _p(ws), _stream()), "kmh_svf_square_bwd")
+        dctrl = torch.empty((N, 3, Cz, Cy, Cx), dtype=torch.float32, device=g.device)
+        ws = workspace(int(lib.kmh_bspline_grid_ws_bytes(N, D, H, W, Cz, Cy, Cx)), g.device, "bspline_bwd")
+        check(lib.kmh_bspline_grid_bwd(_p(du), _p(dctrl), N, D, H, W, Cz, Cy, Cx, _p(ws), _stream()), "kmh_bspline_grid_bwd")
+        if steps:
+            dctrl = dctrl * (2.0 ** -steps)
+        return dctrl, None, None, None, None, None
+
+
+def _svf_check(who, ctrl, shape, steps, mat):
+    _lattice_check(ctrl, "ctrl", who)
+    dims = tuple(int(s) for s in shape)
+    if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] * 3 >= 1 << 30:
+        raise ValueError(f"{who}: shape must be three positive sizes (D, H, W) with D * H * W * 3 < 2^30, got {tuple(shape)}")
+    if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= SVF_MAX_STEPS:
+        raise ValueError(f"{who}: steps must be an integer in 0 .. {SVF_MAX_STEPS}, got {steps!r}")
+    if mat is not None:
+        _need_gpu(who, "mat", mat)
+        if mat.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who}: mat requires grad, and {who} is differentiable in ctrl only: pass mat.detach()")
+        if mat.dtype != torch.float32 or tuple(mat.shape) != (ctrl.shape[0], 3, 4):
+            raise ValueError(f"{who}: mat must be float32 ({ctrl.shape[0]}, 3, 4), got {mat.dtype} {tuple(mat.shape)}")
+        if min(dims) < 2:
+            raise ValueError(f"{who}: with a matrix every axis needs at least two voxels, got {dims}")
+        mat = mat.detach().contiguous()
+    return dims, int(steps), mat
+
+
+def svf_grid(ctrl: Tensor, shape: Sequence[int], steps: int = 6, mat: Optional[Tensor] = None) -> Tensor:
+    """The sampling grid (N, D, H, W, 3) of a diffeomorphism: ctrl (N, 3, Cz, Cy, Cx) float32 on the current GPU is a cubic B-spline
+    lattice of VELOCITIES in bspline_grid's units and order, and the grid is the exponential of that stationary velocity field by
+    scaling and squaring, in displacement form:
+        u_0 = the spline of ctrl 2^-steps (no base),   u_{k+1}[w] = u_k[w] + U_k(Ids[w] + u_k[w])   `steps` times,
+    U_k the trilinear interpolant of u_k with border clamping (the sampler's), Ids = fields.identity_grid; then
+        grid = Ids + u_K   (mat None)   or   grid = ops.affine_grid(mat, shape) + L (s * u_K),  L = mat[:, :, :3], s = S / (S - 1) per axis
+    -- the matrix applied to the deformed point.  A zero lattice gives exactly the base; steps = 0 is bspline_grid (with the matrix
+    applied analytically instead of added to).  The inverse map is svf_grid(-ctrl, ...): see io.svf_grid(inverse=True).
+    steps in 0 .. 12; D * H * W * 3 < 2^30.  Differentiable in ctrl only (mat is data: one that requires grad raises); the backward
+    keeps u_0 .. u_{K-1} (12 B per voxel each) and sums its scatter in 64-bit fixed point, so two calls give bit-identical grids and
+    gradients and a batch equals its samples."""
+    dims, steps, mat = _svf_check("svf_grid", ctrl, shape, steps, mat)
+    return _SvfGrid.apply(ctrl.contiguous(), mat, steps, *dims)
+
+
+def svf_displacement(ctrl: Tensor, shape: Sequence[int], steps: int = 6) -> Tensor:
+    """u_K of svf_grid (N, D, H, W, 3), normalised, on the voxel-centre lattice: svf_grid(ctrl, shape, steps) is
+    fields.identity_grid + this, bit for bit.  Not differentiable (ctrl is detached)."""
+    dims, steps, _ = _svf_check("svf_displacement", ctrl, shape, steps, None)
+    return _svf_forward(ctrl.detach().contiguous(), False, dims, steps, False)[0]
+
+
+def svf_compose(u: Tensor, first: Tensor, add: Optional[Tensor] = None) -> Tensor:
+    """add + U(first): the displacement u (N, D, H, W, 3) interpolated (trilinear, border-clamped) at the grid `first` of the same
+    shape, plus `add` (None: first itself, which gives the grid first + U(first)).  Not differentiable: inputs are detached."""
+    for name, t in (("u", u), ("first", first), ("add", first if add is None else add)):
+        _need_gpu_f32("svf_compose", name, t)
+        if t.dim() != 5 or t.shape[-1] != 3 or t.shape != u.shape or t.numel() == 0:
+            raise ValueError(f"svf_compose: {name} must be (N, D, H, W, 3) like u, got {tuple(t.shape)} and {tuple(u.shape)}")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"svf_compose: {name} requires grad, and svf_compose is not differentiable: pass {name}.detach()")
+    u, first = u.detach().contiguous(), first.detach().contiguous()
+    add = first if add is None else add.detach().contiguous()
+    N, D, H, W, _ = u.shape
+    out = torch.empty_like(u)
+    check(_lib.load().kmh_svf_compose(_p(u), _p(first), _p(add), _p(out), N, D, H, W, _stream()), "kmh_svf_compose")
+    return out
+
+
 class _TpsPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, ctrl, pts):

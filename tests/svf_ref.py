@@ -1,0 +1,206 @@
+"""The definition of keymorph_amd.ops.svf_grid restated in plain torch (dtype-generic: fp64 for the yardstick, fp32 for the size
+of fp32's own error), the recovery pair of tests/bspline_ref.py at any amplitude, and the schedule of keymorph_amd.io.register_svf
+rebuilt from F.grid_sample, F.interpolate and tests/mi_ref.py.
+
+ctrl (N, 3, Cz, Cy, Cx) is a cubic B-spline lattice of VELOCITIES, in ops.bspline_grid's units and order.  With K = steps:
+    u_0 = displacement(ctrl 2^-K)                       (the spline alone, bspline_ref.displacement: no base is added and taken off)
+    u_{k+1}[w] = u_k[w] + U_k(Ids[w] + u_k[w])          (U_k: the trilinear interpolant of u_k on the sampler's align_corners=False
+                                                         lattice with border clamping -- F.grid_sample(padding_mode="border"))
+    grid = Ids + u_K                                    (mat None)
+    grid = affine_grid(mat)[w] + M[:, :3] (s * u_K[w])  (mat (N, 3, 4); s = S / (S - 1) per axis takes a displacement on the
+                                                         voxel-centre lattice to the linspace(-1, 1, S) lattice the matrix acts on)
+The backward is torch's autograd of exactly this: F.grid_sample's border clamp has a zero derivative, as the sampler's."""
+import functools
+
+import torch
+import torch.nn.functional as F
+
+from tests import bspline_ref as R
+from tests import warp_mi_ref as W
+
+F64 = torch.float64
+
+
+def interpolate(u, pts):
+    """u (N, D, H, W, 3) at pts (N, ..., 3) xyz: trilinear, border-clamped, align_corners=False."""
+    shape = pts.shape
+    p = pts.reshape(shape[0], 1, 1, -1, 3)
+    out = F.grid_sample(u.permute(0, 4, 1, 2, 3), p, mode="bilinear", padding_mode="border", align_corners=False)
+    return out.permute(0, 2, 3, 4, 1).reshape(shape)
+
+
+def square(u, ids):
+    return u + interpolate(u, ids + u)
+
+
+def displacements(ctrl, dims, steps):
+    """[u_0, ..., u_K], each (N, D, H, W, 3) in ctrl's dtype."""
+    dims = tuple(int(n) for n in dims)
+    ids = R.identity(dims, ctrl.dtype)[None]
+    us = [R.displacement(ctrl * 2.0 ** -int(steps), dims)]
+    for _ in range(int(steps)):
+        us.append(square(us[-1], ids))
+    return us
+
+
+def finish(u, dims, mat=None):
+    """The grid of the displacement u: Ids + u, or the matrix applied to the deformed point."""
+    dims = tuple(int(n) for n in dims)
+    if mat is None:
+        return R.identity(dims, u.dtype)[None] + u
+    mat = mat.to(u.dtype)
+    s = torch.tensor([n / (n - 1) for n in dims], dtype=u.dtype)                # (z, y, x)
+    return W.grid_of(mat, dims) + torch.einsum("nrk,ndhwk->ndhwr", mat[:, :, :3], u.flip(-1) * s).flip(-1)
+
+
+def svf_grid(ctrl, dims, steps=6, mat=None):
+    return finish(displacements(ctrl, dims, steps)[-1], dims, mat)
+
+
+def inverse_grid(ctrl, dims, steps=6, mat=None):
+    """P + U^-(P), U^- the displacement of -ctrl, P = Ids or the grid of the matrix inverted in voxel space: what
+    io.svf_grid(inverse=True) computes."""
+    dims = tuple(int(n) for n in dims)
+    um = displacements(-ctrl, dims, steps)[-1]
+    if mat is None:
+        return R.identity(dims, ctrl.dtype)[None] + um
+    n = torch.tensor([float(d) for d in dims], dtype=F64)
+    m = mat.to(F64)
+    L = m[:, :, :3] * n[None, :, None] / (n - 1)[None, None, :]
+    t = m[:, :, 3] * n[None, :] / 2
+    Li = torch.linalg.inv(L)
+    P = W.grid_of(W.voxel_to_mat(Li, -torch.einsum("nab,nb->na", Li, t), dims).to(ctrl.dtype), dims)
+    return P + interpolate(um, P)
+
+
+def random_lattice(dims, spacing, amplitude_vox, seed, n=1):
+    """(n, 3, Cz, Cy, Cx) fp64 on bspline_ref.lattice_shape(dims, spacing): uniform in [-1, 1] times amplitude_vox voxels,
+    normalised, (x, y, z)."""
+    lat = R.lattice_shape(dims, spacing)
+    c = 2 * torch.rand(n, 3, *lat, dtype=F64, generator=torch.Generator().manual_seed(seed)) - 1
+    return c * amplitude_vox * torch.tensor([2.0 / dims[2], 2.0 / dims[1], 2.0 / dims[0]], dtype=F64)[None, :, None, None, None]
+
+
+def random_mats(n, seed=5):
+    """(n, 3, 4) fp64: rotation + shear + scale + shift, another one per sample (keymorph_amd.synthetic.random_affine_matrix)."""
+    from keymorph_amd import synthetic
+    return torch.cat([synthetic.random_affine_matrix(seed + k, "cpu")[:, :3, :] for k in range(n)]).contiguous().double()
+
+
+def evaluate_grid(ctrl, dims, steps, mat, cot, dtype):
+    """(grid, d (grid * cot).sum() / d ctrl) of float32 inputs evaluated in `dtype` on the CPU."""
+    c = ctrl.detach().cpu().to(dtype).requires_grad_(True)
+    g = svf_grid(c, dims, steps, None if mat is None else mat.detach().cpu().to(dtype))
+    (dc,) = torch.autograd.grad((g * cot.detach().cpu().to(dtype)).sum(), c)
+    return g.detach(), dc
+
+
+def voxel_displacement(grid):
+    """(N, 3, D, H, W), channels (z, y, x), voxels, of a grid near the identity: tests/fields_ref.py::to_displacement."""
+    from tests import fields_ref
+    return fields_ref.to_displacement(grid)
+
+
+def min_jacobian(grid):
+    """(minimum, number of non-positive values) of the central-difference Jacobian determinant on the interior voxels."""
+    from tests import fields_ref
+    det = fields_ref.jacobian_det_central(voxel_displacement(grid))
+    return float(det.min()), int((det <= 0).sum())
+
+
+def inverse_consistency(fwd, inv, max_u_vox):
+    """max |fwd(inv[w]) - Ids[w]| in voxels over the voxels further than ceil(max|u|) + 1 from every face (content that leaves
+    the field of view has no inverse).  fwd, inv (N, D, H, W, 3) in fp64."""
+    from tests import fields_ref
+    n, D, H, Wd, _ = fwd.shape
+    m = int(-(-max_u_vox // 1)) + 1
+    r = (fields_ref.compose(inv, fwd) - R.identity((D, H, Wd))[None]) * torch.tensor([Wd / 2, H / 2, D / 2], dtype=F64)
+    assert min(D, H, Wd) > 2 * m + 1, "the field is too large for the volume: no voxel is left"
+    return float(r[:, m + 1:D - m - 1, m + 1:H - m - 1, m + 1:Wd - m - 1].abs().max())
+
+
+# ---- the recovery pair at any amplitude (bspline_ref's generator, its AMPLITUDE a parameter) ----------------------------------------
+@functools.lru_cache(maxsize=None)
+def true_ctrl(amplitude=R.AMPLITUDE, seed=R.SEED, size=R.SIZE):
+    c = 2 * torch.rand(1, 3, 3, 3, 3, dtype=F64, generator=torch.Generator().manual_seed(seed)) - 1
+    lat = R.lattice_shape((size,) * 3, R.SPACING)
+    return F.interpolate(c, lat, mode="trilinear", align_corners=True) * amplitude * 2 / size
+
+
+@functools.lru_cache(maxsize=None)
+def recovery_pair(amplitude=R.AMPLITUDE, seed=R.SEED, size=R.SIZE):
+    """bspline_ref.recovery_pair with the true lattice scaled to `amplitude` voxels (4: the same pair, bit for bit)."""
+    dims = (size,) * 3
+    v = torch.stack(torch.meshgrid(*[torch.arange(d, dtype=F64) for d in dims], indexing="ij"), dim=-1)
+    raw = W._field_at(size, R.TEXTURE_SEED, v, dense=True)
+    lo, hi = raw.min(), raw.max()
+    g = R.bspline_grid(true_ctrl(amplitude, seed, size), dims)[0].flip(-1)
+    T = ((g + 1) * size - 1) / 2
+    fixed = ((W._field_at(size, R.TEXTURE_SEED, T, dense=True) - lo) / (hi - lo)).clamp(0, 1)
+
+    def remap(x):
+        return 0.8 * (1 - x) ** 2 + 0.2 * torch.sin(6 * x) ** 2
+    table = remap(torch.linspace(0, 1, 4097, dtype=F64))
+    rlo, rhi = table.min(), table.max()
+    moving = ((remap((raw - lo) / (hi - lo)) - rlo) / (rhi - rlo)).clamp(0, 1)
+    return fixed[None, None].float(), moving[None, None].float()
+
+
+def grid_error(grid, amplitude, dims):
+    """Per sample, the mean over the voxel lattice of |grid - true grid| in voxels (the true grid: the FFD of true_ctrl)."""
+    d = grid.detach().cpu().to(F64) - R.bspline_grid(true_ctrl(amplitude), dims)
+    half = torch.tensor([dims[2] / 2, dims[1] / 2, dims[0] / 2], dtype=F64)
+    return (d * half).norm(dim=-1).mean(dim=(1, 2, 3))
+
+
+# ---- the driver's schedule --------------------------------------------------------------------------------------------------------
+def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, steps=6, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
+             dtype=F64, similarity=R.mi_similarity):
+    """keymorph_amd.io.register_svf with a given matrix, on the CPU in `dtype`: bspline_ref.register with svf_grid in place of
+    bspline_grid."""
+    fixed, moving, mat = fixed.detach().to(dtype), moving.detach().to(dtype), mat.detach().to(F64)
+    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
+    n = torch.tensor([float(d) for d in dims], dtype=F64)
+    L = mat[:, :, :3] * n[None, :, None] / (n - 1)[None, None, :]
+    t = mat[:, :, 3] * n[None, :] / 2
+    q = torch.zeros((N, 3, *R.lattice_shape(dims, control_spacing)), dtype=dtype)
+    for sh in shrink:
+        ldims = tuple(d // int(sh) for d in dims)
+        if min(ldims) < 16:
+            continue
+        if ldims == dims:
+            f_l, m_l = fixed, moving
+        else:
+            f_l = F.interpolate(fixed, size=ldims, mode="trilinear", align_corners=False)
+            m_l = F.interpolate(moving, size=ldims, mode="trilinear", align_corners=False)
+        level = {"moving": m_l, "bins": bins}
+        ratio = torch.tensor([d / l for d, l in zip(dims, ldims)], dtype=F64)
+        mat_l = W.voxel_to_mat(L * ratio[None, None, :] / ratio[None, :, None], t / ratio[None, :], ldims).to(dtype)
+        rx = ratio.flip(0).to(dtype)[None, :, None, None, None]
+        to_norm = torch.tensor([2.0 / ldims[2], 2.0 / ldims[1], 2.0 / ldims[0]], dtype=dtype)[None, :, None, None, None]
+        q_l = (q / rx).requires_grad_(True)
+        opt = torch.optim.Adam([q_l], lr=lr)
+        for _ in range(iters):
+            opt.zero_grad(set_to_none=True)
+            warped = F.grid_sample(m_l, svf_grid(q_l * to_norm, ldims, steps, mat_l), mode="bilinear", padding_mode="border",
+                                   align_corners=False)
+            (bending_weight * R.bending(q_l) - similarity(warped, f_l, level)).sum().backward()
+            opt.step()
+        q = q_l.detach() * rx
+    return q * torch.tensor([2.0 / dims[2], 2.0 / dims[1], 2.0 / dims[0]], dtype=dtype)[None, :, None, None, None]
+
+
+@functools.lru_cache(maxsize=None)
+def recovery_run(amplitude=R.AMPLITUDE, bending_weight=0.05, steps=6):
+    """The velocity lattice the restated driver finds on the recovery pair from the identity matrix, fp64."""
+    fixed, moving = recovery_pair(amplitude)
+    dims = tuple(fixed.shape[2:])
+    return register(fixed, moving, R.identity_mat(1, dims), bending_weight=bending_weight, steps=steps)
+
+
+@functools.lru_cache(maxsize=None)
+def ffd_run(amplitude, bending_weight):
+    """The free-form lattice bspline_ref.register finds on the same pair, fp64."""
+    fixed, moving = recovery_pair(amplitude)
+    dims = tuple(fixed.shape[2:])
+    return R.register(fixed, moving, R.identity_mat(1, dims), bending_weight=bending_weight)
