@@ -633,6 +633,22 @@ int kmh_lncc_fwd(const float* a, const float* b, int N, int D, int H, int W, int
 int kmh_lncc_bwd(const float* a, const float* b, const float* gout, int N, int D, int H, int W, int window, float eps,
                  float* da, float* db, void* ws, void* stream);
 
+/* ---- MIND-SSC, the self-similarity context descriptor as a similarity (csrc/mind.hip states the definition) ---- */
+/* a, b: (N, D, H, W) float32 contiguous, fewer than 2^31 voxels per sample; radius and dilation in 1..3.  bounds (N, 2, 2) =
+ * [a or b][lo or hi], the clamp of the descriptor's variance, constants of the call: kmh_mind_bounds writes (1e-3, 1e3) x each
+ * sample's mean of it.  out[n] = mean over the voxels and the 12 channels of (M_c(a) - M_c(b))^2, >= 0, lower is better.
+ * kmh_mind_bwd: da = gout[n] d out[n] / da, db likewise, either may be NULL.  ws: kmh_mind_ws_bytes bytes (two floats per tile
+ * and sample, and the backward's 18 fields of one side: 72 bytes per voxel); the backward reads nothing the forward left there.
+ * No atomics: runs repeat bit for bit and a batch equals its samples.  -22 for a radius or dilation outside 1..3, N < 1, an
+ * empty volume, 2^31 voxels or more, or a null pointer; kmh_mind_ws_bytes is 0 for those. */
+size_t kmh_mind_ws_bytes(int N, int D, int H, int W, int radius, int dilation);
+int kmh_mind_bounds(const float* a, const float* b, int N, int D, int H, int W, int radius, int dilation, float* bounds,
+                    void* ws, void* stream);
+int kmh_mind_fwd(const float* a, const float* b, const float* bounds, int N, int D, int H, int W, int radius, int dilation,
+                 float* out, void* ws, void* stream);
+int kmh_mind_bwd(const float* a, const float* b, const float* bounds, const float* gout, int N, int D, int H, int W, int radius,
+                 int dilation, float* da, float* db, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

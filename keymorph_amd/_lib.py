@@ -183,6 +183,10 @@ PROTOS = {
     "kmh_lncc_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_lncc_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f]),
     "kmh_lncc_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f, _f]),
+    "kmh_mind_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "kmh_mind_bounds": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "kmh_mind_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "kmh_mind_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
 }
 
 _lib = None

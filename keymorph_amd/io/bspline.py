@@ -21,7 +21,7 @@ def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
 
 
 def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-                     metric="mi", window=9):
+                     metric="mi", window=9, mind_radius=1, mind_dilation=2):
     """ctrl (N, 3, Cz, Cy, Cx) on the lattice ops.bspline_lattice_shape(dims, control_spacing) such that
     apply_bspline(moving, ctrl, mat) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual
     information.  mat (N, 3, 4): the affine part, data; None: register_intensity(fixed, moving, "affine", bins=bins,
@@ -40,6 +40,11 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     computed): the local metric of ANTs and VoxelMorph, for one modality under a smooth bias field, which a global histogram
     cannot see.  The default affine start stays register_intensity's.
 
+    metric="mind": the similarity is -ops.mind_ssc_loss(warped, f_l, mind_radius, mind_dilation, bounds), the MIND-SSC
+    self-similarity context distance: a local metric for two modalities (MR to CT, T1 to T2 under a coil bias).  `bounds`, the
+    clamp of the descriptor's variance, is ops.mind_bounds(m_l, f_l, ...) of the level's unwarped pair, once per level, where the
+    mutual information has its ranges.
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     from ..utils import align_img
@@ -49,8 +54,8 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     if mat is not None and tuple(mat.shape) != (N, 3, 4):
         raise ValueError(f"register_bspline: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
-    if metric not in ("mi", "lncc"):
-        raise ValueError(f"register_bspline: metric must be 'mi' or 'lncc', got {metric!r}")
+    if metric not in ("mi", "lncc", "mind"):
+        raise ValueError(f"register_bspline: metric must be 'mi', 'lncc' or 'mind', got {metric!r}")
     lattice = ops.bspline_lattice_shape(dims, control_spacing)
     with torch.inference_mode(False), torch.enable_grad():
         fixed, moving = as_data(fixed), as_data(moving)
@@ -63,6 +68,7 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
         for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):            # ratio in (z, y, x), q's channels in (x, y, z)
             with torch.no_grad():
                 rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
+                bounds = ops.mind_bounds(m_l, f_l, mind_radius, mind_dilation) if metric == "mind" else None
                 mat_l = voxel_to_mat(_conjugate(L, ratio), scale_axes(t, ratio, divide=True), ldims)
                 q_l = scale_axes(q, [1.0 / r for r in reversed(ratio)])
             q_l.requires_grad_(True)
@@ -73,8 +79,10 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
                 warped = align_img(ops.bspline_grid(scale_axes(q_l, to_norm), ldims, mat_l), m_l)
                 if metric == "mi":
                     sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
-                else:
+                elif metric == "lncc":
                     sim = ops.local_ncc(warped, f_l, window)
+                else:
+                    sim = -ops.mind_ssc_loss(warped, f_l, mind_radius, mind_dilation, bounds)
                 loss = (bending * ops.bspline_bending(q_l) - sim).sum()
                 loss.backward()
                 opt.step()

@@ -41,11 +41,11 @@ def apply_svf(x, ctrl, mat=None, steps=6, inverse=False, mode="bilinear"):
 
 
 def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps=6, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-                 metric="mi", window=9):
+                 metric="mi", window=9, mind_radius=1, mind_dilation=2):
     """ctrl (N, 3, Cz, Cy, Cx), a lattice of velocities on ops.bspline_lattice_shape(dims, control_spacing), such that
     apply_svf(moving, ctrl, mat, steps) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape).  This is
     register_bspline's schedule with ops.svf_grid(., steps) in place of ops.bspline_grid: the same pyramid, per-level units (the
-    lattice is stepped in voxels of the level), Adam, bending penalty on the lattice, both metrics ("mi", "lncc"), and the same
+    lattice is stepped in voxels of the level), Adam, bending penalty on the lattice, the metrics "mi", "lncc" and "mind", and the same
     default affine start (register_intensity) when mat is None.  The loss is a sum, so every sample is optimised on its own, and
     every kernel under it sums in a fixed or order-independent way: a batch equals its samples, bit for bit.
 
@@ -58,8 +58,8 @@ def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     if mat is not None and tuple(mat.shape) != (N, 3, 4):
         raise ValueError(f"register_svf: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
-    if metric not in ("mi", "lncc"):
-        raise ValueError(f"register_svf: metric must be 'mi' or 'lncc', got {metric!r}")
+    if metric not in ("mi", "lncc", "mind"):
+        raise ValueError(f"register_svf: metric must be 'mi', 'lncc' or 'mind', got {metric!r}")
     if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= ops.SVF_MAX_STEPS:
         raise ValueError(f"register_svf: steps must be an integer in 0 .. {ops.SVF_MAX_STEPS}, got {steps!r}")
     lattice = ops.bspline_lattice_shape(dims, control_spacing)
@@ -74,6 +74,7 @@ def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps
         for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):            # ratio in (z, y, x), q's channels in (x, y, z)
             with torch.no_grad():
                 rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
+                bounds = ops.mind_bounds(m_l, f_l, mind_radius, mind_dilation) if metric == "mind" else None
                 mat_l = voxel_to_mat(_conjugate(L, ratio), scale_axes(t, ratio, divide=True), ldims)
                 q_l = scale_axes(q, [1.0 / r for r in reversed(ratio)])
             q_l.requires_grad_(True)
@@ -84,8 +85,10 @@ def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps
                 warped = align_img(ops.svf_grid(scale_axes(q_l, to_norm), ldims, steps, mat_l), m_l)
                 if metric == "mi":
                     sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
-                else:
+                elif metric == "lncc":
                     sim = ops.local_ncc(warped, f_l, window)
+                else:
+                    sim = -ops.mind_ssc_loss(warped, f_l, mind_radius, mind_dilation, bounds)
                 loss = (bending * ops.bspline_bending(q_l) - sim).sum()
                 loss.backward()
                 opt.step()

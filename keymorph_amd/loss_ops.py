@@ -474,6 +474,21 @@ class LNCCLoss(torch.nn.Module):
         return -ops.local_ncc(pred, target, self.window, self.eps).mean()
 
 
+class MINDLoss(torch.nn.Module):
+    """Mean over the batch of ops.mind_ssc_loss(pred, target, radius, dilation): the squared distance of the MIND-SSC
+    self-similarity context descriptors of (N, 1, D, H, W) float32 pairs; lower is better, differentiable in both inputs.  The
+    local similarity for two modalities: MINDLoss()(align_img(grid, img_m), img_f).  The clamp of the descriptor's variance comes
+    from the pair it is called on (ops.mind_bounds); a driver that wants it fixed while it warps calls ops.mind_ssc_loss with
+    bounds of its own."""
+
+    def __init__(self, radius=1, dilation=2):
+        super().__init__()
+        self.radius, self.dilation = radius, dilation
+
+    def forward(self, pred, target):
+        return ops.mind_ssc_loss(pred, target, self.radius, self.dilation).mean()
+
+
 class BendingLoss(torch.nn.Module):
     """Mean over the batch of ops.bspline_bending(q): the squared second differences of a (N, 3, Cz, Cy, Cx) control lattice along
     its three axes, the smoothness penalty of a free-form deformation (ops.bspline_grid)."""

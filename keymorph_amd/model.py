@@ -367,7 +367,10 @@ class IntensityRegistration(nn.Module):
     (N, 3, Cz, Cy, Cx) in addition, "matrix" is the affine it started from, "grid" = ops.bspline_grid(ctrl, dims, matrix) and
     "mi" = ops.mutual_information of the warped pair.  metric="lncc": the "bspline" entry is fitted by local normalised
     cross-correlation over window^3 cubes (io.register_bspline(metric="lncc")) and has "lncc" (N,) = ops.local_ncc of the warped pair
-    in addition; the matrix stages stay on mutual information.
+    in addition; the matrix stages stay on mutual information.  metric="mind": fitted by the MIND-SSC distance
+    (io.register_bspline(metric="mind", mind_radius, mind_dilation)); the entry has "mind" (N,) = ops.mind_ssc_loss of the warped
+    pair (lower is better) with bounds = ops.mind_bounds of the UNWARPED pair (img_m, img_f), the clamp the driver's finest level
+    used.
     "svf": the diffeomorphism of io.register_svf (the same lattice, schedule, metric and constructor arguments as "bspline", read
     as velocities and exponentiated in svf_steps squarings) on top of the affine answer; its entry is the "bspline" one with
     "grid" = ops.svf_grid(ctrl, dims, svf_steps, matrix) and, in addition, "inverse_grid" = io.svf_grid(ctrl, dims, matrix,
@@ -376,14 +379,15 @@ class IntensityRegistration(nn.Module):
     supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf")
 
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
-                 metric="mi", window=9, svf_steps=6):
+                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2):
         super().__init__()
-        if metric not in ("mi", "lncc"):
-            raise ValueError(f"IntensityRegistration: metric must be 'mi' or 'lncc', got {metric!r}")
+        if metric not in ("mi", "lncc", "mind"):
+            raise ValueError(f"IntensityRegistration: metric must be 'mi', 'lncc' or 'mind', got {metric!r}")
         self.bins, self.iters, self.lr = bins, iters, lr
         self.metric, self.window = metric, window
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
         self.svf_steps = svf_steps
+        self.mind_radius, self.mind_dilation = mind_radius, mind_dilation
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
         from . import ops
@@ -408,7 +412,8 @@ class IntensityRegistration(nn.Module):
                 from .io.svf import register_svf, svf_grid
                 from .utils import align_img
                 common = dict(control_spacing=self.control_spacing, bending=self.bending, bins=self.bins, shrink=shrink,
-                              iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window)
+                              iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,
+                              mind_radius=self.mind_radius, mind_dilation=self.mind_dilation)
                 if svf:
                     ctrl = register_svf(img_f, img_m, mat, steps=self.svf_steps, **common)
                 else:
@@ -424,6 +429,9 @@ class IntensityRegistration(nn.Module):
                         res["inverse_grid"] = svf_grid(ctrl, img_f.shape[2:], mat, self.svf_steps, inverse=True)
                     if self.metric == "lncc":
                         res["lncc"] = ops.local_ncc(warped, img_f, self.window)
+                    if self.metric == "mind":
+                        res["mind"] = ops.mind_ssc_loss(warped, img_f, self.mind_radius, self.mind_dilation,
+                                                        ops.mind_bounds(img_m, img_f, self.mind_radius, self.mind_dilation))
             else:
                 with torch.no_grad():
                     res = {"grid": ops.affine_grid(mat, img_f.shape[2:]), "matrix": mat,

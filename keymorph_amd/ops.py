@@ -1131,6 +1131,85 @@ def local_ncc(a: Tensor, b: Tensor, window: int = 9, eps: float = 1e-5) -> Tenso
 
 
 # --------------------------------------------------------------------------
+# MIND-SSC, the self-similarity context descriptor as a similarity (csrc/mind.hip states the definition)
+# --------------------------------------------------------------------------
+MIND_MAX_RADIUS, MIND_MAX_DILATION = 3, 3
+
+
+class _MIND(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, bounds, radius, dilation):
+        lib = _lib.load()
+        N, _, D, H, W = a.shape
+        ws = workspace(int(lib.kmh_mind_ws_bytes(N, D, H, W, radius, dilation)), a.device, "mind")
+        out = torch.empty((N,), dtype=torch.float32, device=a.device)
+        if _lib.profiler.enabled:  # 8 B read per voxel; the halos come from the caches
+            _lib.profiler.meta = {"bytes": 8.0 * a.numel()}
+        check(lib.kmh_mind_fwd(_p(a), _p(b), _p(bounds), N, D, H, W, radius, dilation, _p(out), _p(ws), _stream()), "kmh_mind_fwd")
+        ctx.save_for_backward(a, b, bounds)
+        ctx.radius, ctx.dilation = radius, dilation
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        a, b, bounds = ctx.saved_tensors
+        gout = _prep(gout)
+        N, _, D, H, W = a.shape
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        ws = workspace(int(lib.kmh_mind_ws_bytes(N, D, H, W, ctx.radius, ctx.dilation)), a.device, "mind")
+        if _lib.profiler.enabled:  # per voxel and gradient: 8 B read, 48 B written and read, 24 B written and read, 4 B written
+            _lib.profiler.meta = {"bytes": 156.0 * ((da is not None) + (db is not None)) * a.numel()}
+        check(lib.kmh_mind_bwd(_p(a), _p(b), _p(bounds), _p(gout), N, D, H, W, ctx.radius, ctx.dilation, _p(da), _p(db), _p(ws),
+                               _stream()), "kmh_mind_bwd")
+        return da, db, None, None, None
+
+
+def _mind_check(who, a, b, radius, dilation):
+    for name, t in (("a", a), ("b", b)):
+        _need_gpu_f32(who, name, t)
+    _need_volume_pair(who, a, b, max_voxels=1 << 31)
+    for name, v, top in (("radius", radius, MIND_MAX_RADIUS), ("dilation", dilation, MIND_MAX_DILATION)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= v <= top:
+            raise ValueError(f"{who}: {name} must be an integer in [1, {top}], got {v!r}")
+    return int(radius), int(dilation)
+
+
+def mind_bounds(a: Tensor, b: Tensor, radius: int = 1, dilation: int = 2) -> Tensor:
+    """(N, 2, 2) float32 on the device, [a or b][lo or hi]: 1e-3 and 1e3 times each sample's mean over the voxels of the
+    descriptor's unclamped variance estimate mean_c m_c -- what mind_ssc_loss takes as `bounds`.  A driver computes them once per
+    pair and keeps them while one volume is warped, as it does with mi_ranges.  No host synchronisation."""
+    radius, dilation = _mind_check("mind_bounds", a, b, radius, dilation)
+    lib = _lib.load()
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    N, _, D, H, W = a.shape
+    ws = workspace(int(lib.kmh_mind_ws_bytes(N, D, H, W, radius, dilation)), a.device, "mind")
+    bounds = torch.empty((N, 2, 2), dtype=torch.float32, device=a.device)
+    check(lib.kmh_mind_bounds(_p(a), _p(b), N, D, H, W, radius, dilation, _p(bounds), _p(ws), _stream()), "kmh_mind_bounds")
+    return bounds
+
+
+def mind_ssc_loss(a: Tensor, b: Tensor, radius: int = 1, dilation: int = 2, bounds: Optional[Tensor] = None) -> Tensor:
+    """MIND-SSC distance (Heinrich et al. 2013) of two (N, 1, D, H, W) float32 volumes on the current GPU, per sample -> (N,),
+    >= 0, LOWER is better, differentiable in both: the mean over the voxels and the 12 channels of the squared difference of
+    the two self-similarity context descriptors (box means over (2 radius + 1)^3 of squared differences between the six
+    neighbours at distance `dilation`, minus their minimum, over their clamped mean, through exp(-.)).  A local metric for two
+    modalities: the descriptor does not change under a -> s a + t.  radius, dilation in 1..3.  bounds (N, 2, 2): the clamp of the
+    variance estimate, constants of the call as mutual information's ranges are; None: mind_bounds(a, b, radius, dilation) of
+    these very inputs.  Two calls give bit-identical values and gradients; a batch equals its samples run one by one."""
+    radius, dilation = _mind_check("mind_ssc_loss", a, b, radius, dilation)
+    if bounds is None:
+        bounds = mind_bounds(a, b, radius, dilation)
+    else:
+        _need_gpu_f32("mind_ssc_loss", "bounds", bounds)
+        if tuple(bounds.shape) != (a.shape[0], 2, 2):
+            raise ValueError(f"mind_ssc_loss: bounds must be ({a.shape[0]}, 2, 2) as mind_bounds returns them, got "
+                             f"{tuple(bounds.shape)}")
+    return _MIND.apply(a.contiguous(), b.contiguous(), bounds.detach().contiguous(), radius, dilation)
+
+
+# --------------------------------------------------------------------------
 # trilinear resize (F.interpolate(mode="trilinear", align_corners=False); keymorph/model.py:576-588)
 # --------------------------------------------------------------------------
 def resize_out_size(n_in: int, scale_factor: float) -> int:
