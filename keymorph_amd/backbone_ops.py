@@ -1359,7 +1359,10 @@ def convnet_lazy_ok(x: Tensor, norm_type: str) -> bool:
 def _in_bwd(g, u, zprev, scale, shift, mr, arg=None, in_place=False):
     """Backward of u = [MaxPool3d(2)](ReLU(InstanceNorm(zprev))) for the gradient g of u -> the gradient of zprev, tagged with
     its range scale.  Both sums of InstanceNorm's backward are taken at u's resolution (kmh_in_bwd_stats: g [zhat > 0] against
-    u); arg: the pooling's winners, u the pooled RAW tensor -- the apply pass then scatters through them."""
+    u); arg: the pooling's winners, u the pooled RAW tensor -- the apply pass then scatters through them.  in_place writes the
+    result over g, which only the unpooled route can do: through the pooling the result is 8 times the size of g."""
+    if in_place and arg is not None:
+        raise ValueError("_in_bwd: the pooled route cannot run in place (g is at the pooled resolution, the result is not)")
     lib = _lib.load()
     N, Dp, Hp, Wp, C = zprev.shape
     ab = torch.empty((N, C, 2), dtype=torch.float64, device=g.device)

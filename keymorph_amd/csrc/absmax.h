@@ -38,7 +38,8 @@ __global__ static void final_kernel(float* __restrict__ out2, float min_abs) {
   const float m = fmaxf(__uint_as_float(reinterpret_cast<unsigned*>(out2)[0]), min_abs);
   range_scale(m, out2);
 }
-// out2[2] = {S, 1/S} for max(max|x|, min_abs); everything on `s`, no host sync
+// out2[2] = {S, 1/S} for m = max(max|x|, min_abs), m S in [2^14, 2^15) (fmaxf drops a NaN; an infinite m gives S = 1);
+// everything on `s`, no host sync
 static inline int launch(const float* x, long long n, float min_abs, float* out2, hipStream_t s) {
   hipError_t e = hipMemsetAsync(out2, 0, 2 * sizeof(float), s);
   if (e != hipSuccess) return (int)e;

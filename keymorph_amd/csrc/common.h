@@ -203,13 +203,13 @@ __device__ __forceinline__ void split8(const float v[8], kmh_bf16x8 out[TERMS]) 
   }
 }
 
-// {S, 1/S} with S the power of two that puts `bound` in (2^14, 2^15]: fp16's largest finite value is 65504, and
+// {S, 1/S} with S the power of two that puts `bound` in [2^14, 2^15): fp16's largest finite value is 65504, and
 // fp16 x fp16 products are exact in the fp32 MFMA accumulator
 __device__ __forceinline__ void range_scale(float bound, float* out2) {
   float S = 1.f;
   if (bound > 0.f && bound < 3.0e38f) {        // finite, non-zero (NaN compares false)
     int e;
-    frexpf(bound, &e);                         // bound = f * 2^e, f in [0.5, 1)  =>  bound <= 2^e
+    frexpf(bound, &e);                         // bound = f * 2^e, f in [0.5, 1)  =>  2^(e-1) <= bound < 2^e
     int k = 15 - e;
     k = k < -100 ? -100 : (k > 100 ? 100 : k);
     S = ldexpf(1.f, k);

@@ -926,8 +926,8 @@ KMH_API int kmh_gn_fwd_coeffs(const double* stats, const float* gamma, const flo
   return KMH_LAUNCH_CHECK();
 }
 
-/* out2[2] = {S, 1/S}: S = 2^k with max(max|x|, min_abs) * S in (2^14, 2^15]  (S = 1 for an all-zero or non-finite
- * tensor).  Range scale of one operand tensor for the fp16-split ("f16x3") convolutions; everything stays on the
+/* out2[2] = {S, 1/S}: S = 2^k with max(max|x|, min_abs) * S in [2^14, 2^15): a power of two lands on 2^14  (S = 1 for an
+ * all-zero tensor or an infinite maximum; a NaN among finite values is ignored, an all-NaN tensor counts as zero).  Range scale of one operand tensor for the fp16-split ("f16x3") convolutions; everything stays on the
  * device and on `stream`. */
 KMH_API int kmh_absmax_scale(const float* x, long long n, float min_abs, float* out2, void* stream) {
   return kmh_absmax::launch(x, n, min_abs, out2, (hipStream_t)stream);

@@ -664,7 +664,7 @@ def test_conv_arithmetic_modes_vs_fp64(cfg):
 
 
 def test_absmax_scale():
-    """kmh_absmax_scale: S = 2^k with max|x| S in (2^14, 2^15], any alignment / length, min_abs floor, zeros."""
+    """kmh_absmax_scale: S = 2^k with max|x| S in [2^14, 2^15), any alignment / length, min_abs floor, zeros."""
     from keymorph_amd import backbone_ops as B
     g = gen(2)
     base = torch.randn(100003, generator=g).to(DEV)
