@@ -1,5 +1,6 @@
-"""What the multi-resolution drivers share (io.estimate_translation, io.register_intensity, io.register_bspline): the levels of
-the trilinear pyramid, and how parameters are carried between them."""
+"""What the multi-resolution drivers share (io.estimate_translation, io.register_intensity, and io.register_bspline and
+io.register_svf through io/_deformable.py's fit_lattice): the levels of the trilinear pyramid, and how parameters are carried
+between them."""
 import torch
 
 MIN_AXIS = 16      # a level with a shorter axis is skipped

@@ -7,10 +7,7 @@ grid's order (x, y, z) and normalised units, on the lattice ops.bspline_lattice_
 displacements on a normalised lattice mean the same thing at every pyramid level, so ONE parameter tensor serves all levels
 without refitting; per level it is stepped in that level's voxels (q_l = ctrl (W_l, H_l, D_l) / 2), so that the learning rate and
 the bending weight are in voxels as register_intensity's are.  `mat` (N, 3, 4) is what ops.affine_grid takes."""
-import torch
-
-from ._pyramid import as_data, levels, scale_axes
-from .intensity import _conjugate, mat_to_voxel, register_intensity, voxel_to_mat
+from ._deformable import fit_lattice, metric_table
 
 
 def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
@@ -47,44 +44,6 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
 
     Nothing inside the loop waits for the GPU."""
     from .. import ops
-    from ..utils import align_img
-    if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
-        raise ValueError(f"register_bspline: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
-                         f"{tuple(moving.shape)}")
-    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
-    if mat is not None and tuple(mat.shape) != (N, 3, 4):
-        raise ValueError(f"register_bspline: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
-    if metric not in ("mi", "lncc", "mind"):
-        raise ValueError(f"register_bspline: metric must be 'mi', 'lncc' or 'mind', got {metric!r}")
-    lattice = ops.bspline_lattice_shape(dims, control_spacing)
-    with torch.inference_mode(False), torch.enable_grad():
-        fixed, moving = as_data(fixed), as_data(moving)
-        if mat is None:
-            mat = register_intensity(fixed, moving, "affine", bins=bins, shrink=shrink)
-        mat = as_data(mat)
-        q = torch.zeros((N, 3, *lattice), dtype=torch.float32, device=fixed.device)      # voxels of the full size, (x, y, z)
-        with torch.no_grad():
-            L, t = mat_to_voxel(mat, dims)
-        for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):            # ratio in (z, y, x), q's channels in (x, y, z)
-            with torch.no_grad():
-                rng = ops.mi_ranges(m_l, f_l, bins) if metric == "mi" else None
-                bounds = ops.mind_bounds(m_l, f_l, mind_radius, mind_dilation) if metric == "mind" else None
-                mat_l = voxel_to_mat(_conjugate(L, ratio), scale_axes(t, ratio, divide=True), ldims)
-                q_l = scale_axes(q, [1.0 / r for r in reversed(ratio)])
-            q_l.requires_grad_(True)
-            to_norm = [2.0 / n for n in reversed(ldims)]
-            opt = torch.optim.Adam([q_l], lr=lr)
-            for _ in range(iters):
-                opt.zero_grad(set_to_none=True)
-                warped = align_img(ops.bspline_grid(scale_axes(q_l, to_norm), ldims, mat_l), m_l)
-                if metric == "mi":
-                    sim = ops.mutual_information(warped, f_l, bins, ranges=rng)
-                elif metric == "lncc":
-                    sim = ops.local_ncc(warped, f_l, window)
-                else:
-                    sim = -ops.mind_ssc_loss(warped, f_l, mind_radius, mind_dilation, bounds)
-                loss = (bending * ops.bspline_bending(q_l) - sim).sum()
-                loss.backward()
-                opt.step()
-            q = scale_axes(q_l.detach(), list(reversed(ratio)))
-        return scale_axes(q, [2.0 / n for n in reversed(dims)])
+    table = metric_table("register_bspline", metric, bins, window, mind_radius, mind_dilation)
+    return fit_lattice("register_bspline", fixed, moving, mat, ops.bspline_grid, table, control_spacing, bending, bins, shrink,
+                       iters, lr)

@@ -13,6 +13,7 @@ TPS system is solved on the GPU once per direction instead of 3x per call on the
 """
 from __future__ import annotations
 
+import functools
 import os
 import re
 import time
@@ -381,8 +382,8 @@ class IntensityRegistration(nn.Module):
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
                  metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2):
         super().__init__()
-        if metric not in ("mi", "lncc", "mind"):
-            raise ValueError(f"IntensityRegistration: metric must be 'mi', 'lncc' or 'mind', got {metric!r}")
+        from .io._deformable import metric_table
+        metric_table("IntensityRegistration", metric)                          # refuses an unknown name
         self.bins, self.iters, self.lr = bins, iters, lr
         self.metric, self.window = metric, window
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
@@ -391,7 +392,11 @@ class IntensityRegistration(nn.Module):
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
         from . import ops
+        from .io._deformable import metric_table
+        from .io.bspline import register_bspline
         from .io.intensity import register_intensity
+        from .io.svf import register_svf, svf_grid
+        from .utils import align_img
         if not isinstance(transform_type, (list, tuple)):
             transform_type = [transform_type]
         assert all(s in self.supported_transform_type for s in transform_type), "Invalid transform_type"
@@ -400,38 +405,32 @@ class IntensityRegistration(nn.Module):
         shrink = (4, 2, 1)
         if num_resolutions_for_itkelastix is not None:
             shrink = tuple(2 ** k for k in range(int(num_resolutions_for_itkelastix) - 1, -1, -1))
+        k = self.svf_steps
+        # the deformable stages, a lattice on top of the affine answer: (driver, grid(ctrl, dims, mat), inverse grid likewise or None)
+        lattices = {"bspline": (register_bspline, ops.bspline_grid, None),
+                    "svf": (functools.partial(register_svf, steps=k), lambda ctrl, dims, m: ops.svf_grid(ctrl, dims, k, m),
+                            lambda ctrl, dims, m: svf_grid(ctrl, dims, m, k, inverse=True))}
+        reported = metric_table("IntensityRegistration", self.metric, self.bins, self.window, self.mind_radius,
+                                self.mind_dilation).reported
         result_dict = {}
         for align_type_str in transform_type:
             start_time = time.time()
-            svf = align_type_str == "svf"
-            bspline = svf or align_type_str == "bspline"                       # the deformable stages: a lattice on top of the affine answer
-            mat = register_intensity(img_f, img_m, "affine" if bspline else align_type_str, bins=self.bins, shrink=shrink,
+            deformable = lattices.get(align_type_str)
+            mat = register_intensity(img_f, img_m, "affine" if deformable else align_type_str, bins=self.bins, shrink=shrink,
                                      iters=self.iters, lr=self.lr)
-            if bspline:
-                from .io.bspline import register_bspline
-                from .io.svf import register_svf, svf_grid
-                from .utils import align_img
-                common = dict(control_spacing=self.control_spacing, bending=self.bending, bins=self.bins, shrink=shrink,
-                              iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,
+            if deformable:
+                driver, grid_of, inverse_of = deformable
+                ctrl = driver(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending, bins=self.bins,
+                              shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,
                               mind_radius=self.mind_radius, mind_dilation=self.mind_dilation)
-                if svf:
-                    ctrl = register_svf(img_f, img_m, mat, steps=self.svf_steps, **common)
-                else:
-                    ctrl = register_bspline(img_f, img_m, mat, **common)
                 with torch.no_grad():
-                    if svf:
-                        grid = ops.svf_grid(ctrl, img_f.shape[2:], self.svf_steps, mat)
-                    else:
-                        grid = ops.bspline_grid(ctrl, img_f.shape[2:], mat)
+                    grid = grid_of(ctrl, img_f.shape[2:], mat)
                     warped = align_img(grid, img_m)
                     res = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": ops.mutual_information(warped, img_f, self.bins)}
-                    if svf:
-                        res["inverse_grid"] = svf_grid(ctrl, img_f.shape[2:], mat, self.svf_steps, inverse=True)
-                    if self.metric == "lncc":
-                        res["lncc"] = ops.local_ncc(warped, img_f, self.window)
-                    if self.metric == "mind":
-                        res["mind"] = ops.mind_ssc_loss(warped, img_f, self.mind_radius, self.mind_dilation,
-                                                        ops.mind_bounds(img_m, img_f, self.mind_radius, self.mind_dilation))
+                    if inverse_of:
+                        res["inverse_grid"] = inverse_of(ctrl, img_f.shape[2:], mat)
+                    if reported:
+                        res[self.metric] = reported(warped, img_f, img_m)
             else:
                 with torch.no_grad():
                     res = {"grid": ops.affine_grid(mat, img_f.shape[2:]), "matrix": mat,

@@ -140,10 +140,10 @@ def mi_similarity(warped, f_l, level):
 
 
 def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-             dtype=F64, similarity=mi_similarity):
+             dtype=F64, similarity=mi_similarity, grid_of=bspline_grid):
     """keymorph_amd.io.register_bspline with a given matrix, on the CPU in `dtype`: the same levels, parameters, loss and Adam.
     similarity(warped, f_l, level) -> (N,), higher is better; level = {"moving": m_l, "bins": bins}, a dict of the level's own
-    that the callable may keep things in."""
+    that the callable may keep things in.  grid_of(ctrl_l, ldims, mat_l) -> grid: the transform model (svf_ref.register's differs)."""
     fixed, moving, mat = fixed.detach().to(dtype), moving.detach().to(dtype), mat.detach().to(F64)
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     n = torch.tensor([float(d) for d in dims], dtype=F64)
@@ -168,7 +168,7 @@ def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, bins=32
         opt = torch.optim.Adam([q_l], lr=lr)
         for _ in range(iters):
             opt.zero_grad(set_to_none=True)
-            warped = F.grid_sample(m_l, bspline_grid(q_l * to_norm, ldims, mat_l), mode="bilinear", padding_mode="border",
+            warped = F.grid_sample(m_l, grid_of(q_l * to_norm, ldims, mat_l), mode="bilinear", padding_mode="border",
                                    align_corners=False)
             (bending_weight * bending(q_l) - similarity(warped, f_l, level)).sum().backward()
             opt.step()

@@ -158,36 +158,8 @@ def register(fixed, moving, mat, control_spacing=8, bending_weight=0.05, steps=6
              dtype=F64, similarity=R.mi_similarity):
     """keymorph_amd.io.register_svf with a given matrix, on the CPU in `dtype`: bspline_ref.register with svf_grid in place of
     bspline_grid."""
-    fixed, moving, mat = fixed.detach().to(dtype), moving.detach().to(dtype), mat.detach().to(F64)
-    N, dims = fixed.shape[0], tuple(fixed.shape[2:])
-    n = torch.tensor([float(d) for d in dims], dtype=F64)
-    L = mat[:, :, :3] * n[None, :, None] / (n - 1)[None, None, :]
-    t = mat[:, :, 3] * n[None, :] / 2
-    q = torch.zeros((N, 3, *R.lattice_shape(dims, control_spacing)), dtype=dtype)
-    for sh in shrink:
-        ldims = tuple(d // int(sh) for d in dims)
-        if min(ldims) < 16:
-            continue
-        if ldims == dims:
-            f_l, m_l = fixed, moving
-        else:
-            f_l = F.interpolate(fixed, size=ldims, mode="trilinear", align_corners=False)
-            m_l = F.interpolate(moving, size=ldims, mode="trilinear", align_corners=False)
-        level = {"moving": m_l, "bins": bins}
-        ratio = torch.tensor([d / l for d, l in zip(dims, ldims)], dtype=F64)
-        mat_l = W.voxel_to_mat(L * ratio[None, None, :] / ratio[None, :, None], t / ratio[None, :], ldims).to(dtype)
-        rx = ratio.flip(0).to(dtype)[None, :, None, None, None]
-        to_norm = torch.tensor([2.0 / ldims[2], 2.0 / ldims[1], 2.0 / ldims[0]], dtype=dtype)[None, :, None, None, None]
-        q_l = (q / rx).requires_grad_(True)
-        opt = torch.optim.Adam([q_l], lr=lr)
-        for _ in range(iters):
-            opt.zero_grad(set_to_none=True)
-            warped = F.grid_sample(m_l, svf_grid(q_l * to_norm, ldims, steps, mat_l), mode="bilinear", padding_mode="border",
-                                   align_corners=False)
-            (bending_weight * R.bending(q_l) - similarity(warped, f_l, level)).sum().backward()
-            opt.step()
-        q = q_l.detach() * rx
-    return q * torch.tensor([2.0 / dims[2], 2.0 / dims[1], 2.0 / dims[0]], dtype=dtype)[None, :, None, None, None]
+    return R.register(fixed, moving, mat, control_spacing, bending_weight, bins, shrink, iters, lr, dtype, similarity,
+                      grid_of=lambda ctrl_l, ldims, mat_l: svf_grid(ctrl_l, ldims, steps, mat_l))
 
 
 @functools.lru_cache(maxsize=None)

@@ -338,31 +338,6 @@ def test_apply_bspline_is_the_grid_and_the_sampler(recovery):
     assert torch.equal(apply_bspline(m, ctrl), align_img(ops.bspline_grid(ctrl, m.shape[2:]), m))
 
 
-def test_register_bspline_batch_equals_single_runs(recovery):
-    from keymorph_amd.io import register_bspline
-    fixed, moving, mat, ctrl0 = recovery
-    fixed2, moving2 = R.recovery_pair(seed=4)
-    f, m = torch.cat([fixed, fixed2]).to(DEV), torch.cat([moving, moving2]).to(DEV)
-    both = register_bspline(f, m, mat=mat.expand(2, 3, 4).contiguous())
-    single = register_bspline(fixed2.to(DEV), moving2.to(DEV), mat=mat)
-    assert torch.equal(both[0], ctrl0[0]) and torch.equal(both[1], single[0])
-
-
-def test_register_bspline_does_not_wait_for_the_gpu(recovery):
-    """One full-resolution level under torch's synchronisation check, after a first call that allocates."""
-    from keymorph_amd.io import register_bspline
-    fixed, moving, mat, _ = recovery
-    f, m = fixed.to(DEV), moving.to(DEV)
-    first = register_bspline(f, m, mat=mat, shrink=(1,), iters=3)
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        again = register_bspline(f, m, mat=mat, shrink=(1,), iters=3)
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-    assert torch.equal(first, again)
-
-
 def test_intensity_registration_bspline_entry(recovery):
     from keymorph_amd import ops
     from keymorph_amd.model import IntensityRegistration

@@ -307,40 +307,6 @@ def test_register_bspline_mind_recovers_under_inverted_contrast_and_bias(inverte
     assert loss_ops.jdlessthan0(fields.to_displacement(ops.bspline_grid(ctrl, dims, mat))) == 0
 
 
-def test_register_bspline_mind_batch_equals_single_runs(inverted):
-    from keymorph_amd.io import register_bspline
-    f, m, mat, ctrl0 = inverted
-    f2, m2 = (t.to(DEV) for t in B.recovery_pair(seed=4))
-    both = register_bspline(torch.cat([f, f2]), torch.cat([m, m2]), mat=mat.expand(2, 3, 4).contiguous(), metric="mind")
-    single = register_bspline(f2, m2, mat=mat, metric="mind")
-    assert torch.equal(both[0], ctrl0[0]) and torch.equal(both[1], single[0])
-
-
-def test_register_bspline_mind_does_not_wait_for_the_gpu(inverted):
-    """One full-resolution level under torch's synchronisation check, after a first call that allocates."""
-    from keymorph_amd.io import register_bspline
-    f, m, mat, _ = inverted
-    first = register_bspline(f, m, mat=mat, shrink=(1,), iters=3, metric="mind")
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        again = register_bspline(f, m, mat=mat, shrink=(1,), iters=3, metric="mind")
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-    assert torch.equal(first, again)
-
-
-def test_metric_mi_is_the_call_without_the_argument(inverted):
-    from keymorph_amd.io import register_bspline, register_svf
-    f, m, mat, _ = inverted
-    assert torch.equal(register_bspline(f, m, mat=mat, iters=5, metric="mi"), register_bspline(f, m, mat=mat, iters=5))
-    for fn in (register_bspline, register_svf):
-        with pytest.raises(ValueError):
-            fn(f, m, mat=mat, metric="ncc")
-        with pytest.raises(ValueError):
-            fn(f, m, mat=mat, metric="mind", mind_radius=4)
-
-
 def test_register_svf_mind_runs_and_repeats(inverted):
     from keymorph_amd import ops
     from keymorph_amd.io import apply_svf, register_svf

@@ -394,34 +394,6 @@ def test_apply_svf_and_its_inverse(recovery):
         assert after > before + 0.2
 
 
-def test_register_svf_batch_equals_single_runs(recovery):
-    from keymorph_amd.io import register_svf
-    fixed, moving, mat, ctrl0 = recovery
-    fixed2, moving2 = S.recovery_pair(R.AMPLITUDE, 4)
-    f, m = torch.cat([fixed, fixed2]).to(DEV), torch.cat([moving, moving2]).to(DEV)
-    both = register_svf(f, m, mat=mat.expand(2, 3, 4).contiguous())
-    single = register_svf(fixed2.to(DEV), moving2.to(DEV), mat=mat)
-    assert torch.equal(both[0], ctrl0[0]) and torch.equal(both[1], single[0])
-
-
-def test_register_svf_does_not_wait_for_the_gpu(recovery):
-    """One full-resolution level under torch's synchronisation check, after a first call that allocates."""
-    from keymorph_amd.io import register_svf
-    fixed, moving, mat, _ = recovery
-    f, m = fixed.to(DEV), moving.to(DEV)
-    first = register_svf(f, m, mat=mat, shrink=(1,), iters=3)
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        again = register_svf(f, m, mat=mat, shrink=(1,), iters=3)
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-    assert torch.equal(first, again)
-    assert torch.isfinite(register_svf(f, m, mat=mat, shrink=(1,), iters=2, metric="lncc")).all()
-    with pytest.raises(ValueError):
-        register_svf(f, m, mat=mat, steps=13)
-
-
 def test_intensity_registration_svf_entry(recovery):
     from keymorph_amd import ops
     from keymorph_amd.io import svf_grid
