@@ -148,6 +148,15 @@ int kmh_mi_range(const float* a, const float* b, int N, long long V, int bins, i
                  int has_range_b, float lo_b, float hi_b, void* ws, float* rng, void* stream);
 /* kmh_mi_hist with the ranges given on the device: rng (N, 4) in, as kmh_mi_range wrote it; kmh_mi_final and kmh_mi_bwd follow. */
 int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws, void* stream);
+/* The same over the COUNTED voxels only: mask (N, V) bytes, non-zero = counted, NULL = every voxel.  cnt: N 64-bit integers on
+ * the device, the number of counted voxels per sample, written by the histogram pass and read by the other two (the host never
+ * reads it): p = h / cnt[n], gradients scaled by 1 / cnt[n], 0 at a voxel that is not counted; cnt[n] = 0: MI = 0, G = 0. */
+int kmh_mi_hist_masked(const float* a, const float* b, const unsigned char* mask, const float* rng, int N, long long V, int bins,
+                       void* ws, long long* cnt, void* stream);
+int kmh_mi_final_masked(const void* ws, const float* rng, const long long* cnt, int N, int bins, float* mi, float* G,
+                        void* stream);
+int kmh_mi_bwd_masked(const float* a, const float* b, const unsigned char* mask, const float* rng, const float* G,
+                      const float* gout, const long long* cnt, int N, long long V, int bins, float* da, float* db, void* stream);
 
 /* ---- mutual information of a fixed volume and a moving volume warped by a matrix, fused (csrc/warp_mi.hip) ---- */
 /* By definition MI(grid_sample3d(moving, affine_grid(mat)), fixed) with the ranges rng = kmh_mi_range(moving, fixed): moving,
@@ -159,6 +168,16 @@ int kmh_warp_mi_hist(const float* moving, const float* fixed, const float* mat, 
                      int bins, void* ws, void* stream);
 int kmh_warp_mi_bwd(const float* moving, const float* fixed, const float* mat, const float* rng, const float* G,
                     const float* gout, int N, int D, int H, int W, int bins, void* ws, float* dmat, void* stream);
+/* The same over the counted voxels only.  Fixed-lattice voxel v with sampling coordinate g(v) is counted iff fixed_mask[v] != 0,
+ * moving_mask != 0 at the nearest sampler's voxel for g(v), and (inside != 0) every |g(v)_k| <= 1; masks (N, D, H, W) bytes, either
+ * may be NULL.  cnt as in kmh_mi_hist_masked; kmh_mi_final_masked follows the histogram pass.  Same workspace. */
+int kmh_warp_mi_hist_masked(const float* moving, const float* fixed, const unsigned char* fixed_mask,
+                            const unsigned char* moving_mask, const float* mat, const float* rng, int N, int D, int H, int W,
+                            int bins, int inside, void* ws, long long* cnt, void* stream);
+int kmh_warp_mi_bwd_masked(const float* moving, const float* fixed, const unsigned char* fixed_mask,
+                           const unsigned char* moving_mask, const float* mat, const float* rng, const float* G,
+                           const float* gout, const long long* cnt, int N, int D, int H, int W, int bins, int inside, void* ws,
+                           float* dmat, void* stream);
 
 /* ---- a9: AffineTransform.get_flow_field, keymorph/transformations.py:37-79 and
  *      uniform_norm_grid keymorph/utils.py:387-398.  mat (N,3,4) = inverse_transform_matrix[:, :3, :]

@@ -71,6 +71,11 @@ PROTOS = {
     "kmh_mi_bwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
     "kmh_mi_range": (_i, [_f, _f, _i, _ll, _i, _i, C.c_float, C.c_float, _i, C.c_float, C.c_float, _f, _f, _f]),
     "kmh_mi_hist_ranges": (_i, [_f, _f, _f, _i, _ll, _i, _f, _f]),
+    "kmh_mi_hist_masked": (_i, [_f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
+    "kmh_mi_final_masked": (_i, [_f, _f, _f, _i, _i, _f, _f, _f]),
+    "kmh_mi_bwd_masked": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _ll, _i, _f, _f, _f]),
+    "kmh_warp_mi_hist_masked": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "kmh_warp_mi_bwd_masked": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
     "kmh_warp_mi_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_warp_mi_hist": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
     "kmh_warp_mi_bwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),

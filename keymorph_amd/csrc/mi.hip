@@ -27,6 +27,8 @@
 // mi_final_kernel     one workgroup per sample: marginals as exact integer sums, p, ln and the sum in fp64 in a fixed order;
 //                     writes MI_n and G.  A sample with s_a = 0 or s_b = 0 (a constant image) gets MI = 0 and G = 0 exactly.
 // mi_bwd_kernel       one lane per voxel: recomputes the taps, gathers the 16 entries of G from LDS, writes da and / or db.
+// mi_*_masked_kernel  the histogram, finalise and backward kernels over the voxels a byte mask counts, with their number M_n in
+//                     V's place (stated above them, behind the unmasked kernels, which they leave as they are).
 #include "common.h"
 #include "mi_taps.h"      // the window (taps), the fixed-point format's constants and the workspace's layout: shared with warp_mi.hip
 
@@ -250,6 +252,166 @@ __global__ __launch_bounds__(TPB) void mi_bwd_kernel(const float* __restrict__ a
   }
 }
 
+// ---- the masked variants: kernels of their own, so that the ones above keep their machine code (mi_taps.h) -------------------
+// A voxel is COUNTED iff mask[v] != 0 (mask (N, V) bytes; NULL: every voxel).  Counted voxels add their products as above,
+// M_n = their number replaces V in p = h / M_n and in the gradient's 1 / V, and a voxel that is not counted gets gradient 0.
+// M_n is a 64-bit integer on the device (cnt[n], zeroed by the launcher): never read by the host.
+
+// mi_hist_kernel's partition, tables and flush.  The interval's mask bytes are loaded first; a lane that is not counted reads
+// voxel 0 (one line for the whole wave) instead of its own, a step without a counted lane skips its taps and its adds, and a
+// workgroup whose interval counted nothing skips the flush (its tables are still zero).  Each wave sums its ballots; the
+// workgroup adds the interval's count with one integer atomic.
+__global__ __launch_bounds__(TPB) void mi_hist_masked_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                             const unsigned char* __restrict__ mask,
+                                                             const float* __restrict__ rng, long long V, long long R,
+                                                             long long per, int B, unsigned long long* __restrict__ hist,
+                                                             unsigned long long* __restrict__ cnt) {
+  extern __shared__ unsigned tab[];
+  __shared__ unsigned wcnt[kWaves];
+  const int n = blockIdx.y, BB = B * B, lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  const long long beg = per * blockIdx.x;
+  long long end = beg + per;
+  if (end > R) end = R;
+  a += (long long)n * V;
+  b += (long long)n * V;
+  if (mask) mask += (long long)n * V;
+  hist += (long long)n * BB;
+  for (int e = threadIdx.x; e < kWaves * BB; e += TPB) tab[e] = 0u;
+  __syncthreads();
+  unsigned* mine = tab + wid * BB;
+  for (long long c = beg; c < end; c += kSteps * kWaves) {
+    unsigned live = 0u;
+#pragma unroll
+    for (int it = 0; it < kSteps; ++it) {
+      const long long j = c + wid * kSteps + it, v = j * kWave + lane;
+      const bool in = j < end && v < V;
+      const bool counted = in && (mask ? mask[in ? v : 0] != 0 : true);
+      live |= (counted ? 1u : 0u) << it;
+    }
+    float xa[kSteps], xb[kSteps];
+#pragma unroll
+    for (int it = 0; it < kSteps; ++it) {
+      const long long v = (c + wid * kSteps + it) * kWave + lane;
+      const bool valid = (live >> it) & 1u;
+      xa[it] = a[valid ? v : 0];
+      xb[it] = b[valid ? v : 0];
+    }
+    unsigned counted_here = 0u;                                       // wave-uniform
+#pragma unroll
+    for (int it = 0; it < kSteps; ++it) {
+      const bool valid = (live >> it) & 1u;
+      const unsigned long long who = __ballot(valid);
+      if (!who) continue;                                             // wave-uniform
+      counted_here += (unsigned)__popcll(who);
+      hist_add(valid, xa[it], xb[it], lo_a, s_a, lo_b, s_b, B, lane, mine);
+    }
+    if (lane == 0) wcnt[wid] = counted_here;
+    __syncthreads();
+    unsigned total = 0u;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) total += wcnt[w];
+    if (total) {                                                      // workgroup-uniform
+      for (int e = threadIdx.x; e < BB; e += TPB) {
+        unsigned long long sum = 0ull;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+          sum += tab[w * BB + e];
+          tab[w * BB + e] = 0u;
+        }
+        if (sum) atomicAdd(hist + e, sum);
+      }
+      if (threadIdx.x == 0) atomicAdd(cnt + n, (unsigned long long)total);
+    }
+    __syncthreads();
+  }
+}
+
+// mi_final_kernel with V = cnt[n]; a sample that counted nothing gets MI = 0 and G = 0 exactly, like a constant image
+__global__ __launch_bounds__(TPB) void mi_final_masked_kernel(const unsigned long long* __restrict__ hist,
+                                                              const float* __restrict__ rng,
+                                                              const unsigned long long* __restrict__ cnt, int B,
+                                                              float* __restrict__ mi, float* __restrict__ G) {
+  extern __shared__ double fin[];
+  __shared__ double scratch[kWaves];
+  const int n = blockIdx.x, BB = B * B;
+  double* pa = fin + BB;
+  double* pb = pa + B;
+  hist += (long long)n * BB;
+  G += (long long)n * BB;
+  const unsigned long long M = cnt[n];
+  if (M == 0ull || rng[n * 4 + 1] == 0.f || rng[n * 4 + 3] == 0.f) {
+    for (int e = threadIdx.x; e < BB; e += TPB) G[e] = 0.f;
+    if (threadIdx.x == 0) mi[n] = 0.f;
+    return;
+  }
+  const double unit = 1.0 / ((double)(1 << kFrac) * (double)(long long)M);
+  for (int e = threadIdx.x; e < BB; e += TPB) fin[e] = (double)hist[e] * unit;
+  if (threadIdx.x < 2 * B) {                                          // marginals: integer sums, exact in any order
+    const int k = threadIdx.x % B, col = threadIdx.x / B;
+    unsigned long long s = 0ull;
+    for (int j = 0; j < B; ++j) s += col ? hist[j * B + k] : hist[k * B + j];
+    (col ? pb : pa)[k] = (double)s * unit;
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int e = threadIdx.x; e < BB; e += TPB) {
+    const double p = fin[e];
+    double g = 0.0;
+    if (p > 0.0) {
+      g = log(p / (pa[e / B] * pb[e % B]));
+      acc += p * g;
+    }
+    G[e] = (float)g;
+  }
+  acc = block_sum(acc, scratch);
+  if (threadIdx.x == 0) mi[n] = (float)acc;
+}
+
+// mi_bwd_kernel with 1 / M_n for 1 / V; a voxel that is not counted gets 0
+__global__ __launch_bounds__(TPB) void mi_bwd_masked_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                            const unsigned char* __restrict__ mask,
+                                                            const float* __restrict__ rng, const float* __restrict__ G,
+                                                            const float* __restrict__ gout,
+                                                            const unsigned long long* __restrict__ cnt, long long V, int B,
+                                                            float* __restrict__ da, float* __restrict__ db) {
+  extern __shared__ float g[];
+  const int n = blockIdx.y, BB = B * B;
+  for (int e = threadIdx.x; e < BB; e += TPB) g[e] = G[(long long)n * BB + e];
+  __syncthreads();
+  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  const long long M = (long long)cnt[n];
+  const float go = M ? gout[n] / (float)M : 0.f, ca = go * s_a, cb = go * s_b;
+  const long long off = (long long)n * V;
+#pragma unroll
+  for (int it = 0; it < kBwdVpt; ++it) {
+    const long long v = ((long long)blockIdx.x * kBwdVpt + it) * TPB + threadIdx.x;
+    if (v >= V) return;
+    if (mask && mask[off + v] == 0) {
+      if (da) da[off + v] = 0.f;
+      if (db) db[off + v] = 0.f;
+      continue;
+    }
+    const Taps ta = taps<true>(a[off + v], lo_a, s_a, B), tb = taps<true>(b[off + v], lo_b, s_b, B);
+    const float* row = g + ta.k0 * B + tb.k0;
+    float ga = 0.f, gb = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float rw = 0.f, rd = 0.f;                                      // sum_j G_ij w_b[j], sum_j G_ij w_b'[j]
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gij = row[i * B + j];
+        rw = fmaf(gij, tb.w[j], rw);
+        rd = fmaf(gij, tb.d[j], rd);
+      }
+      ga = fmaf(ta.d[i], rw, ga);
+      gb = fmaf(ta.w[i], rd, gb);
+    }
+    if (da) da[off + v] = ca * ga;
+    if (db) db[off + v] = cb * gb;
+  }
+}
+
 bool mi_args_ok(const void* a, const void* b, int N, long long V, int B) {
   return a && b && N >= 1 && N <= 65535 && V >= 1 && V <= (1ll << 40) && B >= kMinBins && B <= kMaxBins;
 }
@@ -339,5 +501,42 @@ KMH_API int kmh_mi_bwd(const float* a, const float* b, const float* rng, const f
   if (nb > 0x7fffffffll) return -22;
   mi_bwd_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)bins * bins * sizeof(float), (hipStream_t)stream>>>(
       a, b, rng, G, gout, V, bins, da, db);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* kmh_mi_hist_ranges over the counted voxels only: mask (N, V) bytes, non-zero = counted, NULL = every voxel.  cnt: N 64-bit
+ * integers out, the number of counted voxels per sample (cleared here), which kmh_mi_final_masked and kmh_mi_bwd_masked read. */
+KMH_API int kmh_mi_hist_masked(const float* a, const float* b, const unsigned char* mask, const float* rng, int N, long long V,
+                               int bins, void* ws, long long* cnt, void* stream) {
+  if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng || !cnt) return -22;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
+  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)N * sizeof(long long), s);
+  if (e != hipSuccess) return (int)e;
+  const HistSteps p = hist_steps(V, kWaves);
+  mi_hist_masked_kernel<<<dim3((unsigned)p.nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
+      a, b, mask, rng, V, p.R, p.per, bins, ws_table(ws, N), (unsigned long long*)cnt);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* kmh_mi_final with p = h / cnt[n]: for the table of kmh_mi_hist_masked or kmh_warp_mi_hist_masked.  cnt[n] = 0: MI = 0, G = 0. */
+KMH_API int kmh_mi_final_masked(const void* ws, const float* rng, const long long* cnt, int N, int bins, float* mi, float* G,
+                                void* stream) {
+  if (!mi_args_ok(ws, rng, N, 1, bins) || !cnt || !mi || !G) return -22;
+  mi_final_masked_kernel<<<N, TPB, (size_t)(bins * bins + 2 * bins) * sizeof(double), (hipStream_t)stream>>>(
+      ws_table(ws, N), rng, (const unsigned long long*)cnt, bins, mi, G);
+  return KMH_LAUNCH_CHECK();
+}
+
+/* kmh_mi_bwd over the counted voxels, scaled by 1 / cnt[n]; a voxel that is not counted gets 0 in da and db. */
+KMH_API int kmh_mi_bwd_masked(const float* a, const float* b, const unsigned char* mask, const float* rng, const float* G,
+                              const float* gout, const long long* cnt, int N, long long V, int bins, float* da, float* db,
+                              void* stream) {
+  if (!mi_args_ok(a, b, N, V, bins) || !rng || !G || !gout || !cnt) return -22;
+  if (!da && !db) return 0;
+  const long long nb = (V + TPB * kBwdVpt - 1) / (TPB * kBwdVpt);
+  if (nb > 0x7fffffffll) return -22;
+  mi_bwd_masked_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)bins * bins * sizeof(float), (hipStream_t)stream>>>(
+      a, b, mask, rng, G, gout, (const unsigned long long*)cnt, V, bins, da, db);
   return KMH_LAUNCH_CHECK();
 }

@@ -9,7 +9,9 @@
 //   128^3  min/max pass 0.1611 0.1635 0.1622 0.1633   ranges given 0.1522 0.1535 0.1520 0.1526   masked 0.1476 0.1475 0.1478 0.1482
 //   256^3  min/max pass 0.6309 0.6313 0.6304 0.6322   ranges given 0.5828 0.5842 0.5822 0.5828   masked 0.4340 0.4357 0.4340 0.4313
 // The call's mean exceeds the inline mean by more than the two inline runs differ in four of the six.  warp_mi_hist_kernel's
-// machine code is the same with hist_add here or in its own unit.
+// machine code is the same with hist_add here or in its own unit.  For the same reason the masked variants (mi_hist_masked_kernel,
+// warp_mi_hist_masked_kernel: `valid` = in range AND counted) are kernels of their own that call hist_add, not a flag of these:
+// tools/kernel_fingerprint.py shows the unmasked kernels' machine code unchanged beside them.
 #pragma once
 #include "common.h"
 

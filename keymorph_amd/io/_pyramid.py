@@ -31,6 +31,22 @@ def levels(fixed, moving, shrink):
         yield ldims, f_l, m_l, [n / l for n, l in zip(dims, ldims)]
 
 
+def mask_levels(who, name, mask, like, shrink):
+    """The pyramid of a mask of `like`'s shape (uint8 or bool on the GPU, non-zero = counted; else ValueError), one uint8 tensor per
+    level of levels(like, ., shrink): the mask itself at the full size, resize_trilinear(mask.float(), ldims) >= 0.5 below.  None
+    for every level when mask is None.  Built once, under no_grad, without waiting for the GPU."""
+    from .. import ops
+    from ..utils import resize_trilinear
+    dims = tuple(like.shape[2:])
+    sizes = level_dims(dims, shrink)
+    if mask is None:
+        return [None] * len(sizes)
+    mask = ops._need_mask(who, name, mask, like)
+    with torch.no_grad():
+        soft = mask.float() if any(ldims != dims for ldims in sizes) else None
+        return [mask if ldims == dims else (resize_trilinear(soft, size=ldims) >= 0.5).to(torch.uint8) for ldims in sizes]
+
+
 def scale_axes(t, factors, divide=False):
     """t (N, 3, ...) with channel k times factors[k] (divide: over factors[k]).  From Python scalars only: a tensor made from a
     host list would be a host-to-device copy, which waits for the stream, on every step of a driver's loop."""

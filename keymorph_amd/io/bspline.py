@@ -18,7 +18,8 @@ def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
 
 
 def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-                     metric="mi", window=9, mind_radius=1, mind_dilation=2):
+                     metric="mi", window=9, mind_radius=1, mind_dilation=2, fixed_mask=None, moving_mask=None,
+                     inside=False):
     """ctrl (N, 3, Cz, Cy, Cx) on the lattice ops.bspline_lattice_shape(dims, control_spacing) such that
     apply_bspline(moving, ctrl, mat) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual
     information.  mat (N, 3, 4): the affine part, data; None: register_intensity(fixed, moving, "affine", bins=bins,
@@ -42,8 +43,13 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     clamp of the descriptor's variance, is ops.mind_bounds(m_l, f_l, ...) of the level's unwarped pair, once per level, where the
     mutual information has its ranges.
 
+    fixed_mask, moving_mask, inside: which voxels the mutual information counts, as io.register_intensity takes them (the default
+    affine start gets them too).  Per step the counted set is fixed_mask & (align_img(grid, moving_mask, "nearest") != 0) &
+    (|grid| <= 1), of the step's own grid, and the similarity is ops.mutual_information(..., mask=that set).  They work with
+    metric="mi" only: with "lncc" or "mind" any of them raises ValueError (masked local metrics do not exist here).
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     table = metric_table("register_bspline", metric, bins, window, mind_radius, mind_dilation)
     return fit_lattice("register_bspline", fixed, moving, mat, ops.bspline_grid, table, control_spacing, bending, bins, shrink,
-                       iters, lr)
+                       iters, lr, fixed_mask, moving_mask, inside, metric)

@@ -8,7 +8,7 @@ the volume's centre, L (N, 3, 3), t (N, 3) voxels, rows and columns in (z, y, x)
 takes.  translate(x, t) of io.centering is the case L = I."""
 import torch
 
-from ._pyramid import as_data, levels, scale_axes
+from ._pyramid import as_data, levels, mask_levels, scale_axes
 
 
 def _dims3(dims):
@@ -83,7 +83,8 @@ def apply_mat(x, mat, mode="bilinear"):
 _STAGES = {"translation": ("translation",), "rigid": ("translation", "rigid"), "affine": ("translation", "rigid", "affine")}
 
 
-def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 1), iters=30, lr=0.25, spacing=(1.0, 1.0, 1.0)):
+def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 1), iters=30, lr=0.25, spacing=(1.0, 1.0, 1.0),
+                       fixed_mask=None, moving_mask=None, inside=False):
     """mat (N, 3, 4), the argument ops.affine_grid takes, such that apply_mat(moving, mat) lines up with fixed (both
     (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual information; transform = "translation" | "rigid" | "affine",
     spacing = voxel size in (z, y, x) order.
@@ -99,6 +100,13 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
     max_k spacing_k (n_k - 1) / 2 in units of its smallest spacing: a unit step of such a parameter moves the farthest face of
     the volume by about one voxel, like a unit step of the shift, so the one learning rate `lr` (voxels per step) serves all.
 
+    fixed_mask, moving_mask ((N, 1, D, H, W) uint8 or bool on the GPU, non-zero = counted), inside: which voxels the mutual
+    information counts, as ops.warp_mutual_information defines it (elastix' FixedMask / MovingMask, ANTs' -x; inside=True drops
+    samples that the transform sends outside the moving volume, as ITK does).  The centroid start is that of fixed * fixed_mask
+    and moving * moving_mask.  A mask's pyramid is the mask itself at the full size and resize_trilinear(mask.float()) >= 0.5
+    below, built once per level; the intensity ranges stay those of the whole level volumes.  A sample whose level mask is empty
+    does not move at that level.
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     from .centering import _centroid
@@ -113,19 +121,28 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
     dims = tuple(fixed.shape[2:])
     with torch.inference_mode(False), torch.enable_grad():
         fixed, moving = as_data(fixed), as_data(moving)
+        fmasks = mask_levels("register_intensity", "fixed_mask", fixed_mask, fixed, shrink)
+        mmasks = mask_levels("register_intensity", "moving_mask", moving_mask, moving, shrink)
         pyramid = []
         with torch.no_grad():
-            t = _centroid(moving) - _centroid(fixed)
-            for ldims, f_l, m_l, ratio in levels(fixed, moving, shrink):
+            if fixed_mask is None and moving_mask is None:
+                t = _centroid(moving) - _centroid(fixed)
+            else:                                              # an empty mask has no centroid: that sample starts at 0
+                t = _centroid(moving if moving_mask is None else moving * moving_mask) \
+                    - _centroid(fixed if fixed_mask is None else fixed * fixed_mask)
+                for mask in (fixed_mask, moving_mask):
+                    if mask is not None:
+                        t = torch.where((mask != 0).flatten(1).any(1, keepdim=True), t, torch.zeros_like(t))
+            for (ldims, f_l, m_l, ratio), fm_l, mm_l in zip(levels(fixed, moving, shrink), fmasks, mmasks):
                 sp = [s * r for s, r in zip(spacing, ratio)]
                 h = max(s * (n - 1) / 2 for s, n in zip(sp, ldims)) / min(sp)
-                pyramid.append((ldims, f_l, m_l, ops.mi_ranges(m_l, f_l, bins), ratio, sp, h))
+                pyramid.append((ldims, f_l, m_l, ops.mi_ranges(m_l, f_l, bins), ratio, sp, h, fm_l, mm_l))
         omega = torch.zeros_like(t)
         A = None
         for stage in _STAGES[transform]:
             if stage == "affine":
                 A = rotation_matrix(omega).detach()
-            for ldims, f_l, m_l, rng, ratio, sp, h in pyramid:
+            for ldims, f_l, m_l, rng, ratio, sp, h, fm_l, mm_l in pyramid:
                 t_l = scale_axes(t, ratio, divide=True).requires_grad_(True)
                 params = [t_l]
                 if stage == "translation":                     # L does not move in this stage: once per level, no graph
@@ -149,7 +166,7 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
                 opt = torch.optim.Adam(params, lr=lr)
                 for _ in range(iters):
                     opt.zero_grad(set_to_none=True)
-                    loss = -ops.warp_mutual_information(m_l, f_l, level_mat(), bins, rng).sum()
+                    loss = -ops.warp_mutual_information(m_l, f_l, level_mat(), bins, rng, fm_l, mm_l, inside).sum()
                     loss.backward()
                     opt.step()
                 t = scale_axes(t_l.detach(), ratio)

@@ -439,26 +439,28 @@ class ImageLC2(torch.nn.Module):
 class MILoss(torch.nn.Module):
     """-mean over the batch of the mutual information of (N, 1, D, H, W) float32 pairs (ops.mutual_information: cubic B-spline
     Parzen windows, `bins` bins, per-sample ranges); lower is better, differentiable in both inputs:
-    MILoss()(align_img(grid, img_m), img_f) scores or trains a multi-modal alignment."""
+    MILoss()(align_img(grid, img_m), img_f) scores or trains a multi-modal alignment.  mask: ops.mutual_information's, the voxels
+    that are counted."""
 
     def __init__(self, bins=32):
         super().__init__()
         self.bins = bins
 
-    def forward(self, pred, target):
-        return -ops.mutual_information(pred, target, self.bins).mean()
+    def forward(self, pred, target, mask=None):
+        return -ops.mutual_information(pred, target, self.bins, mask=mask).mean()
 
 
 class WarpMILoss(torch.nn.Module):
     """-mean over the batch of ops.warp_mutual_information(moving, fixed, mat, bins, ranges): MILoss of the moving volume warped
-    by the (N, 3, 4) matrix `mat` in one fused pass, differentiable in `mat` only."""
+    by the (N, 3, 4) matrix `mat` in one fused pass, differentiable in `mat` only.  fixed_mask, moving_mask, inside: the
+    operator's, which voxels are counted."""
 
     def __init__(self, bins=32):
         super().__init__()
         self.bins = bins
 
-    def forward(self, moving, fixed, mat, ranges=None):
-        return -ops.warp_mutual_information(moving, fixed, mat, self.bins, ranges).mean()
+    def forward(self, moving, fixed, mat, ranges=None, fixed_mask=None, moving_mask=None, inside=False):
+        return -ops.warp_mutual_information(moving, fixed, mat, self.bins, ranges, fixed_mask, moving_mask, inside).mean()
 
 
 class LNCCLoss(torch.nn.Module):

@@ -380,7 +380,7 @@ class IntensityRegistration(nn.Module):
     supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf")
 
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
-                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2):
+                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2, inside=False):
         super().__init__()
         from .io._deformable import metric_table
         metric_table("IntensityRegistration", metric)                          # refuses an unknown name
@@ -389,10 +389,12 @@ class IntensityRegistration(nn.Module):
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
         self.svf_steps = svf_steps
         self.mind_radius, self.mind_dilation = mind_radius, mind_dilation
+        self.inside = bool(inside)
 
-    def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, **kwargs):
+    def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, mask_f=None, mask_m=None,
+                **kwargs):
         from . import ops
-        from .io._deformable import metric_table
+        from .io._deformable import counted_voxels, metric_table
         from .io.bspline import register_bspline
         from .io.intensity import register_intensity
         from .io.svf import register_svf, svf_grid
@@ -412,21 +414,25 @@ class IntensityRegistration(nn.Module):
                             lambda ctrl, dims, m: svf_grid(ctrl, dims, m, k, inverse=True))}
         reported = metric_table("IntensityRegistration", self.metric, self.bins, self.window, self.mind_radius,
                                 self.mind_dilation).reported
+        masked = mask_f is not None or mask_m is not None or self.inside
+        masks = {"fixed_mask": mask_f, "moving_mask": mask_m, "inside": self.inside} if masked else {}
         result_dict = {}
         for align_type_str in transform_type:
             start_time = time.time()
             deformable = lattices.get(align_type_str)
             mat = register_intensity(img_f, img_m, "affine" if deformable else align_type_str, bins=self.bins, shrink=shrink,
-                                     iters=self.iters, lr=self.lr)
+                                     iters=self.iters, lr=self.lr, **masks)
             if deformable:
                 driver, grid_of, inverse_of = deformable
                 ctrl = driver(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending, bins=self.bins,
                               shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,
-                              mind_radius=self.mind_radius, mind_dilation=self.mind_dilation)
+                              mind_radius=self.mind_radius, mind_dilation=self.mind_dilation, **masks)
                 with torch.no_grad():
                     grid = grid_of(ctrl, img_f.shape[2:], mat)
                     warped = align_img(grid, img_m)
-                    res = {"grid": grid, "matrix": mat, "ctrl": ctrl, "mi": ops.mutual_information(warped, img_f, self.bins)}
+                    counted = counted_voxels(grid, mask_f, mask_m, self.inside) if masked else None
+                    res = {"grid": grid, "matrix": mat, "ctrl": ctrl,
+                           "mi": ops.mutual_information(warped, img_f, self.bins, mask=counted)}
                     if inverse_of:
                         res["inverse_grid"] = inverse_of(ctrl, img_f.shape[2:], mat)
                     if reported:
@@ -434,7 +440,7 @@ class IntensityRegistration(nn.Module):
             else:
                 with torch.no_grad():
                     res = {"grid": ops.affine_grid(mat, img_f.shape[2:]), "matrix": mat,
-                           "mi": ops.warp_mutual_information(img_m, img_f, mat, self.bins)}
+                           "mi": ops.warp_mutual_information(img_m, img_f, mat, self.bins, **masks)}
             res["time"] = time.time() - start_time
             result_dict[align_type_str] = res
         return result_dict

@@ -943,6 +943,70 @@ class _MI(torch.autograd.Function):
         return da, db, None, None, None, None
 
 
+def _need_mask(who: str, name: str, mask, like: Tensor):
+    """mask: None, or a uint8 / bool tensor of like's shape on the GPU -> contiguous uint8 (a bool mask viewed, not copied), or
+    ValueError."""
+    if mask is None:
+        return None
+    if not isinstance(mask, Tensor) or not mask.is_cuda or mask.device != like.device:
+        raise ValueError(f"{who}: {name} must be on the volumes' GPU")
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{who}: {name} must be uint8 or bool (non-zero = counted), got {mask.dtype}")
+    if mask.shape != like.shape:
+        raise ValueError(f"{who}: {name} must have the volumes' shape {tuple(like.shape)}, got {tuple(mask.shape)}")
+    mask = mask.detach().contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _mi_final_masked(ws, rng, cnt, N, bins):
+    """_mi_final with p = h / cnt[n], for the table a masked histogram pass left in ws."""
+    mi = torch.empty((N,), dtype=torch.float32, device=ws.device)
+    G = torch.empty((N, bins, bins), dtype=torch.float32, device=ws.device)
+    check(_lib.load().kmh_mi_final_masked(_p(ws), _p(rng), _p(cnt), N, bins, _p(mi), _p(G), _stream()), "kmh_mi_final_masked")
+    return mi, G
+
+
+class _MIMasked(torch.autograd.Function):
+    """_MI over the counted voxels (mask != 0), ranges given on the device.  The count stays on the device."""
+    @staticmethod
+    def forward(ctx, a, b, bins, rng, mask):
+        lib = _lib.load()
+        N, V = a.shape[0], a.numel() // a.shape[0]
+        ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=a.device)
+        cnt = torch.empty((N,), dtype=torch.int64, device=a.device)
+        if _lib.profiler.enabled:  # at most 9 B read per voxel
+            _lib.profiler.meta = {"bytes": 9.0 * N * V}
+        check(lib.kmh_mi_hist_masked(_p(a), _p(b), _p(mask), _p(rng), N, V, bins, _p(ws), _p(cnt), _stream()),
+              "kmh_mi_hist_masked")
+        mi, G = _mi_final_masked(ws, rng, cnt, N, bins)
+        ctx.save_for_backward(a, b, rng, G, mask, cnt)
+        ctx.bins = bins
+        ctx.mark_non_differentiable(G)
+        return mi, G
+
+    @staticmethod
+    def backward(ctx, gout, _gG):
+        lib = _lib.load()
+        a, b, rng, G, mask, cnt = ctx.saved_tensors
+        gout = _prep(gout)
+        N, V = a.shape[0], a.numel() // a.shape[0]
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": (9.0 + 4.0 * ((da is not None) + (db is not None))) * N * V}
+        check(lib.kmh_mi_bwd_masked(_p(a), _p(b), _p(mask), _p(rng), _p(G), _p(gout), _p(cnt), N, V, ctx.bins, _p(da), _p(db),
+                                    _stream()), "kmh_mi_bwd_masked")
+        return da, db, None, None, None
+
+
+def _mi_masked(a, b, bins, range_a, range_b, ranges, mask):
+    """(MI (N,), G) of checked inputs over the counted voxels.  The ranges are the caller's, or the whole volumes' own: the range
+    stage of kmh_mi_hist on its own (kmh_mi_range), then the masked histogram with the ranges given."""
+    if ranges is None:
+        ranges = _mi_ranges(a.detach(), b.detach(), bins, range_a, range_b)
+    return _MIMasked.apply(a, b, bins, ranges, mask)
+
+
 def _mi_check(a, b, bins, range_a, range_b):
     for name, t in (("a", a), ("b", b)):
         _need_gpu_f32("mutual_information", name, t)
@@ -958,30 +1022,46 @@ def _mi_check(a, b, bins, range_a, range_b):
     return a.contiguous(), b.contiguous(), bins, out[0], out[1]
 
 
-def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges: Optional[Tensor] = None) -> Tensor:
+def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges: Optional[Tensor] = None,
+                       mask: Optional[Tensor] = None) -> Tensor:
     """Mutual information (nats) of two (N, 1, D, H, W) float32 volumes on the current GPU, per sample -> (N,), differentiable in
     both.  Parzen-window joint histogram with the cubic B-spline and Mattes' padding: per sample and image, u = (x - lo) s + 1 with
     s = (bins - 3) / (hi - lo) over the image's own minimum and maximum (no gradient through them), or over `range_x = (lo, hi)`
     (values outside are taken at the range's ends); a constant image has s = 0, MI = 0 and zero gradients.  Two calls give
     bit-identical values and gradients; a batch equals its samples run one by one.  `ranges`: instead of range_a / range_b, the
     (N, 4) device tensor mi_ranges(a0, b) returns, per sample, for a volume a0 whose range bounds a's (a = a warp of a0): the
-    host never reads a range (io.register_bspline)."""
+    host never reads a range (io.register_bspline).  `mask`: (N, 1, D, H, W) uint8 or bool on the GPU, data without a gradient:
+    only voxels with mask != 0 are counted -- they alone enter the joint table, p = h / M_n with M_n their number, their gradient
+    is scaled by 1 / M_n and every other voxel's is 0; M_n = 0 gives MI = 0 and zero gradients.  The ranges stay the caller's or
+    the WHOLE volume's minimum and maximum, not the masked part's.  The host never reads M_n."""
     if ranges is not None:
         if range_a is not None or range_b is not None:
             raise ValueError("mutual_information: give either range_a / range_b or ranges, not both")
         a, b, bins, _, _ = _mi_check(a, b, bins, None, None)
+        mask = _need_mask("mutual_information", "mask", mask, a)
         _need_gpu_f32("mutual_information", "ranges", ranges)
         if tuple(ranges.shape) != (a.shape[0], 4):
             raise ValueError(f"mutual_information: ranges must be ({a.shape[0]}, 4) as mi_ranges returns them, got "
                              f"{tuple(ranges.shape)}")
+        if mask is not None:
+            return _mi_masked(a, b, bins, None, None, ranges.detach().contiguous(), mask)[0]
         return _MI.apply(a, b, bins, None, None, ranges.detach().contiguous())
-    return _MI.apply(*_mi_check(a, b, bins, range_a, range_b))
+    checked = _mi_check(a, b, bins, range_a, range_b)
+    mask = _need_mask("mutual_information", "mask", mask, a)
+    if mask is not None:
+        return _mi_masked(*checked, None, mask)[0]
+    return _MI.apply(*checked)
 
 
-def _mi_table(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None):
+def _mi_table(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges=None, mask=None):
     """(MI (N,), G (N, bins, bins)) without autograd: G = ln(p / (pa pb)) where the joint probability p > 0, else 0 -- the table the
-    gradient of mutual_information gathers from."""
-    mi, _, G = _mi_forward(*_mi_check(a.detach(), b.detach(), bins, range_a, range_b))
+    gradient of mutual_information gathers from.  ranges, mask: as mutual_information takes them."""
+    if mask is not None:
+        a, b, bins, range_a, range_b = _mi_check(a.detach(), b.detach(), bins, range_a, range_b)
+        mask = _need_mask("mutual_information", "mask", mask, a)
+        return _mi_masked(a, b, bins, range_a, range_b, None if ranges is None else ranges.detach().contiguous(), mask)
+    mi, _, G = _mi_forward(*_mi_check(a.detach(), b.detach(), bins, range_a, range_b),
+                           None if ranges is None else ranges.detach().contiguous())
     return mi, G
 
 
@@ -1003,13 +1083,14 @@ def _warp_mi_check(moving, fixed, mat, bins, ranges, who="warp_mutual_informatio
     return bins
 
 
-def _mi_ranges(moving, fixed, bins):
+def _mi_ranges(moving, fixed, bins, range_a=None, range_b=None):
     lib = _lib.load()
     N, V = moving.shape[0], moving.numel() // moving.shape[0]
     ws = torch.empty(16 * N, dtype=torch.uint8, device=moving.device)
     rng = torch.empty((N, 4), dtype=torch.float32, device=moving.device)
-    check(lib.kmh_mi_range(_p(moving), _p(fixed), N, V, bins, 0, 0.0, 0.0, 0, 0.0, 0.0, _p(ws), _p(rng), _stream()),
-          "kmh_mi_range")
+    ra, rb = range_a or (0.0, 0.0), range_b or (0.0, 0.0)
+    check(lib.kmh_mi_range(_p(moving), _p(fixed), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None),
+                           rb[0], rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_range")
     return rng
 
 
@@ -1054,26 +1135,77 @@ class _WarpMI(torch.autograd.Function):
         return None, None, dmat, None, None
 
 
-def _warp_mi(moving, fixed, mat, bins, ranges):
+class _WarpMIMasked(torch.autograd.Function):
+    """_WarpMI over the counted voxels (csrc/warp_mi.hip states which).  The count stays on the device."""
+    @staticmethod
+    def forward(ctx, moving, fixed, mat, rng, bins, fixed_mask, moving_mask, inside):
+        lib = _lib.load()
+        N, _, D, H, W = moving.shape
+        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=moving.device)
+        cnt = torch.empty((N,), dtype=torch.int64, device=moving.device)
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": 10.0 * N * D * H * W}
+        check(lib.kmh_warp_mi_hist_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), N, D, H, W,
+                                          bins, int(inside), _p(ws), _p(cnt), _stream()), "kmh_warp_mi_hist_masked")
+        mi, G = _mi_final_masked(ws, rng, cnt, N, bins)
+        ctx.save_for_backward(moving, fixed, mat, rng, G, cnt, fixed_mask, moving_mask)
+        ctx.bins, ctx.inside = bins, int(inside)
+        ctx.mark_non_differentiable(G)
+        return mi, G
+
+    @staticmethod
+    def backward(ctx, gout, _gG):
+        if not ctx.needs_input_grad[2]:
+            return (None,) * 8
+        lib = _lib.load()
+        moving, fixed, mat, rng, G, cnt, fixed_mask, moving_mask = ctx.saved_tensors
+        gout = _prep(gout)
+        N, _, D, H, W = moving.shape
+        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, ctx.bins, D, H, W)), dtype=torch.uint8, device=moving.device)
+        dmat = torch.empty_like(mat)
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": 10.0 * N * D * H * W}
+        check(lib.kmh_warp_mi_bwd_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), _p(G), _p(gout),
+                                         _p(cnt), N, D, H, W, ctx.bins, ctx.inside, _p(ws), _p(dmat), _stream()),
+              "kmh_warp_mi_bwd_masked")
+        return None, None, dmat, None, None, None, None, None
+
+
+def _warp_mi(moving, fixed, mat, bins, ranges, fixed_mask=None, moving_mask=None, inside=False):
     bins = _warp_mi_check(moving, fixed, mat, bins, ranges)
+    fixed_mask = _need_mask("warp_mutual_information", "fixed_mask", fixed_mask, fixed)
+    moving_mask = _need_mask("warp_mutual_information", "moving_mask", moving_mask, moving)
     moving, fixed = moving.detach().contiguous(), fixed.detach().contiguous()
     rng = _mi_ranges(moving, fixed, bins) if ranges is None else ranges.detach().contiguous()
-    return _WarpMI.apply(moving, fixed, mat.contiguous(), rng, bins)
+    if fixed_mask is None and moving_mask is None and not inside:
+        return _WarpMI.apply(moving, fixed, mat.contiguous(), rng, bins)
+    return _WarpMIMasked.apply(moving, fixed, mat.contiguous(), rng, bins, fixed_mask, moving_mask, bool(inside))
 
 
-def warp_mutual_information(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None) -> Tensor:
+def warp_mutual_information(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None,
+                            fixed_mask: Optional[Tensor] = None, moving_mask: Optional[Tensor] = None,
+                            inside: bool = False) -> Tensor:
     """Mutual information (nats) of `fixed` and `moving` warped by `mat`, per sample -> (N,), in one pass: by definition
     mutual_information(align_img(affine_grid(mat, dims), moving), fixed, range_a=range of moving, range_b=range of fixed) sample by
     sample, with the same joint table bit for bit, but neither the grid nor the warped volume is stored.  moving, fixed:
     (N, 1, D, H, W) float32 on the current GPU (data: no gradient); mat (N, 3, 4) as affine_grid takes it, differentiable;
     ranges: mi_ranges(moving, fixed, bins), computed here when None.  Two calls give bit-identical values and gradients; a batch
-    equals its samples run one by one."""
-    return _warp_mi(moving, fixed, mat, bins, ranges)[0]
+    equals its samples run one by one.
+
+    fixed_mask, moving_mask: (N, 1, D, H, W) uint8 or bool on the GPU (data), inside: bool.  Voxel v of the fixed lattice, with
+    sampling coordinate g(v) = affine_grid(mat)[v], is COUNTED iff fixed_mask[v] != 0, moving_mask is non-zero at the voxel the
+    nearest sampler reads for g(v), and (inside=True) |g(v)_k| <= 1 on all three axes (a NaN is outside); an argument left out
+    does not restrict.  The result is mutual_information(warped, fixed, ranges, mask=c) with
+    c = fixed_mask & (align_img(grid, moving_mask.float(), "nearest") != 0) & (grid.abs() <= 1).all(-1), same table bit for bit.
+    The number of counted voxels M_n is piecewise constant in mat and not differentiated: dmat sums over the counted voxels,
+    scaled by 1 / M_n.  The ranges stay those of the whole volumes."""
+    return _warp_mi(moving, fixed, mat, bins, ranges, fixed_mask, moving_mask, inside)[0]
 
 
-def _warp_mi_table(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None):
+def _warp_mi_table(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None,
+                   fixed_mask=None, moving_mask=None, inside=False):
     """(MI (N,), G (N, bins, bins)) of warp_mutual_information without autograd: _mi_table's counterpart."""
-    mi, G = _warp_mi(moving, fixed, mat.detach(), bins, ranges)
+    mi, G = _warp_mi(moving, fixed, mat.detach(), bins, ranges, fixed_mask, moving_mask, inside)
     return mi, G
 
 
