@@ -668,6 +668,21 @@ int kmh_mind_fwd(const float* a, const float* b, const float* bounds, int N, int
 int kmh_mind_bwd(const float* a, const float* b, const float* bounds, const float* gout, int N, int D, int H, int W, int radius,
                  int dilation, float* da, float* db, void* ws, void* stream);
 
+/* ---- cubic B-spline resampling (csrc/cubic.hip states the definition) ----
+ * x, coef (N,C,D,H,W); grid (N,Do,Ho,Wo,3) xyz in the convention of kmh_grid_sample3d_fwd (border, align_corners=False, the same
+ * fp32 source coordinate, clamp mask and NaN rule).  kmh_cubic_prefilter: coef = the cubic B-spline coefficients of x, separably
+ * along W, H, D with whole-sample mirror ends (an axis of length 1 is left alone).  kmh_cubic_sample_fwd:
+ * out (N,C,Do,Ho,Wo) = the spline of coef at grid (64 taps, mirrored at the ends; it overshoots and is not clamped).
+ * kmh_cubic_sample_bwd_grid: dgrid (N,Do,Ho,Wo,3) = d(out)/d(grid) contracted with gout (N,C,Do,Ho,Wo); 0 on a clamped axis, 0
+ * on all three for a voxel with a NaN coordinate.  There is no gradient with respect to the volume.  No atomics: runs repeat bit
+ * for bit and a batch equals its samples.  -22 for a null pointer, an empty shape, a channel plane of 2^29 voxels or more or
+ * N > 65535. */
+int kmh_cubic_prefilter(const float* x, float* coef, int N, int C, int D, int H, int W, void* stream);
+int kmh_cubic_sample_fwd(const float* coef, const float* grid, float* out, int N, int C, int D, int H, int W, int Do, int Ho,
+                         int Wo, void* stream);
+int kmh_cubic_sample_bwd_grid(const float* coef, const float* grid, const float* gout, float* dgrid, int N, int C, int D, int H,
+                              int W, int Do, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

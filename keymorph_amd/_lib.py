@@ -192,6 +192,9 @@ PROTOS = {
     "kmh_mind_bounds": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
     "kmh_mind_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
     "kmh_mind_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "kmh_cubic_prefilter": (_i, [_f, _f, _i, _i, _i, _i, _i, _f]),
+    "kmh_cubic_sample_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_cubic_sample_bwd_grid": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
 }
 
 _lib = None

@@ -131,7 +131,110 @@ class _GridSample3d(torch.autograd.Function):
 
 
 def grid_sample3d(x: Tensor, grid: Tensor, mode: str = "bilinear") -> Tensor:
+    """mode "cubic": cubic_sample(cubic_coefficients(x), grid), differentiable in the grid only."""
+    if mode == "cubic":
+        return _GridSampleCubic.apply(x, grid)
     return _GridSample3d.apply(x, grid, {"bilinear": 0, "nearest": 1}[mode])
+
+
+# cubic B-spline resampling (csrc/cubic.hip): the limits of its kernels
+CUBIC_MAX_PLANE = 1 << 29      # voxels of one channel plane (32-bit byte offsets inside it)
+CUBIC_MAX_BATCH = 65535
+
+
+def _cubic_check(who: str, x, grid=None) -> None:
+    """x: a non-empty (N, C, D, H, W) volume on the GPU within the kernels' limits; grid: (N, Do, Ho, Wo, 3), non-empty.
+    KeymorphHipError for a tensor that is not on the GPU, ValueError for the rest -- before anything is allocated or copied."""
+    _need_gpu(who, "the volume", x)
+    if grid is not None:
+        _need_gpu(who, "grid", grid)
+    if x.dim() != 5 or x.numel() == 0:
+        raise ValueError(f"{who}: expected a non-empty (N, C, D, H, W) volume, got {tuple(x.shape)}")
+    N, _, D, H, W = x.shape
+    if D * H * W >= CUBIC_MAX_PLANE or N > CUBIC_MAX_BATCH:
+        raise ValueError(f"{who}: a channel plane must have fewer than 2^29 voxels and the batch at most {CUBIC_MAX_BATCH} "
+                         f"samples, got {tuple(x.shape)}")
+    if grid is not None and (grid.dim() != 5 or grid.shape[0] != N or grid.shape[4] != 3 or grid.numel() == 0):
+        raise ValueError(f"{who}: expected a non-empty grid ({N}, Do, Ho, Wo, 3), got {tuple(grid.shape)}")
+
+
+def _cubic_prefilter(x: Tensor) -> Tensor:
+    x = _prep(x.detach(), "x")
+    coef = torch.empty_like(x)
+    N, C, D, H, W = x.shape
+    if _lib.profiler.enabled:  # the floor: every pass reads and writes each voxel once
+        _lib.profiler.meta = {"bytes": 8.0 * x.numel() * sum(1 for n in (D, H, W) if n > 1)}
+    check(_lib.load().kmh_cubic_prefilter(_p(x), _p(coef), N, C, D, H, W, _stream()), "kmh_cubic_prefilter")
+    return coef
+
+
+def _cubic_fwd(coef: Tensor, grid: Tensor) -> Tensor:
+    N, C, D, H, W = coef.shape
+    _, Do, Ho, Wo, _ = grid.shape
+    out = torch.empty((N, C, Do, Ho, Wo), dtype=torch.float32, device=coef.device)
+    if _lib.profiler.enabled:  # grid 12 B + C * out 4 B per output voxel, the coefficients once
+        _lib.profiler.meta = {"bytes": float(N * Do * Ho * Wo) * (12 + 4 * C) + 4.0 * coef.numel()}
+    check(_lib.load().kmh_cubic_sample_fwd(_p(coef), _p(grid), _p(out), N, C, D, H, W, Do, Ho, Wo, _stream()),
+          "kmh_cubic_sample_fwd")
+    return out
+
+
+def _cubic_bwd(ctx, gout):
+    """the shared backward of the two cubic Functions: saved (coef, grid); input 0 is the volume / the coefficients"""
+    if ctx.needs_input_grad[0]:
+        raise NotImplementedError("cubic resampling has no gradient with respect to the volume (only to the grid)")
+    if not ctx.needs_input_grad[1]:
+        return None, None
+    coef, grid = ctx.saved_tensors
+    gout = _prep(gout)
+    N, C, D, H, W = coef.shape
+    _, Do, Ho, Wo, _ = grid.shape
+    dgrid = torch.empty_like(grid)
+    if _lib.profiler.enabled:  # gout 4C + grid 12 + dgrid 12 B per output voxel, the coefficients once
+        _lib.profiler.meta = {"bytes": float(N * Do * Ho * Wo) * (24 + 4 * C) + 4.0 * coef.numel()}
+    check(_lib.load().kmh_cubic_sample_bwd_grid(_p(coef), _p(grid), _p(gout), _p(dgrid), N, C, D, H, W, Do, Ho, Wo,
+                                                _stream()), "kmh_cubic_sample_bwd_grid")
+    return None, dgrid
+
+
+class _CubicSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coef, grid):
+        coef, grid = _prep(coef, "coef"), _prep(grid, "grid")
+        ctx.save_for_backward(coef, grid)
+        return _cubic_fwd(coef, grid)
+
+    backward = staticmethod(_cubic_bwd)
+
+
+class _GridSampleCubic(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, grid):
+        _cubic_check("grid_sample3d", x, grid)
+        coef, grid = _cubic_prefilter(x), _prep(grid, "grid")
+        ctx.save_for_backward(coef, grid)
+        return _cubic_fwd(coef, grid)
+
+    backward = staticmethod(_cubic_bwd)
+
+
+def cubic_coefficients(x: Tensor) -> Tensor:
+    """The cubic B-spline coefficients of x (N, C, D, H, W) -> (N, C, D, H, W) float32: the separable recursive prefilter along
+    W, H and D with whole-sample mirror ends (scipy.ndimage.spline_filter(order=3, mode="mirror") per channel); an axis of
+    length 1 is left alone.  No graph through it: the volumes are data.  For callers that sample one volume many times:
+    cubic_sample(cubic_coefficients(x), grid) is grid_sample3d(x, grid, "cubic")."""
+    _cubic_check("cubic_coefficients", x)
+    return _cubic_prefilter(x)
+
+
+def cubic_sample(coef: Tensor, grid: Tensor) -> Tensor:
+    """The cubic B-spline with coefficients coef (N, C, D, H, W) at grid (N, Do, Ho, Wo, 3) -> (N, C, Do, Ho, Wo), in align_img's
+    convention (border, align_corners=False: the trilinear sampler's source coordinate, clamped to the voxel centres, with a zero
+    grid gradient where clamped).  64 taps, mirrored at the ends like the coefficients.  The spline interpolates the data at the
+    voxel centres and overshoots between them: data in [0, 1] can leave [0, 1], and nothing is clamped -- label maps stay on
+    "nearest".  Differentiable in grid only; a coef that requires a gradient raises NotImplementedError in backward."""
+    _cubic_check("cubic_sample", coef, grid)
+    return _CubicSample.apply(coef, grid)
 
 
 class _WarpMSE(torch.autograd.Function):
