@@ -683,6 +683,22 @@ int kmh_cubic_sample_fwd(const float* coef, const float* grid, float* out, int N
 int kmh_cubic_sample_bwd_grid(const float* coef, const float* grid, const float* gout, float* dgrid, int N, int C, int D, int H,
                               int W, int Do, int Ho, int Wo, void* stream);
 
+/* ---- Gaussian smoothing and its transpose (csrc/gauss.hip states the definition) ----
+ * x, out, gout, dx (N,C,D,H,W) float32.  Per axis a radius r (rz, ry, rx; 0 = the axis is not touched) and HOST pointers: w* to
+ * the half-kernel w[0..r] (w[|k|], normalised over k = -r..r), t* to the tail sums t[i] = sum_{k >= i} w[k], i = 0..r (the
+ * transpose only); a pointer may be NULL where its radius is 0.  The launcher copies them into kernel arguments by value: no
+ * host-to-device copy.  kmh_gauss_fwd: out[i] = sum_k w[k] x[clamp(i + k, 0, n - 1)] along W, then H, then D.  kmh_gauss_bwd:
+ * dx = the transposed operator applied to gout, a gather, along D, then H, then W.  ws: kmh_gauss_ws_bytes(...) bytes of
+ * scratch (0 with fewer than two active axes; ws may then be NULL).  out must not alias x (nor dx gout), ws neither.  No
+ * atomics: runs repeat bit for bit and a batch equals its samples.  -22 (kmh_gauss_ws_bytes: 0) for a null pointer, an empty
+ * shape, a radius outside 0..32, a channel plane of 2^29 voxels or more or N C > 65535. */
+size_t kmh_gauss_ws_bytes(int N, int C, int D, int H, int W, int rz, int ry, int rx);
+int kmh_gauss_fwd(const float* x, float* out, void* ws, int N, int C, int D, int H, int W, int rz, int ry, int rx,
+                  const float* wz, const float* wy, const float* wx, void* stream);
+int kmh_gauss_bwd(const float* gout, float* dx, void* ws, int N, int C, int D, int H, int W, int rz, int ry, int rx,
+                  const float* wz, const float* wy, const float* wx, const float* tz, const float* ty, const float* tx,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,9 @@ PROTOS = {
     "kmh_cubic_prefilter": (_i, [_f, _f, _i, _i, _i, _i, _i, _f]),
     "kmh_cubic_sample_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
     "kmh_cubic_sample_bwd_grid": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_gauss_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "kmh_gauss_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "kmh_gauss_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
 }
 
 _lib = None

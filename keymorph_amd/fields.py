@@ -184,3 +184,37 @@ def from_displacement(disp: Tensor) -> Tensor:
     out = torch.empty((n, D, H, W, 3), dtype=torch.float32, device=disp.device)
     check(_lib.load().kmh_field_from_displacement(_p(disp), _p(out), n, D, H, W, _stream()), "kmh_field_from_displacement")
     return out
+
+
+class _SmoothGrid(torch.autograd.Function):
+    """smooth(): the chain of three kernels forward; backward, the smoothing's transpose on each component of the cotangent -- the
+    two displacement maps scale a component by S / 2 and by 2 / S, which cancel around an operator that works per channel."""
+
+    @staticmethod
+    def forward(ctx, grid, sigma, plan):
+        ctx.plan = plan
+        return from_displacement(ops.gaussian_smooth(to_displacement(grid.detach()), sigma))
+
+    @staticmethod
+    def backward(ctx, gout):
+        if ctx.plan is None:
+            return gout, None, None
+        g = ops._prep(gout, "gout").permute(0, 4, 1, 2, 3).contiguous()
+        return ops._gauss_call(g, ctx.plan, True).permute(0, 2, 3, 4, 1).contiguous(), None, None
+
+
+def smooth(grid: Tensor, sigma) -> Tensor:
+    """The grid (n, D, H, W, 3) whose voxel displacement is ``grid``'s, smoothed by a Gaussian of ``sigma`` voxels (a number or a
+    (z, y, x) triple): ``from_displacement(ops.gaussian_smooth(to_displacement(grid), sigma))`` -- the regulariser of demons and
+    SyN.  The DISPLACEMENT is smoothed, not the grid: the smoothing replicates its border, which would flatten the identity's
+    ramp near the faces, while a zero displacement stays zero (``smooth(identity_grid(...), sigma)`` is the identity, bit for bit).
+    Unlike the rest of this module it is differentiable in ``grid``."""
+    if not isinstance(grid, torch.Tensor):
+        raise _lib.KeymorphHipError(f"grid: expected a torch tensor, got {type(grid).__name__}")
+    ops._need_gpu_f32("smooth", "grid", grid)
+    if grid.dim() != 5 or grid.shape[-1] != 3 or grid.numel() == 0:
+        raise ValueError(f"grid: expected a grid (n, D, H, W, 3), got {tuple(grid.shape)}")
+    n, D, H, W, _ = grid.shape
+    # the displacement's shape as a view of one element: sigma and the limits are checked before anything is allocated
+    plan = ops._gauss_plan("smooth", grid.detach().reshape(-1)[:1].expand(n, 3, D, H, W), sigma, 4.0)
+    return _SmoothGrid.apply(grid, sigma, plan)

@@ -6,7 +6,7 @@ import collections
 
 import torch
 
-from ._pyramid import as_data, levels, mask_levels, scale_axes
+from ._pyramid import as_data, levels, mask_levels, resolve_smoothing, scale_axes
 from .intensity import _conjugate, mat_to_voxel, register_intensity, voxel_to_mat
 
 # per_level(m_l, f_l) -> state: once per level, under no_grad, of the level's UNWARPED pair, without waiting for the GPU.
@@ -52,13 +52,15 @@ def counted_voxels(grid, fixed_mask=None, moving_mask=None, inside=False):
 
 
 def fit_lattice(who, fixed, moving, mat, grid_of, metric, control_spacing, bending, bins, shrink, iters, lr, fixed_mask=None,
-                moving_mask=None, inside=False, metric_name="mi"):
+                moving_mask=None, inside=False, metric_name="mi", smoothing_sigmas=None):
     """ctrl (N, 3, Cz, Cy, Cx) on ops.bspline_lattice_shape(dims, control_spacing), normalised, such that
     align_img(grid_of(ctrl, dims, mat), moving) lines up with fixed under `metric` (a Metric): the schedule the drivers' docstrings
     describe.  grid_of(ctrl_l, ldims, mat_l) -> grid (N, *ldims, 3) is the transform model, differentiable in ctrl_l.  mat None:
     register_intensity's affine answer.  fixed_mask, moving_mask, inside: register_intensity's; per step the counted set is
     counted_voxels of the step's grid (level masks as register_intensity builds them) and goes to the similarity as `mask`.  Only
-    metric_name "mi" knows masks: ValueError with any other.  Nothing inside the loop waits for the GPU."""
+    metric_name "mi" knows masks: ValueError with any other.  smoothing_sigmas: estimate_translation's, for this pyramid and for the
+    affine start run here when mat is None; the metric's per-level state comes from the smoothed level pair.  Nothing inside the
+    loop waits for the GPU."""
     from .. import ops
     from ..utils import align_img
     if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
@@ -67,6 +69,7 @@ def fit_lattice(who, fixed, moving, mat, grid_of, metric, control_spacing, bendi
     masked = fixed_mask is not None or moving_mask is not None or bool(inside)
     if masked and metric_name != "mi":
         raise ValueError(f"{who}: fixed_mask, moving_mask and inside work with metric='mi' only, got metric={metric_name!r}")
+    resolve_smoothing(who, shrink, smoothing_sigmas)
     N, dims = fixed.shape[0], tuple(fixed.shape[2:])
     if mat is not None and tuple(mat.shape) != (N, 3, 4):
         raise ValueError(f"{who}: mat must be ({N}, 3, 4), got {tuple(mat.shape)}")
@@ -77,12 +80,12 @@ def fit_lattice(who, fixed, moving, mat, grid_of, metric, control_spacing, bendi
         mmasks = mask_levels(who, "moving_mask", moving_mask, moving, shrink)
         if mat is None:
             mat = register_intensity(fixed, moving, "affine", bins=bins, shrink=shrink, fixed_mask=fixed_mask,
-                                     moving_mask=moving_mask, inside=inside)
+                                     moving_mask=moving_mask, inside=inside, smoothing_sigmas=smoothing_sigmas)
         mat = as_data(mat)
         q = torch.zeros((N, 3, *lattice), dtype=torch.float32, device=fixed.device)      # voxels of the full size, (x, y, z)
         with torch.no_grad():
             L, t = mat_to_voxel(mat, dims)
-        for (ldims, f_l, m_l, ratio), fm_l, mm_l in zip(levels(fixed, moving, shrink), fmasks, mmasks):
+        for (ldims, f_l, m_l, ratio), fm_l, mm_l in zip(levels(fixed, moving, shrink, smoothing_sigmas, who), fmasks, mmasks):
             # ratio in (z, y, x), q's channels in (x, y, z)
             with torch.no_grad():
                 state = metric.per_level(m_l, f_l)

@@ -17,11 +17,57 @@ def level_dims(dims, shrink):
     return out
 
 
-def levels(fixed, moving, shrink):
+def resolve_smoothing(who, shrink, smoothing):
+    """The per-level Gaussian sigmas of a pyramid, one entry per entry of `shrink`, or None.  smoothing: None (no smoothing: the
+    pyramid of before), "auto" (sigma = shrink / 2 per level, 0 at shrink 1 -- the ANTs / elastix habit), or a sequence of
+    len(shrink) entries, each a number or a (z, y, x) triple >= 0 in voxels of the FULL-resolution volume.  ValueError naming
+    `who` for anything else."""
+    from .. import ops
+    if smoothing is None:
+        return None
+    shrink = tuple(shrink)
+    if isinstance(smoothing, str):
+        if smoothing != "auto":
+            raise ValueError(f"{who}: smoothing_sigmas must be None, 'auto' or one entry per pyramid level, got {smoothing!r}")
+        return tuple(0.0 if int(sh) <= 1 else int(sh) / 2.0 for sh in shrink)
+    try:
+        entries = tuple(smoothing)
+    except TypeError:
+        raise ValueError(f"{who}: smoothing_sigmas must be None, 'auto' or one entry per pyramid level, got {smoothing!r}") from None
+    if len(entries) != len(shrink):
+        raise ValueError(f"{who}: smoothing_sigmas has {len(entries)} entries for the {len(shrink)} levels of shrink={shrink}")
+    out = []
+    for e in entries:
+        sig = ops._gauss_sigmas(who, e, 4.0)
+        out.append(float(e) if isinstance(e, (int, float)) else sig)
+    return tuple(out)
+
+
+def level_smoothing(who, dims, shrink, smoothing):
+    """resolve_smoothing's entries for the levels level_dims(dims, shrink) keeps (a dropped level drops its entry); None: None."""
+    sig = resolve_smoothing(who, shrink, smoothing)
+    if sig is None:
+        return None
+    return [s for sh, s in zip(shrink, sig) if min(int(n) // int(sh) for n in dims) >= MIN_AXIS]
+
+
+def levels(fixed, moving, shrink, smoothing=None, who="levels"):
     """Per level (ldims, fixed_l, moving_l, ratio) of two (N, 1, D, H, W) volumes of one shape: the pair resized (trilinear, no
-    graph) to ldims -- the inputs themselves, no copy, at the full size -- and ratio[k] = dims[k] / ldims[k], (z, y, x)."""
+    graph) to ldims -- the inputs themselves, no copy, at the full size -- and ratio[k] = dims[k] / ldims[k], (z, y, x).
+    smoothing (resolve_smoothing; `who` is named in its errors): level l is resize_trilinear(ops.gaussian_smooth(v, sigma_l),
+    ldims), smoothed at the full resolution before it shrinks; with sigma_l = 0 at the full size it is still the input itself."""
     from ..utils import resize_trilinear
     dims = tuple(fixed.shape[2:])
+    if smoothing is not None:
+        from .. import ops
+        sigmas = level_smoothing(who, dims, shrink, smoothing)
+        for ldims, sigma in zip(level_dims(dims, shrink), sigmas):
+            with torch.no_grad():
+                f_l, m_l = ops.gaussian_smooth(fixed, sigma), ops.gaussian_smooth(moving, sigma)
+                if ldims != dims:
+                    f_l, m_l = resize_trilinear(f_l, size=ldims), resize_trilinear(m_l, size=ldims)
+            yield ldims, f_l, m_l, [n / l for n, l in zip(dims, ldims)]
+        return
     for ldims in level_dims(dims, shrink):
         if ldims == dims:
             f_l, m_l = fixed, moving

@@ -19,7 +19,7 @@ def apply_bspline(x, ctrl, mat=None, mode="bilinear"):
 
 def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
                      metric="mi", window=9, mind_radius=1, mind_dilation=2, fixed_mask=None, moving_mask=None,
-                     inside=False):
+                     inside=False, smoothing_sigmas=None):
     """ctrl (N, 3, Cz, Cy, Cx) on the lattice ops.bspline_lattice_shape(dims, control_spacing) such that
     apply_bspline(moving, ctrl, mat) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual
     information.  mat (N, 3, 4): the affine part, data; None: register_intensity(fixed, moving, "affine", bins=bins,
@@ -48,8 +48,12 @@ def register_bspline(fixed, moving, mat=None, control_spacing=8, bending=0.05, b
     (|grid| <= 1), of the step's own grid, and the similarity is ops.mutual_information(..., mask=that set).  They work with
     metric="mi" only: with "lncc" or "mind" any of them raises ValueError (masked local metrics do not exist here).
 
+    smoothing_sigmas: None, "auto" or one Gaussian sigma per entry of `shrink`, as io.estimate_translation takes it: every level
+    pair is smoothed at the full size before it is resized (the default affine start gets it too), and the ranges / bounds come
+    from the smoothed pair.
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     table = metric_table("register_bspline", metric, bins, window, mind_radius, mind_dilation)
     return fit_lattice("register_bspline", fixed, moving, mat, ops.bspline_grid, table, control_spacing, bending, bins, shrink,
-                       iters, lr, fixed_mask, moving_mask, inside, metric)
+                       iters, lr, fixed_mask, moving_mask, inside, metric, smoothing_sigmas)

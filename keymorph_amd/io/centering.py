@@ -4,7 +4,7 @@ translation is applied to the unmasked image (linear) and to the mask (nearest).
 SimpleITK; here it is ops.mutual_information under Adam, over a trilinear pyramid."""
 import torch
 
-from ._pyramid import levels, scale_axes
+from ._pyramid import levels, resolve_smoothing, scale_axes
 
 
 def translate(x, t, mode="bilinear"):
@@ -35,20 +35,25 @@ def _centroid(x):
     return torch.stack([(c[:, k] + 1.0) * (0.5 * (n - 1)) for k, n in enumerate(x.shape[2:])], dim=1)
 
 
-def estimate_translation(fixed, moving, bins=32, shrink=(4, 2, 1), iters=30, lr=0.25):
+def estimate_translation(fixed, moving, bins=32, shrink=(4, 2, 1), iters=30, lr=0.25, smoothing_sigmas=None):
     """t (N, 3) voxels, (z, y, x), such that translate(moving, t) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of
     one shape) under mutual information.  Start: the difference of the two intensity centroids.  Then, per pyramid level
     (size // shrink by trilinear resize; a level with an axis shorter than 16 is skipped), `iters` Adam steps of size `lr` voxels
     of that level on -MI(translate(moving_l, t_l), fixed_l); t is carried from level to level in full-resolution voxels.  Every
-    sample is optimised on its own (the loss is the sum over the batch); nothing inside the loop waits for the GPU."""
+    sample is optimised on its own (the loss is the sum over the batch); nothing inside the loop waits for the GPU.
+    smoothing_sigmas: None (the plain trilinear pyramid), "auto" (shrink / 2 per level, 0 at shrink 1) or one Gaussian sigma per
+    entry of `shrink`, a number or a (z, y, x) triple in full-resolution voxels: each level is ops.gaussian_smooth'ed at the full
+    size before it is resized (io/_pyramid.py), as ANTs' --smoothing-sigmas and elastix' pyramid schedules do -- what noisy
+    volumes need at shrink 4, where the trilinear resize alone reads two voxels in four."""
     from .. import ops
     if fixed.shape != moving.shape or fixed.dim() != 5 or fixed.shape[1] != 1:
         raise ValueError(f"estimate_translation: expected two (N, 1, D, H, W) volumes of one shape, got {tuple(fixed.shape)} and "
                          f"{tuple(moving.shape)}")
+    resolve_smoothing("estimate_translation", shrink, smoothing_sigmas)      # refused before any work
     fixed, moving = fixed.detach(), moving.detach()
     with torch.no_grad():
         t = _centroid(moving) - _centroid(fixed)
-    for _, f_l, m_l, ratio in levels(fixed, moving, shrink):
+    for _, f_l, m_l, ratio in levels(fixed, moving, shrink, smoothing_sigmas, "estimate_translation"):
         t_l = scale_axes(t, ratio, divide=True).requires_grad_(True)
         opt = torch.optim.Adam([t_l], lr=lr)
         for _ in range(iters):

@@ -8,7 +8,7 @@ the volume's centre, L (N, 3, 3), t (N, 3) voxels, rows and columns in (z, y, x)
 takes.  translate(x, t) of io.centering is the case L = I."""
 import torch
 
-from ._pyramid import as_data, levels, mask_levels, scale_axes
+from ._pyramid import as_data, levels, mask_levels, resolve_smoothing, scale_axes
 
 
 def _dims3(dims):
@@ -85,7 +85,7 @@ _STAGES = {"translation": ("translation",), "rigid": ("translation", "rigid"), "
 
 
 def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 1), iters=30, lr=0.25, spacing=(1.0, 1.0, 1.0),
-                       fixed_mask=None, moving_mask=None, inside=False):
+                       fixed_mask=None, moving_mask=None, inside=False, smoothing_sigmas=None):
     """mat (N, 3, 4), the argument ops.affine_grid takes, such that apply_mat(moving, mat) lines up with fixed (both
     (N, 1, D, H, W) float32 on the GPU, of one shape) under mutual information; transform = "translation" | "rigid" | "affine",
     spacing = voxel size in (z, y, x) order.
@@ -108,6 +108,10 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
     below, built once per level; the intensity ranges stay those of the whole level volumes.  A sample whose level mask is empty
     does not move at that level.
 
+    smoothing_sigmas: None, "auto" or one Gaussian sigma per entry of `shrink` (full-resolution voxels), as
+    estimate_translation takes it: the level pair is smoothed before it is resized, and the intensity ranges are those of the
+    smoothed level pair.  The masks' pyramids do not change.
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     from .centering import _centroid
@@ -119,6 +123,7 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
     spacing = tuple(float(s) for s in spacing)
     if len(spacing) != 3 or min(spacing) <= 0:
         raise ValueError(f"register_intensity: spacing must be three positive numbers, got {spacing}")
+    resolve_smoothing("register_intensity", shrink, smoothing_sigmas)
     dims = tuple(fixed.shape[2:])
     with torch.inference_mode(False), torch.enable_grad():
         fixed, moving = as_data(fixed), as_data(moving)
@@ -134,7 +139,8 @@ def register_intensity(fixed, moving, transform="rigid", bins=32, shrink=(4, 2, 
                 for mask in (fixed_mask, moving_mask):
                     if mask is not None:
                         t = torch.where((mask != 0).flatten(1).any(1, keepdim=True), t, torch.zeros_like(t))
-            for (ldims, f_l, m_l, ratio), fm_l, mm_l in zip(levels(fixed, moving, shrink), fmasks, mmasks):
+            pairs = levels(fixed, moving, shrink, smoothing_sigmas, "register_intensity")
+            for (ldims, f_l, m_l, ratio), fm_l, mm_l in zip(pairs, fmasks, mmasks):
                 sp = [s * r for s, r in zip(spacing, ratio)]
                 h = max(s * (n - 1) / 2 for s, n in zip(sp, ldims)) / min(sp)
                 pyramid.append((ldims, f_l, m_l, ops.mi_ranges(m_l, f_l, bins), ratio, sp, h, fm_l, mm_l))

@@ -41,7 +41,8 @@ def apply_svf(x, ctrl, mat=None, steps=6, inverse=False, mode="bilinear"):
 
 
 def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps=6, bins=32, shrink=(4, 2, 1), iters=60, lr=0.1,
-                 metric="mi", window=9, mind_radius=1, mind_dilation=2, fixed_mask=None, moving_mask=None, inside=False):
+                 metric="mi", window=9, mind_radius=1, mind_dilation=2, fixed_mask=None, moving_mask=None, inside=False,
+                 smoothing_sigmas=None):
     """ctrl (N, 3, Cz, Cy, Cx), a lattice of velocities on ops.bspline_lattice_shape(dims, control_spacing), such that
     apply_svf(moving, ctrl, mat, steps) lines up with fixed (both (N, 1, D, H, W) float32 on the GPU, of one shape).  This is
     register_bspline's schedule with ops.svf_grid(., steps) in place of ops.bspline_grid: the same pyramid, per-level units (the
@@ -54,10 +55,13 @@ def register_svf(fixed, moving, mat=None, control_spacing=8, bending=0.05, steps
     (|grid| <= 1), of the step's own grid, and the similarity is ops.mutual_information(..., mask=that set).  They work with
     metric="mi" only: with "lncc" or "mind" any of them raises ValueError (masked local metrics do not exist here).
 
+    smoothing_sigmas: register_bspline's (None, "auto" or one Gaussian sigma per entry of `shrink`).
+
     Nothing inside the loop waits for the GPU."""
     from .. import ops
     table = metric_table("register_svf", metric, bins, window, mind_radius, mind_dilation)
     if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= ops.SVF_MAX_STEPS:
         raise ValueError(f"register_svf: steps must be an integer in 0 .. {ops.SVF_MAX_STEPS}, got {steps!r}")
     return fit_lattice("register_svf", fixed, moving, mat, lambda ctrl_l, ldims, mat_l: ops.svf_grid(ctrl_l, ldims, steps, mat_l),
-                       table, control_spacing, bending, bins, shrink, iters, lr, fixed_mask, moving_mask, inside, metric)
+                       table, control_spacing, bending, bins, shrink, iters, lr, fixed_mask, moving_mask, inside, metric,
+                       smoothing_sigmas)

@@ -375,12 +375,15 @@ class IntensityRegistration(nn.Module):
     "svf": the diffeomorphism of io.register_svf (the same lattice, schedule, metric and constructor arguments as "bspline", read
     as velocities and exponentiated in svf_steps squarings) on top of the affine answer; its entry is the "bspline" one with
     "grid" = ops.svf_grid(ctrl, dims, svf_steps, matrix) and, in addition, "inverse_grid" = io.svf_grid(ctrl, dims, matrix,
-    svf_steps, inverse=True), the grid that resamples a fixed-space volume into moving space."""
+    svf_steps, inverse=True), the grid that resamples a fixed-space volume into moving space.
+    smoothing_sigmas (constructor): None, "auto" or one Gaussian sigma per level of the pyramid the call builds (ValueError
+    otherwise), handed to every driver: each level is smoothed at the full size before it is resized (io.estimate_translation
+    says why)."""
 
     supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf")
 
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
-                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2, inside=False):
+                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2, inside=False, smoothing_sigmas=None):
         super().__init__()
         from .io._deformable import metric_table
         metric_table("IntensityRegistration", metric)                          # refuses an unknown name
@@ -390,11 +393,19 @@ class IntensityRegistration(nn.Module):
         self.svf_steps = svf_steps
         self.mind_radius, self.mind_dilation = mind_radius, mind_dilation
         self.inside = bool(inside)
+        if smoothing_sigmas is not None and not isinstance(smoothing_sigmas, str):
+            try:
+                smoothing_sigmas = tuple(smoothing_sigmas)                     # its length is checked against the pyramid in forward
+            except TypeError:
+                raise ValueError("IntensityRegistration: smoothing_sigmas must be None, 'auto' or one entry per pyramid level, got "
+                                 f"{smoothing_sigmas!r}") from None
+        self.smoothing_sigmas = smoothing_sigmas
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, mask_f=None, mask_m=None,
                 **kwargs):
         from . import ops
         from .io._deformable import counted_voxels, metric_table
+        from .io._pyramid import resolve_smoothing
         from .io.bspline import register_bspline
         from .io.intensity import register_intensity
         from .io.svf import register_svf, svf_grid
@@ -407,6 +418,8 @@ class IntensityRegistration(nn.Module):
         shrink = (4, 2, 1)
         if num_resolutions_for_itkelastix is not None:
             shrink = tuple(2 ** k for k in range(int(num_resolutions_for_itkelastix) - 1, -1, -1))
+        resolve_smoothing("IntensityRegistration", shrink, self.smoothing_sigmas)
+        smooth = {"smoothing_sigmas": self.smoothing_sigmas}
         k = self.svf_steps
         # the deformable stages, a lattice on top of the affine answer: (driver, grid(ctrl, dims, mat), inverse grid likewise or None)
         lattices = {"bspline": (register_bspline, ops.bspline_grid, None),
@@ -421,12 +434,12 @@ class IntensityRegistration(nn.Module):
             start_time = time.time()
             deformable = lattices.get(align_type_str)
             mat = register_intensity(img_f, img_m, "affine" if deformable else align_type_str, bins=self.bins, shrink=shrink,
-                                     iters=self.iters, lr=self.lr, **masks)
+                                     iters=self.iters, lr=self.lr, **masks, **smooth)
             if deformable:
                 driver, grid_of, inverse_of = deformable
                 ctrl = driver(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending, bins=self.bins,
                               shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,
-                              mind_radius=self.mind_radius, mind_dilation=self.mind_dilation, **masks)
+                              mind_radius=self.mind_radius, mind_dilation=self.mind_dilation, **masks, **smooth)
                 with torch.no_grad():
                     grid = grid_of(ctrl, img_f.shape[2:], mat)
                     warped = align_img(grid, img_m)

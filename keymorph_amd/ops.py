@@ -6,6 +6,9 @@ eager/PyTorch fallback -- a CPU tensor or a missing library raises.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
+import math
 import os
 
 from typing import Optional, Sequence, Tuple
@@ -235,6 +238,131 @@ def cubic_sample(coef: Tensor, grid: Tensor) -> Tensor:
     "nearest".  Differentiable in grid only; a coef that requires a gradient raises NotImplementedError in backward."""
     _cubic_check("cubic_sample", coef, grid)
     return _CubicSample.apply(coef, grid)
+
+
+# Gaussian smoothing (csrc/gauss.hip): the limits of its kernels
+GAUSS_MAX_RADIUS = 32          # taps on either side of the centre (sigma <= 8 at truncate = 4)
+GAUSS_MAX_PLANE = 1 << 29      # voxels of one channel plane
+GAUSS_MAX_PLANES = 65535       # N * C (gridDim.y)
+
+
+def _gauss_sigmas(who: str, sigma, truncate) -> Tuple[float, float, float]:
+    """sigma, a number or a (z, y, x) triple, as three finite floats >= 0, and truncate finite and > 0, or ValueError"""
+    if isinstance(sigma, (int, float)) and not isinstance(sigma, bool):
+        sigma = (sigma,) * 3
+    try:
+        s = tuple(float(v) for v in sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: sigma must be a number or a (z, y, x) triple of numbers, got {sigma!r}") from None
+    if len(s) != 3 or any(isinstance(v, bool) for v in sigma) or not all(math.isfinite(v) and v >= 0.0 for v in s):
+        raise ValueError(f"{who}: sigma must be a finite number >= 0 or a (z, y, x) triple of them, got {sigma!r}")
+    if isinstance(truncate, bool) or not isinstance(truncate, (int, float)) or not math.isfinite(truncate) or truncate <= 0:
+        raise ValueError(f"{who}: truncate must be a finite number > 0, got {truncate!r}")
+    return s
+
+
+def gaussian_radius(sigma: float, truncate: float = 4.0) -> int:
+    """R = int(truncate * sigma + 0.5), scipy.ndimage.gaussian_filter's radius: the kernel has the taps k = -R .. R."""
+    return int(float(truncate) * float(sigma) + 0.5)
+
+
+@functools.lru_cache(maxsize=64)
+def _gauss_taps(sigma: float, truncate: float):
+    """(R, the half-kernel w[0 .. R], the tail sums T[i] = sum_{k >= i} w[k]): fp64 lists, w normalised over k = -R .. R in fp64"""
+    R = gaussian_radius(sigma, truncate)
+    if R == 0:
+        return 0, [1.0], [1.0]
+    e = [math.exp(-0.5 * k * k / (sigma * sigma)) for k in range(R + 1)]
+    total = math.fsum(e + e[1:])
+    w = [v / total for v in e]
+    return R, w, [math.fsum(w[i:]) for i in range(R + 1)]
+
+
+@functools.lru_cache(maxsize=64)
+def _gauss_host(sigma: float, truncate: float):
+    """(R, w, T) as host float arrays for the C ABI: rounded to fp32 once, here"""
+    R, w, t = _gauss_taps(sigma, truncate)
+    return R, (ctypes.c_float * (R + 1))(*w), (ctypes.c_float * (R + 1))(*t)
+
+
+def gaussian_kernel1d(sigma: float, truncate: float = 4.0) -> Tensor:
+    """The 2 R + 1 weights gaussian_smooth uses along an axis with this sigma, a float32 tensor on the host: R =
+    int(truncate * sigma + 0.5), w[k] = exp(-k^2 / 2 sigma^2) / sum_k exp(-k^2 / 2 sigma^2) for k = -R .. R, computed and
+    normalised in fp64 and rounded to fp32 once.  sigma = 0 (or any R = 0): the single weight 1."""
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise ValueError(f"gaussian_kernel1d: sigma must be one number, got {sigma!r}")
+    s = _gauss_sigmas("gaussian_kernel1d", sigma, truncate)[0]
+    if float(truncate) * s > GAUSS_MAX_RADIUS:
+        raise ValueError(f"gaussian_kernel1d: truncate * sigma must be at most {GAUSS_MAX_RADIUS} (sigma <= 8 at truncate = 4), got "
+                         f"sigma {sigma} with truncate {truncate}")
+    R, w, _ = _gauss_host(s, float(truncate))
+    half = list(w)
+    return torch.tensor(half[:0:-1] + half, dtype=torch.float32)
+
+
+def _gauss_plan(who: str, x, sigma, truncate):
+    """The checks of gaussian_smooth -> None (nothing to do) or ((rz, ry, rx), [w_z, w_y, w_x], [t_z, t_y, t_x]).
+    KeymorphHipError for a tensor that is not on the GPU, ValueError for the rest -- before anything is allocated."""
+    _need_gpu_f32(who, "x", x)
+    sig = _gauss_sigmas(who, sigma, truncate)
+    if x.dim() != 5 or x.numel() == 0:
+        raise ValueError(f"{who}: expected a non-empty (N, C, D, H, W) volume, got {tuple(x.shape)}")
+    N, C, D, H, W = x.shape
+    radii = tuple(gaussian_radius(s, truncate) for s in sig)
+    if float(truncate) * max(sig) > GAUSS_MAX_RADIUS:              # so R = int(truncate * sigma + 0.5) <= 32 as well
+        raise ValueError(f"{who}: truncate * sigma must be at most {GAUSS_MAX_RADIUS} per axis (sigma <= 8 at truncate = 4), got "
+                         f"sigma {sig} with truncate {truncate}")
+    if D * H * W >= GAUSS_MAX_PLANE or N * C > GAUSS_MAX_PLANES:
+        raise ValueError(f"{who}: a channel plane must have fewer than 2^29 voxels and N * C be at most {GAUSS_MAX_PLANES}, got "
+                         f"{tuple(x.shape)}")
+    if max(radii) == 0:
+        return None
+    host = [_gauss_host(s, float(truncate)) for s in sig]
+    return radii, [h[1] for h in host], [h[2] for h in host]
+
+
+def _gauss_call(x: Tensor, plan, transpose: bool) -> Tensor:
+    lib = _lib.load()
+    radii, w, t = plan
+    N, C, D, H, W = x.shape
+    out = torch.empty_like(x)
+    nbytes = int(lib.kmh_gauss_ws_bytes(N, C, D, H, W, *radii))
+    ws = workspace(nbytes, x.device, "gauss") if nbytes else None
+    if _lib.profiler.enabled:  # every active axis reads and writes each voxel once
+        _lib.profiler.meta = {"bytes": 8.0 * x.numel() * sum(1 for r in radii if r)}
+    host = [ctypes.addressof(a) for a in w]
+    if transpose:
+        check(lib.kmh_gauss_bwd(_p(x), _p(out), _p(ws), N, C, D, H, W, *radii, *host, *[ctypes.addressof(a) for a in t],
+                                _stream()), "kmh_gauss_bwd")
+    else:
+        check(lib.kmh_gauss_fwd(_p(x), _p(out), _p(ws), N, C, D, H, W, *radii, *host, _stream()), "kmh_gauss_fwd")
+    return out
+
+
+class _GaussianSmooth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return _gauss_call(x.contiguous(), plan, False)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _gauss_call(_prep(gout, "gout"), ctx.plan, True), None
+
+
+def gaussian_smooth(x: Tensor, sigma, truncate: float = 4.0) -> Tensor:
+    """x (N, C, D, H, W) float32 on the GPU smoothed by a Gaussian of `sigma` voxels, a number or a (z, y, x) triple:
+    scipy.ndimage.gaussian_filter(x, sigma, mode="nearest", truncate=truncate) on the three spatial axes.  Per axis with
+    R = int(truncate * sigma + 0.5) > 0:  out[i] = sum_{k=-R..R} w[k] x[clamp(i + k, 0, n - 1)]  with gaussian_kernel1d's weights,
+    along W, then H, then D; an axis with R = 0 is not touched, and when that is every axis the result is x itself (no copy).
+    Differentiable in x: the backward is the exact transpose, a gather without atomics.  Runs repeat bit for bit and a batch
+    equals its samples.  ValueError: sigma negative or not finite, truncate * sigma > 32 on an axis (sigma <= 8 at truncate = 4;
+    the kernels hold at most 32 taps on either side of the centre), a channel
+    plane of 2^29 voxels or more, N * C > 65535."""
+    plan = _gauss_plan("gaussian_smooth", x, sigma, truncate)
+    if plan is None:
+        return x
+    return _GaussianSmooth.apply(x, plan)
 
 
 class _WarpMSE(torch.autograd.Function):
