@@ -699,6 +699,25 @@ int kmh_gauss_bwd(const float* gout, float* dx, void* ws, int N, int C, int D, i
                   const float* wz, const float* wy, const float* wx, const float* tz, const float* ty, const float* tx,
                   void* stream);
 
+/* ---- label maps through a grid by trilinear vote (csrc/label_warp.hip states the definition) ----
+ * lab (N,C,D,H,W): integer label maps, every channel a map of its own, of elem_bytes 1 (is_signed 0: uint8, bool) or 2 / 4 / 8
+ * (is_signed 1); grid (N,Do,Ho,Wo,3) in the convention of kmh_grid_sample3d_fwd.  out (N,C,Do,Ho,Wo), same element type: per
+ * voxel the label l with the largest S_l = the bilinear sample of the channel [lab == l] (same corners, same fma chain, so
+ * out = argmax over the one-hot channels of kmh_grid_sample3d_fwd bit for bit), the smallest such label on a tie; weight (same
+ * shape, float32, or NULL) = that S_l.  One launch, no atomics.  -22 for a null pointer, an empty shape, another element type,
+ * a channel plane of 2^29 voxels or more or N C > 65535. */
+int kmh_warp_labels(const void* lab, int elem_bytes, int is_signed, const float* grid, void* out, float* weight, int N, int C,
+                    int D, int H, int W, int Do, int Ho, int Wo, void* stream);
+
+/* ---- Dice on integer label maps (csrc/label_dice.hip; element types as kmh_warp_labels) ----
+ * kmh_label_presence_int: kmh_label_presence for the four widths; flags (nflags + 1 ints) is only ever set, so several maps can
+ * share it.  kmh_label_pair_counts: counts (3 * nlab uint64, zeroed by the caller) = {|x = l|, |y = l|, |x = l and y = l|} over
+ * the n ids of x and y, l = slot_of[id] for ids in [0, nids); an id outside the table or a slot >= nlab is not counted;
+ * nlab <= 4096. */
+int kmh_label_presence_int(const void* seg, int elem_bytes, int is_signed, long long n, int nflags, int* flags, void* stream);
+int kmh_label_pair_counts(const void* x, const void* y, int elem_bytes, int is_signed, long long n,
+                          const unsigned short* slot_of, int nids, int nlab, unsigned long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

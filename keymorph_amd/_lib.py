@@ -198,6 +198,9 @@ PROTOS = {
     "kmh_gauss_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "kmh_gauss_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
     "kmh_gauss_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "kmh_warp_labels": (_i, [_f, _i, _i, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "kmh_label_presence_int": (_i, [_f, _i, _i, _ll, _i, _f, _f]),
+    "kmh_label_pair_counts": (_i, [_f, _f, _i, _i, _ll, _f, _i, _i, _f, _f]),
 }
 
 _lib = None

@@ -9,15 +9,16 @@ from ._pyramid import levels, resolve_smoothing, scale_axes
 
 def translate(x, t, mode="bilinear"):
     """x (N, C, D, H, W) shifted by t (N, 3) voxels in (z, y, x) order: out[v] = x[v + t], border values outside; differentiable in
-    t (and in x for "bilinear"; "cubic" is the cubic B-spline of ops.cubic_sample, for the image that is kept).  A pure voxel shift
+    t (and in x for "bilinear"; "cubic" is the cubic B-spline of ops.cubic_sample, for the image that is kept; "label" is
+    ops.warp_labels on an integer label map, no gradient).  A pure voxel shift
     through ops.affine_grid and align_img: the matrix diag((n - 1) / n) cancels the linspace(-1, 1) base grid against
     align_corners=False sampling (a translation alone would also zoom by (n - 1) / n), and the offsets are 2 t / n."""
     from .. import ops
     from ..utils import align_img
     if x.dim() != 5 or t.dim() != 2 or tuple(t.shape) != (x.shape[0], 3):
         raise ValueError(f"translate: expected x (N, C, D, H, W) and t (N, 3), got {tuple(x.shape)} and {tuple(t.shape)}")
-    if mode not in ("bilinear", "nearest", "cubic"):
-        raise ValueError(f"translate: mode must be 'bilinear', 'nearest' or 'cubic', got {mode!r}")
+    if mode not in ("bilinear", "nearest", "cubic", "label"):
+        raise ValueError(f"translate: mode must be 'bilinear', 'nearest', 'cubic' or 'label', got {mode!r}")
     # the matrix from Python scalars only (scale_axes says why): this runs on every step of estimate_translation's loop
     t = t.float()
     lin = t.new_zeros((x.shape[0], 3, 3))

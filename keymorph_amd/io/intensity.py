@@ -75,7 +75,7 @@ def rigid_params_to_voxel(omega, t, spacing=(1.0, 1.0, 1.0)):
 
 def apply_mat(x, mat, mode="bilinear"):
     """align_img(ops.affine_grid(mat, dims), x, mode): x (N, C, D, H, W) resampled through the (N, 3, 4) matrix; mode "bilinear",
-    "nearest" or "cubic" (align_img)."""
+    "nearest", "cubic" or, for an integer label map, "label" (align_img)."""
     from .. import ops
     from ..utils import align_img
     return align_img(ops.affine_grid(mat, x.shape[2:]), x, mode)

@@ -246,6 +246,73 @@ def fast_dice(x, y):
     return float(np.mean(dice_score))
 
 
+def _label_map(x, fn):
+    """An integer label map (tensor or ndarray) on the GPU, contiguous, in one of kmh_warp_labels' element types; an unsigned
+    numpy array wider than a byte goes to the next wider signed type first, so that its ids keep their values."""
+    if isinstance(x, np.ndarray) and x.dtype.kind == "u" and x.dtype.itemsize in (2, 4):
+        x = x.astype(np.dtype(f"int{16 * x.dtype.itemsize}"))
+    t = _on_gpu(x, fn)
+    if t.dtype == torch.int8:
+        t = t.to(torch.int16)
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise TypeError(f"{fn}: expected integer label maps (uint8, bool, int16, int32 or int64), got {t.dtype}")
+    return t.contiguous()
+
+
+def _dice_per_label(cx, cy, cxy):
+    """fast_dice's arithmetic (keymorph/loss_ops.py:96-106) on the counts of the labels present in either map, in ascending
+    label order: 2 |x = l and y = l| / (|y = l| + |x = l| + 1e-5) per label; a single label goes through _dice_from_counts."""
+    if len(cx) > 1:
+        hx, hy, diag = (np.asarray(c).astype(np.float64) for c in (cx, cy, cxy))
+        return 2 * diag / (hy + hx + 1e-5)
+    return np.array([_dice_from_counts(cx[0], cy[0], cxy[0])], dtype=np.float64)
+
+
+def label_dice(x, y, return_per_label=False):
+    """fast_dice on two integer label maps themselves: the mean over the labels present in either map of
+    2 |x = l and y = l| / (|x = l| + |y = l| + 1e-5), pooled over the whole of both maps; a Python float equal to
+    fast_dice(one_hot(x), one_hot(y)) where that can be built.  x, y: tensors or numpy arrays of one shape, uint8, bool, int16,
+    int32 or int64, ids in [0, 65536) and at most 4096 distinct ids in the two maps together (ValueError otherwise).  Two passes
+    over the maps on the GPU (which ids occur; their counts), no one-hot tensor: label_dice(ops.warp_labels(seg_m, grid), seg_f)
+    scores a FreeSurfer-sized map.  return_per_label: (value, labels, dice), the ids (int64) and their Dice (float64) as numpy
+    arrays."""
+    from . import _lib
+    from .ops import LABEL_DTYPES, _p, _stream, check
+    from .utils import _MAX_LABEL
+    fn = "label_dice"
+    tx, ty = _label_map(x, fn), _label_map(y, fn)
+    if tx.shape != ty.shape:
+        raise ValueError(f"{fn}: shapes differ: {tuple(tx.shape)} vs {tuple(ty.shape)}")
+    if tx.numel() == 0:
+        raise ValueError(f"{fn}: the label maps are empty")
+    if tx.dtype != ty.dtype:
+        tx, ty = tx.to(torch.int64), ty.to(torch.int64)
+    nbytes, signed = LABEL_DTYPES[tx.dtype]
+    lib, n = _lib.load(), tx.numel()
+    flags = torch.zeros(_MAX_LABEL + 1, dtype=torch.int32, device=tx.device)
+    for t in (tx, ty):
+        check(lib.kmh_label_presence_int(_p(t), nbytes, signed, n, _MAX_LABEL, _p(flags), _stream()), "kmh_label_presence_int")
+    flags = flags.cpu().numpy()
+    if flags[_MAX_LABEL]:
+        raise ValueError(f"{fn}: label ids must lie in [0, {_MAX_LABEL})")
+    labels = np.nonzero(flags[:_MAX_LABEL])[0].astype(np.int64)
+    nlab = len(labels)
+    if nlab > 4096:
+        raise ValueError(f"{fn}: {nlab} distinct labels in the two maps, at most 4096 are counted")
+    slot_of = np.full(_MAX_LABEL, 0xFFFF, dtype=np.uint16)
+    slot_of[labels] = np.arange(nlab, dtype=np.uint16)
+    slot_of = torch.from_numpy(slot_of.view(np.int16)).to(tx.device)
+    counts = torch.zeros(3 * nlab, dtype=torch.int64, device=tx.device)
+    check(lib.kmh_label_pair_counts(_p(tx), _p(ty), nbytes, signed, n, _p(slot_of), _MAX_LABEL, nlab, _p(counts), _stream()),
+          "kmh_label_pair_counts")
+    cx, cy, cxy = counts.cpu().numpy().reshape(3, nlab)
+    per_label = _dice_per_label(cx, cy, cxy)
+    value = float(np.mean(per_label))
+    return (value, labels, per_label) if return_per_label else value
+
+
 def dice(x, y):
     """2 * sum(x * y) / (sum(x) + sum(y)) of two 0/1 arrays or tensors (keymorph/loss_ops.py:109-111), counted on the GPU;
     a Python float (nan for two empty inputs)."""

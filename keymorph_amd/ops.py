@@ -134,10 +134,61 @@ class _GridSample3d(torch.autograd.Function):
 
 
 def grid_sample3d(x: Tensor, grid: Tensor, mode: str = "bilinear") -> Tensor:
-    """mode "cubic": cubic_sample(cubic_coefficients(x), grid), differentiable in the grid only."""
+    """mode "cubic": cubic_sample(cubic_coefficients(x), grid), differentiable in the grid only.  mode "label": warp_labels(x,
+    grid), x an integer label map; no gradient."""
     if mode == "cubic":
         return _GridSampleCubic.apply(x, grid)
+    if mode == "label":
+        return warp_labels(x, grid)
     return _GridSample3d.apply(x, grid, {"bilinear": 0, "nearest": 1}[mode])
+
+
+# label maps through a grid by trilinear vote (csrc/label_warp.hip): its element types as (bytes, signed), and its limits
+LABEL_DTYPES = {torch.uint8: (1, 0), torch.bool: (1, 0), torch.int16: (2, 1), torch.int32: (4, 1), torch.int64: (8, 1)}
+LABEL_MAX_PLANE = 1 << 29      # voxels of one channel plane (an int64 plane inside a 32-bit byte range)
+LABEL_MAX_PLANES = 65535       # N * C (gridDim.y)
+
+
+def warp_labels(labels: Tensor, grid: Tensor, return_weight: bool = False):
+    """Integer label maps labels (N, C, D, H, W) -- uint8, bool, int16, int32 or int64 on the current GPU, every channel a map of
+    its own -- resampled at grid (N, Do, Ho, Wo, 3) -> (N, C, Do, Ho, Wo) of the same dtype: per output voxel the label whose
+    one-hot channel align_img's bilinear sampler would give the largest value, the smallest such label on a tie.  For labels in
+    [0, L) that is torch.argmax(align_img(grid, one_hot(labels).float()), 1) bit for bit (the same corners, the same float32
+    weights, the same order of additions), in one pass over 8 corner labels per voxel and without the L channels; label ids
+    enter only through == and <, so any ids do (signed order for the signed dtypes, False < True).  return_weight: also the
+    winner's summed weight (float32, the .max(1) of that chain).  Neither output carries a gradient; labels and grid may be part
+    of a graph, which is left alone."""
+    who = "warp_labels"
+    _need_gpu(who, "labels", labels)
+    _need_gpu(who, "grid", grid)
+    if labels.dtype not in LABEL_DTYPES:
+        if labels.dtype.is_floating_point:
+            raise TypeError(f"{who}: labels is {labels.dtype}; pass the integer label map itself (uint8, bool, int16, int32 or "
+                            "int64), not a float copy or a one-hot encoding of it")
+        raise TypeError(f"{who}: labels must be uint8, bool, int16, int32 or int64, got {labels.dtype}")
+    if labels.dim() != 5 or labels.numel() == 0:
+        raise ValueError(f"{who}: expected non-empty (N, C, D, H, W) label maps, got {tuple(labels.shape)}")
+    N, C, D, H, W = labels.shape
+    if D * H * W >= LABEL_MAX_PLANE or N * C > LABEL_MAX_PLANES:
+        raise ValueError(f"{who}: a channel plane must have fewer than 2^29 voxels and N * C be at most {LABEL_MAX_PLANES}, got "
+                         f"{tuple(labels.shape)}")
+    if grid.dim() != 5 or grid.shape[0] != N or grid.shape[4] != 3 or grid.numel() == 0:
+        raise ValueError(f"{who}: expected a non-empty grid ({N}, Do, Ho, Wo, 3), got {tuple(grid.shape)}")
+    nbytes, signed = LABEL_DTYPES[labels.dtype]
+    lab = labels.detach().contiguous()
+    if lab.dtype == torch.bool:
+        lab = lab.view(torch.uint8)
+    grid = _prep(grid.detach(), "grid")
+    _, Do, Ho, Wo, _ = grid.shape
+    out = torch.empty((N, C, Do, Ho, Wo), dtype=lab.dtype, device=lab.device)
+    weight = torch.empty((N, C, Do, Ho, Wo), dtype=torch.float32, device=lab.device) if return_weight else None
+    if _lib.profiler.enabled:  # grid 12 B, 8 corner labels of which a smooth grid shares all but ~1, one label (+ 4 B) out
+        _lib.profiler.meta = {"bytes": float(N * C * Do * Ho * Wo) * (12 + 2 * nbytes + (4 if return_weight else 0))}
+    check(_lib.load().kmh_warp_labels(_p(lab), nbytes, signed, _p(grid), _p(out), _p(weight), N, C, D, H, W, Do, Ho, Wo,
+                                      _stream()), "kmh_warp_labels")
+    if labels.dtype == torch.bool:
+        out = out.view(torch.bool)
+    return (out, weight) if return_weight else out
 
 
 # cubic B-spline resampling (csrc/cubic.hip): the limits of its kernels

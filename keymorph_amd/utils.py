@@ -20,7 +20,9 @@ def str_or_float(x):
 def align_img(grid, x, mode="bilinear"):
     """F.grid_sample(x, grid, mode, padding_mode='border', align_corners=False): utils.py:14-21.  mode "cubic" (which F.grid_sample
     lacks for volumes) is the cubic B-spline interpolant of ops.cubic_sample: for the image a user keeps, differentiable in the
-    grid only; it overshoots, so label maps stay on "nearest"."""
+    grid only; it overshoots, so label maps stay on "nearest" -- or go through mode "label" (ops.warp_labels): x is then an
+    integer label map and the result, of x's dtype, is argmax over the channels of align_img(grid, one_hot(x)) without the
+    channels."""
     if x.dim() == 4:  # (N,C,H,W) + (N,Ho,Wo,2): a depth-1 volume sampled at z = 0
         g3 = torch.cat([grid, torch.zeros_like(grid[..., :1])], dim=-1).unsqueeze(1)
         return ops.grid_sample3d(x.unsqueeze(2), g3, mode).squeeze(2)
