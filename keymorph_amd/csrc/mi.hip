@@ -28,9 +28,14 @@
 //                     writes MI_n and G.  A sample with s_a = 0 or s_b = 0 (a constant image) gets MI = 0 and G = 0 exactly.
 // mi_bwd_kernel       one lane per voxel: recomputes the taps, gathers the 16 entries of G from LDS, writes da and / or db.
 // mi_*_masked_kernel  the histogram, finalise and backward kernels over the voxels a byte mask counts, with their number M_n in
-//                     V's place (stated above them, behind the unmasked kernels, which they leave as they are).
+//                     V's place.  A voxel is COUNTED iff mask[v] != 0 (mask (N, V) bytes; NULL: every voxel).  Counted voxels add
+//                     their products as above, M_n replaces V in p = h / M_n and in the gradient's 1 / V, and a voxel that is
+//                     not counted gets gradient 0.  M_n is a 64-bit integer on the device (cnt[n], zeroed by the launcher):
+//                     never read by the host.
+// Each masked kernel and its unmasked neighbour share their text (mi_hist_body, mi_finalise, mi_voxel_grads): the kernels differ
+// in their parameter lists, in where the count comes from and in the mask test, so the definition above stands once.
 #include "common.h"
-#include "mi_taps.h"      // the window (taps), the fixed-point format's constants and the workspace's layout: shared with warp_mi.hip
+#include "mi_taps.h"      // ranges, the window (taps), the fixed-point format, the LDS tables' flush, the workspace: shared with warp_mi.hip
 
 namespace {
 constexpr int TPB = 256;
@@ -100,86 +105,114 @@ __global__ void mi_scale_kernel(const unsigned* __restrict__ keys, int N, int B,
   rng[i * 2 + 1] = hi > lo ? (float)(B - 3) / (hi - lo) : 0.f;      // NaN compares false: s = 0
 }
 
-// grid (blocks, N).  The sample's V voxels are R = ceil(V / 64) steps of 64 consecutive voxels, one per lane.  Workgroup blockIdx.x
-// owns steps [blockIdx.x * per, + per), kSteps * kWaves of them per flush interval: wave w takes steps c + w * kSteps .. + kSteps.
-// LDS: kWaves tables of B * B.
-__global__ __launch_bounds__(TPB) void mi_hist_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      const float* __restrict__ rng, long long V, long long R, long long per,
-                                                      int B, unsigned long long* __restrict__ hist) {
+// The histogram kernels' body.  grid (blocks, N).  The sample's V voxels are R = ceil(V / 64) steps of 64 consecutive voxels, one
+// per lane.  Workgroup blockIdx.x owns steps [blockIdx.x * per, + per), kSteps * kWaves of them per flush interval: wave w takes
+// steps c + w * kSteps .. + kSteps.  LDS: kWaves tables of B * B.
+// MASKED: the interval's mask bytes are loaded first; a lane that is not counted reads voxel 0 (one line for the whole wave)
+// instead of its own, a step without a counted lane skips its taps and its adds, and each wave sums its ballots for the
+// workgroup's count (flush_tables).
+template <bool MASKED>
+__device__ __forceinline__ void mi_hist_body(const float* __restrict__ a, const float* __restrict__ b,
+                                             const unsigned char* __restrict__ mask, const float* __restrict__ rng, long long V,
+                                             long long R, long long per, int B, unsigned long long* __restrict__ hist,
+                                             unsigned long long* __restrict__ cnt) {
   extern __shared__ unsigned tab[];
   const int n = blockIdx.y, BB = B * B, lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  const Range r = load_range(rng, n);
   const long long beg = per * blockIdx.x;
   long long end = beg + per;
   if (end > R) end = R;
   a += (long long)n * V;
   b += (long long)n * V;
+  if (MASKED && mask) mask += (long long)n * V;
   hist += (long long)n * BB;
-  for (int e = threadIdx.x; e < kWaves * BB; e += TPB) tab[e] = 0u;
-  __syncthreads();
+  if (MASKED) cnt += n;
+  zero_tables<kWaves>(tab, BB);
   unsigned* mine = tab + wid * BB;
   for (long long c = beg; c < end; c += kSteps * kWaves) {
     // the interval's 2 * kSteps loads first, all in flight together (an unused slot reads voxel 0)
     float xa[kSteps], xb[kSteps];
     unsigned live = 0u;
+    if constexpr (MASKED) {
+#pragma unroll
+      for (int it = 0; it < kSteps; ++it) {
+        const long long j = c + wid * kSteps + it, v = j * kWave + lane;
+        const bool in = j < end && v < V;
+        const bool counted = in && (mask ? mask[in ? v : 0] != 0 : true);
+        live |= (counted ? 1u : 0u) << it;
+      }
+    }
 #pragma unroll
     for (int it = 0; it < kSteps; ++it) {
       const long long j = c + wid * kSteps + it, v = j * kWave + lane;
-      const bool valid = j < end && v < V;
-      live |= (valid ? 1u : 0u) << it;
+      const bool valid = MASKED ? (live >> it) & 1u : j < end && v < V;
+      if (!MASKED) live |= (valid ? 1u : 0u) << it;
       xa[it] = a[valid ? v : 0];
       xb[it] = b[valid ? v : 0];
     }
+    unsigned counted_here = 0u;                                       // wave-uniform
 #pragma unroll
     for (int it = 0; it < kSteps; ++it) {
       const bool valid = (live >> it) & 1u;
       if (!__any(valid)) continue;                                    // wave-uniform
-      // hist_add's text (mi_taps.h), kept inline: as a call this kernel is rescheduled and measured slower (mi_taps.h has the figures)
-      unsigned q[16];
-      int key = -1;
-      if (valid) {
-        const Taps ta = taps<false>(xa[it], lo_a, s_a, B), tb = taps<false>(xb[it], lo_b, s_b, B);
-        key = ta.k0 * B + tb.k0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) q[i * 4 + k] = (unsigned)__float2int_rn(ta.w[i] * tb.w[k] * (float)(1 << kFrac));
+      if constexpr (MASKED) {
+        counted_here += (unsigned)__popcll(__ballot(valid));
+        hist_add(valid, xa[it], xb[it], r, B, lane, mine);
       } else {
+        // hist_add's text, kept inline in the unmasked kernel: as a call it is rescheduled and measured slower (mi_taps.h has
+        // the figures).  The masked kernel calls it: with this text it measured slower under a mask of ones (MI355X,
+        // tools/bench_masked_mi.py, medians of 30 calls in ms, separate processes in the order call, inline, call, inline:
+        // 128^3 0.1596 0.1599 0.1597 0.1597, 256^3 0.5768 0.5853 0.5775 0.5856; profiles/mi_dedup_kernel_identity.md).
+        unsigned q[16];
+        int key = -1;
+        if (valid) {
+          const Taps ta = taps<false>(xa[it], r.lo_a, r.s_a, B), tb = taps<false>(xb[it], r.lo_b, r.s_b, B);
+          key = ta.k0 * B + tb.k0;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) q[i] = 0u;
-      }
-      const int first = __shfl(key, __ffsll((long long)__ballot(valid)) - 1, kWave);
-      if (__all(!valid || key == first)) {
-        // one window for the whole wave: 64 lanes * rint(2^23 * 4/9) < 2^28 per sum
+          for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const unsigned sum = wave_usum(q[i]);
-          if (lane == 0 && sum) atomicAdd(mine + first + (i >> 2) * B + (i & 3), sum);
+            for (int k = 0; k < 4; ++k) q[i * 4 + k] = (unsigned)__float2int_rn(ta.w[i] * tb.w[k] * (float)(1 << kFrac));
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) q[i] = 0u;
         }
-      } else if (valid) {
+        const int first = __shfl(key, __ffsll((long long)__ballot(valid)) - 1, kWave);
+        if (__all(!valid || key == first)) {
+          // one window for the whole wave: 64 lanes * rint(2^23 * 4/9) < 2^28 per sum
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (q[i]) atomicAdd(mine + key + (i >> 2) * B + (i & 3), q[i]);
+          for (int i = 0; i < 16; ++i) {
+            const unsigned sum = wave_usum(q[i]);
+            if (lane == 0 && sum) atomicAdd(mine + first + (i >> 2) * B + (i & 3), sum);
+          }
+        } else if (valid) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (q[i]) atomicAdd(mine + key + (i >> 2) * B + (i & 3), q[i]);
+        }
       }
     }
-    __syncthreads();
-    for (int e = threadIdx.x; e < BB; e += TPB) {
-      unsigned long long sum = 0ull;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) {
-        sum += tab[w * BB + e];
-        tab[w * BB + e] = 0u;
-      }
-      if (sum) atomicAdd(hist + e, sum);
-    }
-    __syncthreads();
+    flush_tables<kWaves, MASKED>(tab, BB, hist, counted_here, cnt);
   }
 }
 
-// one workgroup per sample; LDS: B * B doubles (p) + 2 B doubles (pa, pb)
-__global__ __launch_bounds__(TPB) void mi_final_kernel(const unsigned long long* __restrict__ hist,
-                                                       const float* __restrict__ rng, long long V, int B,
-                                                       float* __restrict__ mi, float* __restrict__ G) {
+__global__ __launch_bounds__(TPB) void mi_hist_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                      const float* __restrict__ rng, long long V, long long R, long long per,
+                                                      int B, unsigned long long* __restrict__ hist) {
+  mi_hist_body<false>(a, b, nullptr, rng, V, R, per, B, hist, nullptr);
+}
+__global__ __launch_bounds__(TPB) void mi_hist_masked_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                             const unsigned char* __restrict__ mask,
+                                                             const float* __restrict__ rng, long long V, long long R,
+                                                             long long per, int B, unsigned long long* __restrict__ hist,
+                                                             unsigned long long* __restrict__ cnt) {
+  mi_hist_body<true>(a, b, mask, rng, V, R, per, B, hist, cnt);
+}
+
+// The finalise kernels' body: one workgroup per sample, M = the number of voxels its table `hist` counted.  A sample that
+// counted nothing or has a constant image (s = 0: independent) gets MI = 0 and G = 0 exactly.
+// LDS: B * B doubles (p) + 2 B doubles (pa, pb)
+__device__ __forceinline__ void mi_finalise(const unsigned long long* __restrict__ hist, const float* __restrict__ rng, long long M,
+                                            int B, float* __restrict__ mi, float* __restrict__ G) {
   extern __shared__ double fin[];
   __shared__ double scratch[kWaves];
   const int n = blockIdx.x, BB = B * B;
@@ -187,12 +220,12 @@ __global__ __launch_bounds__(TPB) void mi_final_kernel(const unsigned long long*
   double* pb = pa + B;
   hist += (long long)n * BB;
   G += (long long)n * BB;
-  if (rng[n * 4 + 1] == 0.f || rng[n * 4 + 3] == 0.f) {             // a constant image: independent, exactly
+  if (M == 0 || rng[n * 4 + 1] == 0.f || rng[n * 4 + 3] == 0.f) {
     for (int e = threadIdx.x; e < BB; e += TPB) G[e] = 0.f;
     if (threadIdx.x == 0) mi[n] = 0.f;
     return;
   }
-  const double unit = 1.0 / ((double)(1 << kFrac) * (double)V);
+  const double unit = 1.0 / ((double)(1 << kFrac) * (double)M);
   for (int e = threadIdx.x; e < BB; e += TPB) fin[e] = (double)hist[e] * unit;
   if (threadIdx.x < 2 * B) {                                          // marginals: integer sums, exact in any order
     const int k = threadIdx.x % B, col = threadIdx.x / B;
@@ -213,6 +246,39 @@ __global__ __launch_bounds__(TPB) void mi_final_kernel(const unsigned long long*
   }
   acc = block_sum(acc, scratch);
   if (threadIdx.x == 0) mi[n] = (float)acc;
+}
+
+__global__ __launch_bounds__(TPB) void mi_final_kernel(const unsigned long long* __restrict__ hist,
+                                                       const float* __restrict__ rng, long long V, int B,
+                                                       float* __restrict__ mi, float* __restrict__ G) {
+  mi_finalise(hist, rng, V, B, mi, G);                                // the launcher has V >= 1
+}
+__global__ __launch_bounds__(TPB) void mi_final_masked_kernel(const unsigned long long* __restrict__ hist,
+                                                              const float* __restrict__ rng,
+                                                              const unsigned long long* __restrict__ cnt, int B,
+                                                              float* __restrict__ mi, float* __restrict__ G) {
+  mi_finalise(hist, rng, (long long)cnt[blockIdx.x], B, mi, G);
+}
+
+// The backward kernels' per-voxel gradient: (ga, gb) = sum_ij G_ij (w_a'[i] w_b[j], w_a[i] w_b'[j]) at the pair (xa, xb), G of the
+// sample in LDS (g).  The kernels scale them by gout s / (the number of counted voxels).
+__device__ __forceinline__ void mi_voxel_grads(float xa, float xb, const Range& r, int B, const float* g, float& ga, float& gb) {
+  const Taps ta = taps<true>(xa, r.lo_a, r.s_a, B), tb = taps<true>(xb, r.lo_b, r.s_b, B);
+  const float* row = g + ta.k0 * B + tb.k0;
+  ga = 0.f;
+  gb = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float rw = 0.f, rd = 0.f;                                        // sum_j G_ij w_b[j], sum_j G_ij w_b'[j]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gij = row[i * B + j];
+      rw = fmaf(gij, tb.w[j], rw);
+      rd = fmaf(gij, tb.d[j], rd);
+    }
+    ga = fmaf(ta.d[i], rw, ga);
+    gb = fmaf(ta.w[i], rd, gb);
+  }
 }
 
 // grid (blocks, N), four voxels per lane; LDS: G of the sample (B * B floats)
@@ -225,150 +291,24 @@ __global__ __launch_bounds__(TPB) void mi_bwd_kernel(const float* __restrict__ a
   const int n = blockIdx.y, BB = B * B;
   for (int e = threadIdx.x; e < BB; e += TPB) g[e] = G[(long long)n * BB + e];
   __syncthreads();
-  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
-  const float go = gout[n] / (float)V, ca = go * s_a, cb = go * s_b;
+  const Range r = load_range(rng, n);
+  const float go = gout[n] / (float)V, ca = go * r.s_a, cb = go * r.s_b;
   const long long off = (long long)n * V;
 #pragma unroll
   for (int it = 0; it < kBwdVpt; ++it) {
     const long long v = ((long long)blockIdx.x * kBwdVpt + it) * TPB + threadIdx.x;
     if (v >= V) return;
-    const Taps ta = taps<true>(a[off + v], lo_a, s_a, B), tb = taps<true>(b[off + v], lo_b, s_b, B);
-    const float* row = g + ta.k0 * B + tb.k0;
-    float ga = 0.f, gb = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float rw = 0.f, rd = 0.f;                                      // sum_j G_ij w_b[j], sum_j G_ij w_b'[j]
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gij = row[i * B + j];
-        rw = fmaf(gij, tb.w[j], rw);
-        rd = fmaf(gij, tb.d[j], rd);
-      }
-      ga = fmaf(ta.d[i], rw, ga);
-      gb = fmaf(ta.w[i], rd, gb);
-    }
+    float ga, gb;
+    mi_voxel_grads(a[off + v], b[off + v], r, B, g, ga, gb);
     if (da) da[off + v] = ca * ga;
     if (db) db[off + v] = cb * gb;
   }
 }
 
-// ---- the masked variants: kernels of their own, so that the ones above keep their machine code (mi_taps.h) -------------------
-// A voxel is COUNTED iff mask[v] != 0 (mask (N, V) bytes; NULL: every voxel).  Counted voxels add their products as above,
-// M_n = their number replaces V in p = h / M_n and in the gradient's 1 / V, and a voxel that is not counted gets gradient 0.
-// M_n is a 64-bit integer on the device (cnt[n], zeroed by the launcher): never read by the host.
-
-// mi_hist_kernel's partition, tables and flush.  The interval's mask bytes are loaded first; a lane that is not counted reads
-// voxel 0 (one line for the whole wave) instead of its own, a step without a counted lane skips its taps and its adds, and a
-// workgroup whose interval counted nothing skips the flush (its tables are still zero).  Each wave sums its ballots; the
-// workgroup adds the interval's count with one integer atomic.
-__global__ __launch_bounds__(TPB) void mi_hist_masked_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                             const unsigned char* __restrict__ mask,
-                                                             const float* __restrict__ rng, long long V, long long R,
-                                                             long long per, int B, unsigned long long* __restrict__ hist,
-                                                             unsigned long long* __restrict__ cnt) {
-  extern __shared__ unsigned tab[];
-  __shared__ unsigned wcnt[kWaves];
-  const int n = blockIdx.y, BB = B * B, lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
-  const long long beg = per * blockIdx.x;
-  long long end = beg + per;
-  if (end > R) end = R;
-  a += (long long)n * V;
-  b += (long long)n * V;
-  if (mask) mask += (long long)n * V;
-  hist += (long long)n * BB;
-  for (int e = threadIdx.x; e < kWaves * BB; e += TPB) tab[e] = 0u;
-  __syncthreads();
-  unsigned* mine = tab + wid * BB;
-  for (long long c = beg; c < end; c += kSteps * kWaves) {
-    unsigned live = 0u;
-#pragma unroll
-    for (int it = 0; it < kSteps; ++it) {
-      const long long j = c + wid * kSteps + it, v = j * kWave + lane;
-      const bool in = j < end && v < V;
-      const bool counted = in && (mask ? mask[in ? v : 0] != 0 : true);
-      live |= (counted ? 1u : 0u) << it;
-    }
-    float xa[kSteps], xb[kSteps];
-#pragma unroll
-    for (int it = 0; it < kSteps; ++it) {
-      const long long v = (c + wid * kSteps + it) * kWave + lane;
-      const bool valid = (live >> it) & 1u;
-      xa[it] = a[valid ? v : 0];
-      xb[it] = b[valid ? v : 0];
-    }
-    unsigned counted_here = 0u;                                       // wave-uniform
-#pragma unroll
-    for (int it = 0; it < kSteps; ++it) {
-      const bool valid = (live >> it) & 1u;
-      const unsigned long long who = __ballot(valid);
-      if (!who) continue;                                             // wave-uniform
-      counted_here += (unsigned)__popcll(who);
-      hist_add(valid, xa[it], xb[it], lo_a, s_a, lo_b, s_b, B, lane, mine);
-    }
-    if (lane == 0) wcnt[wid] = counted_here;
-    __syncthreads();
-    unsigned total = 0u;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) total += wcnt[w];
-    if (total) {                                                      // workgroup-uniform
-      for (int e = threadIdx.x; e < BB; e += TPB) {
-        unsigned long long sum = 0ull;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-          sum += tab[w * BB + e];
-          tab[w * BB + e] = 0u;
-        }
-        if (sum) atomicAdd(hist + e, sum);
-      }
-      if (threadIdx.x == 0) atomicAdd(cnt + n, (unsigned long long)total);
-    }
-    __syncthreads();
-  }
-}
-
-// mi_final_kernel with V = cnt[n]; a sample that counted nothing gets MI = 0 and G = 0 exactly, like a constant image
-__global__ __launch_bounds__(TPB) void mi_final_masked_kernel(const unsigned long long* __restrict__ hist,
-                                                              const float* __restrict__ rng,
-                                                              const unsigned long long* __restrict__ cnt, int B,
-                                                              float* __restrict__ mi, float* __restrict__ G) {
-  extern __shared__ double fin[];
-  __shared__ double scratch[kWaves];
-  const int n = blockIdx.x, BB = B * B;
-  double* pa = fin + BB;
-  double* pb = pa + B;
-  hist += (long long)n * BB;
-  G += (long long)n * BB;
-  const unsigned long long M = cnt[n];
-  if (M == 0ull || rng[n * 4 + 1] == 0.f || rng[n * 4 + 3] == 0.f) {
-    for (int e = threadIdx.x; e < BB; e += TPB) G[e] = 0.f;
-    if (threadIdx.x == 0) mi[n] = 0.f;
-    return;
-  }
-  const double unit = 1.0 / ((double)(1 << kFrac) * (double)(long long)M);
-  for (int e = threadIdx.x; e < BB; e += TPB) fin[e] = (double)hist[e] * unit;
-  if (threadIdx.x < 2 * B) {                                          // marginals: integer sums, exact in any order
-    const int k = threadIdx.x % B, col = threadIdx.x / B;
-    unsigned long long s = 0ull;
-    for (int j = 0; j < B; ++j) s += col ? hist[j * B + k] : hist[k * B + j];
-    (col ? pb : pa)[k] = (double)s * unit;
-  }
-  __syncthreads();
-  double acc = 0.0;
-  for (int e = threadIdx.x; e < BB; e += TPB) {
-    const double p = fin[e];
-    double g = 0.0;
-    if (p > 0.0) {
-      g = log(p / (pa[e / B] * pb[e % B]));
-      acc += p * g;
-    }
-    G[e] = (float)g;
-  }
-  acc = block_sum(acc, scratch);
-  if (threadIdx.x == 0) mi[n] = (float)acc;
-}
-
-// mi_bwd_kernel with 1 / M_n for 1 / V; a voxel that is not counted gets 0
+// mi_bwd_kernel with 1 / M_n for 1 / V; a voxel that is not counted gets 0.  Its own prologue and loop, by measurement: as one
+// body with mi_bwd_kernel (mask NULL there) this kernel came out slower.  MI355X, kmh_mi_bwd_masked under a ball mask, medians of
+// 30 calls in ms, separate processes in the order two loops, one body, two loops, one body
+// (profiles/mi_dedup_kernel_identity.md):  128^3 0.0123 0.0127 0.0123 0.0124   256^3 0.0484 0.0501 0.0477 0.0498
 __global__ __launch_bounds__(TPB) void mi_bwd_masked_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             const unsigned char* __restrict__ mask,
                                                             const float* __restrict__ rng, const float* __restrict__ G,
@@ -379,9 +319,9 @@ __global__ __launch_bounds__(TPB) void mi_bwd_masked_kernel(const float* __restr
   const int n = blockIdx.y, BB = B * B;
   for (int e = threadIdx.x; e < BB; e += TPB) g[e] = G[(long long)n * BB + e];
   __syncthreads();
-  const float lo_a = rng[n * 4], s_a = rng[n * 4 + 1], lo_b = rng[n * 4 + 2], s_b = rng[n * 4 + 3];
+  const Range r = load_range(rng, n);
   const long long M = (long long)cnt[n];
-  const float go = M ? gout[n] / (float)M : 0.f, ca = go * s_a, cb = go * s_b;
+  const float go = M ? gout[n] / (float)M : 0.f, ca = go * r.s_a, cb = go * r.s_b;
   const long long off = (long long)n * V;
 #pragma unroll
   for (int it = 0; it < kBwdVpt; ++it) {
@@ -392,21 +332,8 @@ __global__ __launch_bounds__(TPB) void mi_bwd_masked_kernel(const float* __restr
       if (db) db[off + v] = 0.f;
       continue;
     }
-    const Taps ta = taps<true>(a[off + v], lo_a, s_a, B), tb = taps<true>(b[off + v], lo_b, s_b, B);
-    const float* row = g + ta.k0 * B + tb.k0;
-    float ga = 0.f, gb = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float rw = 0.f, rd = 0.f;                                      // sum_j G_ij w_b[j], sum_j G_ij w_b'[j]
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gij = row[i * B + j];
-        rw = fmaf(gij, tb.w[j], rw);
-        rd = fmaf(gij, tb.d[j], rd);
-      }
-      ga = fmaf(ta.d[i], rw, ga);
-      gb = fmaf(ta.w[i], rd, gb);
-    }
+    float ga, gb;
+    mi_voxel_grads(a[off + v], b[off + v], r, B, g, ga, gb);
     if (da) da[off + v] = ca * ga;
     if (db) db[off + v] = cb * gb;
   }
@@ -414,6 +341,48 @@ __global__ __launch_bounds__(TPB) void mi_bwd_masked_kernel(const float* __restr
 
 bool mi_args_ok(const void* a, const void* b, int N, long long V, int B) {
   return a && b && N >= 1 && N <= 65535 && V >= 1 && V <= (1ll << 40) && B >= kMinBins && B <= kMaxBins;
+}
+
+// The histogram pass: clears the workspace (keys and table; `cleared`: the range stage already has) and the count, then the
+// kernel over hist_steps' partition.  cnt != NULL: the masked kernel.
+hipError_t mi_hist_launch(const float* a, const float* b, const unsigned char* mask, const float* rng, int N, long long V,
+                          int bins, void* ws, bool cleared, long long* cnt, hipStream_t s) {
+  hipError_t e = cleared ? hipSuccess : hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
+  if (e == hipSuccess && cnt) e = hipMemsetAsync(cnt, 0, (size_t)N * sizeof(long long), s);
+  if (e != hipSuccess) return e;
+  const HistSteps p = hist_steps(V, kWaves);
+  const dim3 grid((unsigned)p.nb, (unsigned)N);
+  const size_t lds = (size_t)kWaves * bins * bins * sizeof(unsigned);
+  if (cnt)
+    mi_hist_masked_kernel<<<grid, TPB, lds, s>>>(a, b, mask, rng, V, p.R, p.per, bins, ws_table(ws, N), (unsigned long long*)cnt);
+  else
+    mi_hist_kernel<<<grid, TPB, lds, s>>>(a, b, rng, V, p.R, p.per, bins, ws_table(ws, N));
+  return hipSuccess;
+}
+
+// cnt != NULL: p = h / cnt[n], else p = h / V
+void mi_final_launch(const void* ws, const float* rng, const long long* cnt, int N, long long V, int bins, float* mi, float* G,
+                     hipStream_t s) {
+  const size_t lds = (size_t)(bins * bins + 2 * bins) * sizeof(double);
+  if (cnt)
+    mi_final_masked_kernel<<<N, TPB, lds, s>>>(ws_table(ws, N), rng, (const unsigned long long*)cnt, bins, mi, G);
+  else
+    mi_final_kernel<<<N, TPB, lds, s>>>(ws_table(ws, N), rng, V, bins, mi, G);
+}
+
+// cnt != NULL: the masked kernel, over the voxels `mask` counts
+int mi_bwd_launch(const float* a, const float* b, const unsigned char* mask, const float* rng, const float* G, const float* gout,
+                  const long long* cnt, int N, long long V, int bins, float* da, float* db, hipStream_t s) {
+  if (!da && !db) return 0;
+  const long long nb = (V + TPB * kBwdVpt - 1) / (TPB * kBwdVpt);
+  if (nb > 0x7fffffffll) return -22;
+  const dim3 grid((unsigned)nb, (unsigned)N);
+  const size_t lds = (size_t)bins * bins * sizeof(float);
+  if (cnt)
+    mi_bwd_masked_kernel<<<grid, TPB, lds, s>>>(a, b, mask, rng, G, gout, (const unsigned long long*)cnt, V, bins, da, db);
+  else
+    mi_bwd_kernel<<<grid, TPB, lds, s>>>(a, b, rng, G, gout, V, bins, da, db);
+  return KMH_LAUNCH_CHECK();
 }
 }  // namespace
 
@@ -440,13 +409,6 @@ static hipError_t mi_range_launch(const float* a, const float* b, int N, long lo
   return hipSuccess;
 }
 
-static void mi_hist_launch(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws,
-                           hipStream_t s) {
-  const HistSteps p = hist_steps(V, kWaves);
-  mi_hist_kernel<<<dim3((unsigned)p.nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
-      a, b, rng, V, p.R, p.per, bins, ws_table(ws, N));
-}
-
 /* a, b: (N, V) float32 contiguous.  has_range_x != 0: image x uses the range (lo_x, hi_x) instead of its own minimum and maximum.
  * rng: (N, 4) floats out = (lo_a, s_a, lo_b, s_b).  ws: kmh_mi_ws_bytes(N, bins) bytes, holds the joint table for kmh_mi_final. */
 KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int bins, int has_range_a, float lo_a, float hi_a,
@@ -454,8 +416,8 @@ KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int 
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = mi_range_launch(a, b, N, V, bins, has_range_a, lo_a, hi_a, has_range_b, lo_b, hi_b, ws, ws_bytes(N, bins), rng, s);
+  if (e == hipSuccess) e = mi_hist_launch(a, b, nullptr, rng, N, V, bins, ws, true, nullptr, s);
   if (e != hipSuccess) return (int)e;
-  mi_hist_launch(a, b, rng, N, V, bins, ws, s);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -464,10 +426,8 @@ KMH_API int kmh_mi_hist(const float* a, const float* b, int N, long long V, int 
 KMH_API int kmh_mi_hist_ranges(const float* a, const float* b, const float* rng, int N, long long V, int bins, void* ws,
                                void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng) return -22;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
+  hipError_t e = mi_hist_launch(a, b, nullptr, rng, N, V, bins, ws, false, nullptr, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
-  mi_hist_launch(a, b, rng, N, V, bins, ws, s);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -487,8 +447,7 @@ KMH_API int kmh_mi_range(const float* a, const float* b, int N, long long V, int
  * where p > 0, else 0: what kmh_mi_bwd reads. */
 KMH_API int kmh_mi_final(const void* ws, const float* rng, int N, long long V, int bins, float* mi, float* G, void* stream) {
   if (!mi_args_ok(ws, rng, N, V, bins) || !mi || !G) return -22;
-  mi_final_kernel<<<N, TPB, (size_t)(bins * bins + 2 * bins) * sizeof(double), (hipStream_t)stream>>>(ws_table(ws, N), rng, V, bins,
-                                                                                                      mi, G);
+  mi_final_launch(ws, rng, nullptr, N, V, bins, mi, G, (hipStream_t)stream);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -496,12 +455,7 @@ KMH_API int kmh_mi_final(const void* ws, const float* rng, int N, long long V, i
 KMH_API int kmh_mi_bwd(const float* a, const float* b, const float* rng, const float* G, const float* gout, int N, long long V,
                        int bins, float* da, float* db, void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !rng || !G || !gout) return -22;
-  if (!da && !db) return 0;
-  const long long nb = (V + TPB * kBwdVpt - 1) / (TPB * kBwdVpt);
-  if (nb > 0x7fffffffll) return -22;
-  mi_bwd_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)bins * bins * sizeof(float), (hipStream_t)stream>>>(
-      a, b, rng, G, gout, V, bins, da, db);
-  return KMH_LAUNCH_CHECK();
+  return mi_bwd_launch(a, b, nullptr, rng, G, gout, nullptr, N, V, bins, da, db, (hipStream_t)stream);
 }
 
 /* kmh_mi_hist_ranges over the counted voxels only: mask (N, V) bytes, non-zero = counted, NULL = every voxel.  cnt: N 64-bit
@@ -509,13 +463,8 @@ KMH_API int kmh_mi_bwd(const float* a, const float* b, const float* rng, const f
 KMH_API int kmh_mi_hist_masked(const float* a, const float* b, const unsigned char* mask, const float* rng, int N, long long V,
                                int bins, void* ws, long long* cnt, void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !ws || !rng || !cnt) return -22;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, ws_bytes(N, bins), s);
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)N * sizeof(long long), s);
+  hipError_t e = mi_hist_launch(a, b, mask, rng, N, V, bins, ws, false, cnt, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
-  const HistSteps p = hist_steps(V, kWaves);
-  mi_hist_masked_kernel<<<dim3((unsigned)p.nb, (unsigned)N), TPB, (size_t)kWaves * bins * bins * sizeof(unsigned), s>>>(
-      a, b, mask, rng, V, p.R, p.per, bins, ws_table(ws, N), (unsigned long long*)cnt);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -523,8 +472,7 @@ KMH_API int kmh_mi_hist_masked(const float* a, const float* b, const unsigned ch
 KMH_API int kmh_mi_final_masked(const void* ws, const float* rng, const long long* cnt, int N, int bins, float* mi, float* G,
                                 void* stream) {
   if (!mi_args_ok(ws, rng, N, 1, bins) || !cnt || !mi || !G) return -22;
-  mi_final_masked_kernel<<<N, TPB, (size_t)(bins * bins + 2 * bins) * sizeof(double), (hipStream_t)stream>>>(
-      ws_table(ws, N), rng, (const unsigned long long*)cnt, bins, mi, G);
+  mi_final_launch(ws, rng, cnt, N, 0, bins, mi, G, (hipStream_t)stream);
   return KMH_LAUNCH_CHECK();
 }
 
@@ -533,10 +481,5 @@ KMH_API int kmh_mi_bwd_masked(const float* a, const float* b, const unsigned cha
                               const float* gout, const long long* cnt, int N, long long V, int bins, float* da, float* db,
                               void* stream) {
   if (!mi_args_ok(a, b, N, V, bins) || !rng || !G || !gout || !cnt) return -22;
-  if (!da && !db) return 0;
-  const long long nb = (V + TPB * kBwdVpt - 1) / (TPB * kBwdVpt);
-  if (nb > 0x7fffffffll) return -22;
-  mi_bwd_masked_kernel<<<dim3((unsigned)nb, (unsigned)N), TPB, (size_t)bins * bins * sizeof(float), (hipStream_t)stream>>>(
-      a, b, mask, rng, G, gout, (const unsigned long long*)cnt, V, bins, da, db);
-  return KMH_LAUNCH_CHECK();
+  return mi_bwd_launch(a, b, mask, rng, G, gout, cnt, N, V, bins, da, db, (hipStream_t)stream);
 }

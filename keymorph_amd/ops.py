@@ -1175,54 +1175,71 @@ def _need_bins(who: str, bins) -> int:
     return int(bins)
 
 
-def _mi_final(ws, rng, N, V, bins):
-    """(mi (N,), G (N, bins, bins)) from the joint table a histogram pass (kmh_mi_hist*, kmh_warp_mi_hist) left in ws."""
+def _mi_final(ws, rng, N, V, bins, cnt=None):
+    """(mi (N,), G (N, bins, bins)) from the joint table a histogram pass (kmh_mi_hist*, kmh_warp_mi_hist*) left in ws, with
+    p = h / V, or p = h / cnt[n] for the count (N,) a masked pass left on the device."""
     mi = torch.empty((N,), dtype=torch.float32, device=ws.device)
     G = torch.empty((N, bins, bins), dtype=torch.float32, device=ws.device)
-    check(_lib.load().kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+    if cnt is None:
+        check(_lib.load().kmh_mi_final(_p(ws), _p(rng), N, V, bins, _p(mi), _p(G), _stream()), "kmh_mi_final")
+    else:
+        check(_lib.load().kmh_mi_final_masked(_p(ws), _p(rng), _p(cnt), N, bins, _p(mi), _p(G), _stream()), "kmh_mi_final_masked")
     return mi, G
 
 
-def _mi_forward(a, b, bins, range_a, range_b, ranges=None):
-    """(mi (N,), rng (N, 4), G (N, bins, bins)) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise.
-    ranges: a checked (N, 4) device tensor as mi_ranges returns it, used instead of range_a / range_b."""
+def _mi_forward(a, b, bins, range_a, range_b, ranges=None, mask=None):
+    """(mi (N,), rng (N, 4), G (N, bins, bins), cnt) of two checked (N, 1, D, H, W) tensors: the histogram pass, then the finalise.
+    ranges: a checked (N, 4) device tensor as mi_ranges returns it, used instead of range_a / range_b.  mask: a checked byte mask;
+    only its voxels are counted and cnt (N,) int64 is their number, which stays on the device (cnt is None without a mask).  The
+    ranges are the caller's, or the whole volumes' own: the range stage of kmh_mi_hist on its own (kmh_mi_range), then the masked
+    histogram with the ranges given."""
     lib = _lib.load()
     N, V = a.shape[0], a.numel() // a.shape[0]
     dev = a.device
+    if mask is not None and ranges is None:
+        ranges = _mi_ranges(a, b, bins, range_a, range_b)
     ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=dev)
     rng = torch.empty((N, 4), dtype=torch.float32, device=dev) if ranges is None else ranges
+    cnt = None if mask is None else torch.empty((N,), dtype=torch.int64, device=dev)
     ra, rb = range_a or (0.0, 0.0), range_b or (0.0, 0.0)
-    if _lib.profiler.enabled:  # 8 B read per voxel
-        _lib.profiler.meta = {"bytes": 8.0 * N * V}
-    if ranges is not None:
+    if _lib.profiler.enabled:  # 8 B read per voxel, at most 9 B with a mask
+        _lib.profiler.meta = {"bytes": (8.0 if mask is None else 9.0) * N * V}
+    if mask is not None:
+        check(lib.kmh_mi_hist_masked(_p(a), _p(b), _p(mask), _p(rng), N, V, bins, _p(ws), _p(cnt), _stream()),
+              "kmh_mi_hist_masked")
+    elif ranges is not None:
         check(lib.kmh_mi_hist_ranges(_p(a), _p(b), _p(rng), N, V, bins, _p(ws), _stream()), "kmh_mi_hist_ranges")
     else:
         check(lib.kmh_mi_hist(_p(a), _p(b), N, V, bins, int(range_a is not None), ra[0], ra[1], int(range_b is not None), rb[0],
                               rb[1], _p(ws), _p(rng), _stream()), "kmh_mi_hist")
-    mi, G = _mi_final(ws, rng, N, V, bins)
-    return mi, rng, G
+    mi, G = _mi_final(ws, rng, N, V, bins, cnt)
+    return mi, rng, G, cnt
 
 
 class _MI(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, bins, range_a, range_b, ranges=None):
-        mi, rng, G = _mi_forward(a, b, bins, range_a, range_b, ranges)
-        ctx.save_for_backward(a, b, rng, G)
+    def forward(ctx, a, b, bins, range_a, range_b, ranges=None, mask=None):
+        mi, rng, G, cnt = _mi_forward(a, b, bins, range_a, range_b, ranges, mask)
+        ctx.save_for_backward(a, b, rng, G, mask, cnt)
         ctx.bins = bins
         return mi
 
     @staticmethod
     def backward(ctx, gout):
         lib = _lib.load()
-        a, b, rng, G = ctx.saved_tensors
+        a, b, rng, G, mask, cnt = ctx.saved_tensors
         gout = _prep(gout)
         N, V = a.shape[0], a.numel() // a.shape[0]
         da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        if _lib.profiler.enabled:  # 8 B read and 4 B written per voxel and gradient
-            _lib.profiler.meta = {"bytes": (8.0 + 4.0 * ((da is not None) + (db is not None))) * N * V}
-        check(lib.kmh_mi_bwd(_p(a), _p(b), _p(rng), _p(G), _p(gout), N, V, ctx.bins, _p(da), _p(db), _stream()), "kmh_mi_bwd")
-        return da, db, None, None, None, None
+        if _lib.profiler.enabled:  # 8 B (9 B with a mask) read and 4 B written per voxel and gradient
+            _lib.profiler.meta = {"bytes": ((8.0 if cnt is None else 9.0) + 4.0 * ((da is not None) + (db is not None))) * N * V}
+        if cnt is None:
+            check(lib.kmh_mi_bwd(_p(a), _p(b), _p(rng), _p(G), _p(gout), N, V, ctx.bins, _p(da), _p(db), _stream()), "kmh_mi_bwd")
+        else:
+            check(lib.kmh_mi_bwd_masked(_p(a), _p(b), _p(mask), _p(rng), _p(G), _p(gout), _p(cnt), N, V, ctx.bins, _p(da), _p(db),
+                                        _stream()), "kmh_mi_bwd_masked")
+        return da, db, None, None, None, None, None
 
 
 def _need_mask(who: str, name: str, mask, like: Tensor):
@@ -1238,55 +1255,6 @@ def _need_mask(who: str, name: str, mask, like: Tensor):
         raise ValueError(f"{who}: {name} must have the volumes' shape {tuple(like.shape)}, got {tuple(mask.shape)}")
     mask = mask.detach().contiguous()
     return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-
-
-def _mi_final_masked(ws, rng, cnt, N, bins):
-    """_mi_final with p = h / cnt[n], for the table a masked histogram pass left in ws."""
-    mi = torch.empty((N,), dtype=torch.float32, device=ws.device)
-    G = torch.empty((N, bins, bins), dtype=torch.float32, device=ws.device)
-    check(_lib.load().kmh_mi_final_masked(_p(ws), _p(rng), _p(cnt), N, bins, _p(mi), _p(G), _stream()), "kmh_mi_final_masked")
-    return mi, G
-
-
-class _MIMasked(torch.autograd.Function):
-    """_MI over the counted voxels (mask != 0), ranges given on the device.  The count stays on the device."""
-    @staticmethod
-    def forward(ctx, a, b, bins, rng, mask):
-        lib = _lib.load()
-        N, V = a.shape[0], a.numel() // a.shape[0]
-        ws = torch.empty(max(int(lib.kmh_mi_ws_bytes(N, bins)), 1), dtype=torch.uint8, device=a.device)
-        cnt = torch.empty((N,), dtype=torch.int64, device=a.device)
-        if _lib.profiler.enabled:  # at most 9 B read per voxel
-            _lib.profiler.meta = {"bytes": 9.0 * N * V}
-        check(lib.kmh_mi_hist_masked(_p(a), _p(b), _p(mask), _p(rng), N, V, bins, _p(ws), _p(cnt), _stream()),
-              "kmh_mi_hist_masked")
-        mi, G = _mi_final_masked(ws, rng, cnt, N, bins)
-        ctx.save_for_backward(a, b, rng, G, mask, cnt)
-        ctx.bins = bins
-        ctx.mark_non_differentiable(G)
-        return mi, G
-
-    @staticmethod
-    def backward(ctx, gout, _gG):
-        lib = _lib.load()
-        a, b, rng, G, mask, cnt = ctx.saved_tensors
-        gout = _prep(gout)
-        N, V = a.shape[0], a.numel() // a.shape[0]
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        if _lib.profiler.enabled:
-            _lib.profiler.meta = {"bytes": (9.0 + 4.0 * ((da is not None) + (db is not None))) * N * V}
-        check(lib.kmh_mi_bwd_masked(_p(a), _p(b), _p(mask), _p(rng), _p(G), _p(gout), _p(cnt), N, V, ctx.bins, _p(da), _p(db),
-                                    _stream()), "kmh_mi_bwd_masked")
-        return da, db, None, None, None
-
-
-def _mi_masked(a, b, bins, range_a, range_b, ranges, mask):
-    """(MI (N,), G) of checked inputs over the counted voxels.  The ranges are the caller's, or the whole volumes' own: the range
-    stage of kmh_mi_hist on its own (kmh_mi_range), then the masked histogram with the ranges given."""
-    if ranges is None:
-        ranges = _mi_ranges(a.detach(), b.detach(), bins, range_a, range_b)
-    return _MIMasked.apply(a, b, bins, ranges, mask)
 
 
 def _mi_check(a, b, bins, range_a, range_b):
@@ -1325,25 +1293,17 @@ def mutual_information(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range
         if tuple(ranges.shape) != (a.shape[0], 4):
             raise ValueError(f"mutual_information: ranges must be ({a.shape[0]}, 4) as mi_ranges returns them, got "
                              f"{tuple(ranges.shape)}")
-        if mask is not None:
-            return _mi_masked(a, b, bins, None, None, ranges.detach().contiguous(), mask)[0]
-        return _MI.apply(a, b, bins, None, None, ranges.detach().contiguous())
+        return _MI.apply(a, b, bins, None, None, ranges.detach().contiguous(), mask)
     checked = _mi_check(a, b, bins, range_a, range_b)
-    mask = _need_mask("mutual_information", "mask", mask, a)
-    if mask is not None:
-        return _mi_masked(*checked, None, mask)[0]
-    return _MI.apply(*checked)
+    return _MI.apply(*checked, None, _need_mask("mutual_information", "mask", mask, a))
 
 
 def _mi_table(a: Tensor, b: Tensor, bins: int = 32, range_a=None, range_b=None, ranges=None, mask=None):
     """(MI (N,), G (N, bins, bins)) without autograd: G = ln(p / (pa pb)) where the joint probability p > 0, else 0 -- the table the
     gradient of mutual_information gathers from.  ranges, mask: as mutual_information takes them."""
-    if mask is not None:
-        a, b, bins, range_a, range_b = _mi_check(a.detach(), b.detach(), bins, range_a, range_b)
-        mask = _need_mask("mutual_information", "mask", mask, a)
-        return _mi_masked(a, b, bins, range_a, range_b, None if ranges is None else ranges.detach().contiguous(), mask)
-    mi, _, G = _mi_forward(*_mi_check(a.detach(), b.detach(), bins, range_a, range_b),
-                           None if ranges is None else ranges.detach().contiguous())
+    checked = _mi_check(a.detach(), b.detach(), bins, range_a, range_b)
+    mi, _, G, _ = _mi_forward(*checked, None if ranges is None else ranges.detach().contiguous(),
+                              _need_mask("mutual_information", "mask", mask, checked[0]))
     return mi, G
 
 
@@ -1385,51 +1345,23 @@ def mi_ranges(moving: Tensor, fixed: Tensor, bins: int = 32) -> Tensor:
 
 
 class _WarpMI(torch.autograd.Function):
+    """With a mask or `inside`, over the counted voxels (csrc/warp_mi.hip states which); their count stays on the device."""
     @staticmethod
-    def forward(ctx, moving, fixed, mat, rng, bins):
+    def forward(ctx, moving, fixed, mat, rng, bins, fixed_mask=None, moving_mask=None, inside=False):
         lib = _lib.load()
         N, _, D, H, W = moving.shape
+        masked = fixed_mask is not None or moving_mask is not None or inside
         ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=moving.device)
-        if _lib.profiler.enabled:  # the fixed volume once, the moving volume about once (8 corners, coherent)
-            _lib.profiler.meta = {"bytes": 8.0 * N * D * H * W}
-        check(lib.kmh_warp_mi_hist(_p(moving), _p(fixed), _p(mat), _p(rng), N, D, H, W, bins, _p(ws), _stream()),
-              "kmh_warp_mi_hist")
-        mi, G = _mi_final(ws, rng, N, D * H * W, bins)
-        ctx.save_for_backward(moving, fixed, mat, rng, G)
-        ctx.bins = bins
-        ctx.mark_non_differentiable(G)
-        return mi, G
-
-    @staticmethod
-    def backward(ctx, gout, _gG):
-        if not ctx.needs_input_grad[2]:
-            return None, None, None, None, None
-        lib = _lib.load()
-        moving, fixed, mat, rng, G = ctx.saved_tensors
-        gout = _prep(gout)
-        N, _, D, H, W = moving.shape
-        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, ctx.bins, D, H, W)), dtype=torch.uint8, device=moving.device)
-        dmat = torch.empty_like(mat)
-        if _lib.profiler.enabled:
-            _lib.profiler.meta = {"bytes": 8.0 * N * D * H * W}
-        check(lib.kmh_warp_mi_bwd(_p(moving), _p(fixed), _p(mat), _p(rng), _p(G), _p(gout), N, D, H, W, ctx.bins, _p(ws),
-                                  _p(dmat), _stream()), "kmh_warp_mi_bwd")
-        return None, None, dmat, None, None
-
-
-class _WarpMIMasked(torch.autograd.Function):
-    """_WarpMI over the counted voxels (csrc/warp_mi.hip states which).  The count stays on the device."""
-    @staticmethod
-    def forward(ctx, moving, fixed, mat, rng, bins, fixed_mask, moving_mask, inside):
-        lib = _lib.load()
-        N, _, D, H, W = moving.shape
-        ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, bins, D, H, W)), dtype=torch.uint8, device=moving.device)
-        cnt = torch.empty((N,), dtype=torch.int64, device=moving.device)
-        if _lib.profiler.enabled:
-            _lib.profiler.meta = {"bytes": 10.0 * N * D * H * W}
-        check(lib.kmh_warp_mi_hist_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), N, D, H, W,
-                                          bins, int(inside), _p(ws), _p(cnt), _stream()), "kmh_warp_mi_hist_masked")
-        mi, G = _mi_final_masked(ws, rng, cnt, N, bins)
+        cnt = torch.empty((N,), dtype=torch.int64, device=moving.device) if masked else None
+        if _lib.profiler.enabled:  # the fixed volume once, the moving volume about once (8 corners, coherent); the masks' bytes
+            _lib.profiler.meta = {"bytes": (10.0 if masked else 8.0) * N * D * H * W}
+        if masked:
+            check(lib.kmh_warp_mi_hist_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), N, D, H, W,
+                                              bins, int(inside), _p(ws), _p(cnt), _stream()), "kmh_warp_mi_hist_masked")
+        else:
+            check(lib.kmh_warp_mi_hist(_p(moving), _p(fixed), _p(mat), _p(rng), N, D, H, W, bins, _p(ws), _stream()),
+                  "kmh_warp_mi_hist")
+        mi, G = _mi_final(ws, rng, N, D * H * W, bins, cnt)
         ctx.save_for_backward(moving, fixed, mat, rng, G, cnt, fixed_mask, moving_mask)
         ctx.bins, ctx.inside = bins, int(inside)
         ctx.mark_non_differentiable(G)
@@ -1446,11 +1378,15 @@ class _WarpMIMasked(torch.autograd.Function):
         ws = torch.empty(int(lib.kmh_warp_mi_ws_bytes(N, ctx.bins, D, H, W)), dtype=torch.uint8, device=moving.device)
         dmat = torch.empty_like(mat)
         if _lib.profiler.enabled:
-            _lib.profiler.meta = {"bytes": 10.0 * N * D * H * W}
-        check(lib.kmh_warp_mi_bwd_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), _p(G), _p(gout),
-                                         _p(cnt), N, D, H, W, ctx.bins, ctx.inside, _p(ws), _p(dmat), _stream()),
-              "kmh_warp_mi_bwd_masked")
-        return None, None, dmat, None, None, None, None, None
+            _lib.profiler.meta = {"bytes": (8.0 if cnt is None else 10.0) * N * D * H * W}
+        if cnt is None:
+            check(lib.kmh_warp_mi_bwd(_p(moving), _p(fixed), _p(mat), _p(rng), _p(G), _p(gout), N, D, H, W, ctx.bins, _p(ws),
+                                      _p(dmat), _stream()), "kmh_warp_mi_bwd")
+        else:
+            check(lib.kmh_warp_mi_bwd_masked(_p(moving), _p(fixed), _p(fixed_mask), _p(moving_mask), _p(mat), _p(rng), _p(G),
+                                             _p(gout), _p(cnt), N, D, H, W, ctx.bins, ctx.inside, _p(ws), _p(dmat), _stream()),
+                  "kmh_warp_mi_bwd_masked")
+        return (None, None, dmat) + (None,) * 5
 
 
 def _warp_mi(moving, fixed, mat, bins, ranges, fixed_mask=None, moving_mask=None, inside=False):
@@ -1459,9 +1395,7 @@ def _warp_mi(moving, fixed, mat, bins, ranges, fixed_mask=None, moving_mask=None
     moving_mask = _need_mask("warp_mutual_information", "moving_mask", moving_mask, moving)
     moving, fixed = moving.detach().contiguous(), fixed.detach().contiguous()
     rng = _mi_ranges(moving, fixed, bins) if ranges is None else ranges.detach().contiguous()
-    if fixed_mask is None and moving_mask is None and not inside:
-        return _WarpMI.apply(moving, fixed, mat.contiguous(), rng, bins)
-    return _WarpMIMasked.apply(moving, fixed, mat.contiguous(), rng, bins, fixed_mask, moving_mask, bool(inside))
+    return _WarpMI.apply(moving, fixed, mat.contiguous(), rng, bins, fixed_mask, moving_mask, bool(inside))
 
 
 def warp_mutual_information(moving: Tensor, fixed: Tensor, mat: Tensor, bins: int = 32, ranges: Optional[Tensor] = None,
