@@ -55,8 +55,9 @@ __device__ __forceinline__ float tps_d2(float dz, float dy, float dx) { return f
 // log(r + e), r = sqrt(d2), e = 1e-6, with ONE transcendental instead of two (v_sqrt/v_rsq and v_log are quarter-rate and
 // were 16 of the 24 issue slots per pair of kernel values):  2 log2(r + e) = log2(d2) + 2 log2(1 + e/r), and e/r <= 1e-3
 // (d2 >= 1e-6), so log2(1 + e/r) = (e/r) / ln 2 to 5e-4 of ITSELF.  e/r comes from the integer reciprocal-square-root
-// estimate (two integer instructions, +-3.4 % of e/r, centred by the 0.98636): the whole correction is <= 2e-6/r in
-// natural-log units and its error <= 3.5e-8/r -- under the rounding of r + 1e-6 in fp32 (6e-8 relative) that the
+// estimate (two integer instructions, within 4.8 % of e/r once centred by the 0.98636): the whole correction is <= 2e-6/r in
+// natural-log units and its error on log(r + e) <= 4.8e-8/r (tests/test_grids_reference_cpu.py measures both over the range
+// of d2) -- under the rounding of r + 1e-6 in fp32 (6e-8 relative) that the
 // reference's own operation sequence carries, and the fp64 value of log(sqrt(d2) + 1e-6) is what the tests compare with.
 __device__ __forceinline__ float tps_rsq_est(float d2) { return __uint_as_float(0x5f3759dfu - (__float_as_uint(d2) >> 1)); }
 constexpr float kTpsRsqCentre = 0.98636f;                                    // zero-mean estimate

@@ -8,9 +8,9 @@
 namespace {
 
 // torch.linspace(-1, 1, n)[i] in fp32 (symmetric evaluation: start + i*step below the midpoint,
-// end - (n-1-i)*step above)
+// end - (n-1-i)*step above); an axis of one voxel is its start, -1, as linspace(-1, 1, 1) is
 __device__ __forceinline__ float lin(int i, int n, float step) {
-  return (i < n / 2) ? (-1.f + step * (float)i) : (1.f - step * (float)(n - 1 - i));
+  return (i < n / 2 || n == 1) ? (-1.f + step * (float)i) : (1.f - step * (float)(n - 1 - i));
 }
 __host__ __device__ __forceinline__ float lin_step(int n) { return n > 1 ? 2.f / (float)(n - 1) : 0.f; }
 

@@ -211,7 +211,8 @@ constexpr int VSTAGE = 256;        // voxels staged per LDS refill (one per thre
 constexpr int VCHUNK = 8192;       // voxels per block
 
 // 2 dU/d(d2) = 2 ln(r + eps) + r / (r + eps), from L = 2 log2(r + eps) and the reciprocal-square-root estimate y:
-// r / (r + eps) = 1 / (1 + t) = 1 - t + O(t^2), t = eps / r = 1e-6 * 0.98636 y <= 1e-3 (t^2 <= 1e-6 of a term of size one)
+// r / (r + eps) = 1 / (1 + t) = 1 - t + O(t^2), t = eps / r = 1e-6 * 0.98636 y <= 1e-3 (t^2 <= 1e-6 of a term of size one, and
+// the estimate's 4.8 % of t <= 4.8e-5)
 __device__ __forceinline__ kmh_f2 tps_du2(kmh_f2 L, kmh_f2 y) {
   const kmh_f2 ln2 = {0.6931471805599453f, 0.6931471805599453f}, one = {1.f, 1.f};
   const kmh_f2 mt = {-1.0e-6f * kTpsRsqCentre, -1.0e-6f * kTpsRsqCentre};

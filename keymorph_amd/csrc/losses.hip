@@ -114,11 +114,12 @@ __global__ __launch_bounds__(TPB) void argmax_onehot_kernel(const float* __restr
   const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
   if (i >= V) return;
   const float* p = pred + (long long)n * C * V + i;
+  // torch.argmax's rule: the first NaN if there is one, otherwise the first maximum
   float best = p[0];
   int bi = 0;
   for (int c = 1; c < C; ++c) {
     float v = p[(long long)c * V];
-    if (v > best) { best = v; bi = c; }
+    if (v > best || (v != v && best == best)) { best = v; bi = c; }
   }
   float* o = out + (long long)n * C * V + i;
   for (int c = 0; c < C; ++c) o[(long long)c * V] = (c == bi) ? 1.f : 0.f;

@@ -625,6 +625,8 @@ def warp_dice_rows(x: Tensor, grid: Tensor, fixed: Tensor) -> Tensor:
 
 
 def argmax_onehot(pred: Tensor) -> Tensor:
+    """(N, C, V) -> the one-hot of torch.argmax over the channels, float32: the first NaN if a voxel has one (in whichever
+    channel), otherwise the first maximum (+0 == -0)."""
     lib = _lib.load()
     pred = _prep(pred)
     N, C, V = pred.shape

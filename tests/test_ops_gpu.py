@@ -294,8 +294,10 @@ def test_affine_grid(shape):
     close(Mh.grad, Mr.grad, 1e-3, 1e-4)
 
 
-# (the last two shapes take the row-hoisted evaluators with the weighted sums on the 4x4x1 MFMA: whole 1024-voxel blocks and
-# W % 4 == 0 forward, W % 256 == 0 backward; T = 130 leaves idle keypoint lanes in the backward's MFMA blocks)
+# (forward arms: W % 8 == 0 -- 8 voxels per lane, the row's (z, y) part of the squared distance hoisted -- at W = 8, 16, 256, and the
+# plain 4-voxel arm at W = 9; W % 4 == 0 with W % 8 != 0 is run by tests/test_grids_edges_gpu.py.  Backward: the row-hoisted arm at
+# W % 256 == 0 (the last two shapes), the plain one elsewhere; packed-fp32 VALU throughout, no MFMA; T = 130 leaves idle keypoint
+# lanes in the backward's 512-keypoint tile)
 @pytest.mark.parametrize("T_,shape", [(16, (6, 7, 8)), (64, (12, 10, 9)), (130, (8, 8, 8)), (64, (8, 16, 16)), (130, (2, 4, 256)),
                                       (512, (4, 8, 256))])
 def test_tps_grid_given_theta(T_, shape):
