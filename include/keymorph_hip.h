@@ -640,6 +640,23 @@ size_t kmh_svf_square_bwd_ws_bytes(int N, int D, int H, int W);
 int kmh_svf_square_bwd(const float* u, const float* g, float* du, const unsigned* amax_in, unsigned* amax_out, int N, int D, int H,
                        int W, void* ws, void* stream);
 
+/* ---- dense displacement fields as a transform model (csrc/dense.hip states the definitions) ---- */
+/* disp, delta, ddisp, out: PLANAR (N,3,D,H,W) float32 contiguous, channels (z, y, x), voxels of their own lattice
+ * (kmh_field_to_displacement's convention); grid, dgrid (N,D,H,W,3); N in [1, 65535] and D*H*W*3 < 2^30, else -22 before anything is
+ * launched.
+ * kmh_disp_grid_fwd: grid = Ids + u, u = disp over S / 2 per axis in xyz (mat NULL: bit-identical to kmh_field_from_displacement),
+ *   else kmh_affine_grid_fwd's grid + L (s * u) as kmh_svf_finish_fwd (every axis >= 2).  kmh_disp_grid_bwd: its transpose in disp.
+ * kmh_disp_step_scale: out[n] = step / max_w |delta[n, :, w]|_2 over the voxels whose squared norm is finite, 0 where that maximum
+ *   is 0; an integer max on float bits, so runs repeat bit for bit and a batch equals its samples.  Nothing is read back.
+ * kmh_disp_update: out[n, :, w] = d[w] + U_n(Ids[w] + d[w] over S / 2), d = delta * scale[n] (scale (N) in device memory, or NULL:
+ *   delta), U_n the border-clamped trilinear interpolant of disp[n] (the sampler's coordinate, clamp and NaN rule); every product
+ *   and sum rounded on its own.  out must not be disp. */
+int kmh_disp_grid_fwd(const float* disp, const float* mat, float* grid, int N, int D, int H, int W, void* stream);
+int kmh_disp_grid_bwd(const float* dgrid, const float* mat, float* ddisp, int N, int D, int H, int W, void* stream);
+int kmh_disp_step_scale(const float* delta, float step, float* out, int N, int D, int H, int W, void* stream);
+int kmh_disp_update(const float* disp, const float* delta, const float* scale, float* out, int N, int D, int H, int W,
+                    void* stream);
+
 /* ---- local normalised cross-correlation (csrc/lncc.hip states the definition) ---- */
 /* a, b: (N, D, H, W) float32 contiguous, fewer than 2^31 voxels per sample; window odd in [3, 15], truncated at the border.
  * out[n] = mean over the voxels of cross^2 / (va vb + eps) of the window sums.  kmh_lncc_bwd: da = gout[n] d out[n] / da, db

@@ -185,6 +185,10 @@ PROTOS = {
     "kmh_svf_finish_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "kmh_svf_square_bwd_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "kmh_svf_square_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f]),
+    "kmh_disp_grid_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_disp_grid_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f]),
+    "kmh_disp_step_scale": (_i, [_f, C.c_float, _f, _i, _i, _i, _i, _f]),
+    "kmh_disp_update": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "kmh_lncc_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kmh_lncc_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f]),
     "kmh_lncc_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, C.c_float, _f, _f, _f, _f]),

@@ -11,3 +11,4 @@ from .intensity import (apply_mat, estimate_affine, estimate_rigid, mat_to_voxel
                         rigid_params_to_voxel, rotation_matrix, voxel_to_mat)
 from .bspline import apply_bspline, register_bspline         # noqa: F401
 from .svf import apply_svf, register_svf, svf_grid         # noqa: F401
+from .greedy import apply_greedy, register_greedy         # noqa: F401

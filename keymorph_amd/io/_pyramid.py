@@ -1,6 +1,6 @@
 """What the multi-resolution drivers share (io.estimate_translation, io.register_intensity, and io.register_bspline and
-io.register_svf through io/_deformable.py's fit_lattice): the levels of the trilinear pyramid, and how parameters are carried
-between them."""
+io.register_svf through io/_deformable.py's fit_lattice, io.register_greedy): the levels of the trilinear pyramid, and how parameters
+are carried between them."""
 import torch
 
 MIN_AXIS = 16      # a level with a shorter axis is skipped
@@ -43,12 +43,17 @@ def resolve_smoothing(who, shrink, smoothing):
     return tuple(out)
 
 
+def level_entries(dims, shrink, entries):
+    """Of one entry per entry of `shrink`, those of the levels level_dims(dims, shrink) keeps (a dropped level drops its entry)."""
+    return [e for sh, e in zip(shrink, entries) if min(int(n) // int(sh) for n in dims) >= MIN_AXIS]
+
+
 def level_smoothing(who, dims, shrink, smoothing):
     """resolve_smoothing's entries for the levels level_dims(dims, shrink) keeps (a dropped level drops its entry); None: None."""
     sig = resolve_smoothing(who, shrink, smoothing)
     if sig is None:
         return None
-    return [s for sh, s in zip(shrink, sig) if min(int(n) // int(sh) for n in dims) >= MIN_AXIS]
+    return level_entries(dims, shrink, sig)
 
 
 def levels(fixed, moving, shrink, smoothing=None, who="levels"):

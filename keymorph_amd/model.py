@@ -376,14 +376,18 @@ class IntensityRegistration(nn.Module):
     as velocities and exponentiated in svf_steps squarings) on top of the affine answer; its entry is the "bspline" one with
     "grid" = ops.svf_grid(ctrl, dims, svf_steps, matrix) and, in addition, "inverse_grid" = io.svf_grid(ctrl, dims, matrix,
     svf_steps, inverse=True), the grid that resamples a fixed-space volume into moving space.
+    "greedy": the dense displacement field of io.register_greedy (greedy_step voxels per iteration, greedy_sigmas = (sigma_update,
+    sigma_total), greedy_iters per level; the same metric arguments) on top of the affine answer; its entry has "disp"
+    (N, 3, D, H, W) instead of "ctrl", "grid" = ops.displacement_grid(disp, matrix) and "inverse_grid" = fields.invert(grid).
     smoothing_sigmas (constructor): None, "auto" or one Gaussian sigma per level of the pyramid the call builds (ValueError
     otherwise), handed to every driver: each level is smoothed at the full size before it is resized (io.estimate_translation
     says why)."""
 
-    supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf")
+    supported_transform_type = ("translation", "rigid", "affine", "bspline", "svf", "greedy")
 
     def __init__(self, bins=32, iters=30, lr=0.25, control_spacing=8, bending=0.05, bspline_iters=60, bspline_lr=0.1,
-                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2, inside=False, smoothing_sigmas=None):
+                 metric="mi", window=9, svf_steps=6, mind_radius=1, mind_dilation=2, inside=False, smoothing_sigmas=None,
+                 greedy_step=0.5, greedy_sigmas=(3 ** 0.5, 0.5 ** 0.5), greedy_iters=60):
         super().__init__()
         from .io._deformable import metric_table
         metric_table("IntensityRegistration", metric)                          # refuses an unknown name
@@ -391,6 +395,13 @@ class IntensityRegistration(nn.Module):
         self.metric, self.window = metric, window
         self.control_spacing, self.bending, self.bspline_iters, self.bspline_lr = control_spacing, bending, bspline_iters, bspline_lr
         self.svf_steps = svf_steps
+        try:
+            self.greedy_sigmas = tuple(greedy_sigmas)
+        except TypeError:
+            self.greedy_sigmas = ()
+        if len(self.greedy_sigmas) != 2:
+            raise ValueError(f"IntensityRegistration: greedy_sigmas must be (sigma_update, sigma_total), got {greedy_sigmas!r}")
+        self.greedy_step, self.greedy_iters = greedy_step, greedy_iters
         self.mind_radius, self.mind_dilation = mind_radius, mind_dilation
         self.inside = bool(inside)
         if smoothing_sigmas is not None and not isinstance(smoothing_sigmas, str):
@@ -403,10 +414,11 @@ class IntensityRegistration(nn.Module):
 
     def forward(self, img_f, img_m, transform_type="affine", num_resolutions_for_itkelastix=None, mask_f=None, mask_m=None,
                 **kwargs):
-        from . import ops
+        from . import fields, ops
         from .io._deformable import counted_voxels, metric_table
         from .io._pyramid import resolve_smoothing
         from .io.bspline import register_bspline
+        from .io.greedy import register_greedy
         from .io.intensity import register_intensity
         from .io.svf import register_svf, svf_grid
         from .utils import align_img
@@ -433,9 +445,23 @@ class IntensityRegistration(nn.Module):
         for align_type_str in transform_type:
             start_time = time.time()
             deformable = lattices.get(align_type_str)
-            mat = register_intensity(img_f, img_m, "affine" if deformable else align_type_str, bins=self.bins, shrink=shrink,
-                                     iters=self.iters, lr=self.lr, **masks, **smooth)
-            if deformable:
+            dense = align_type_str == "greedy"
+            mat = register_intensity(img_f, img_m, "affine" if deformable or dense else align_type_str, bins=self.bins,
+                                     shrink=shrink, iters=self.iters, lr=self.lr, **masks, **smooth)
+            if dense:
+                disp = register_greedy(img_f, img_m, mat, step=self.greedy_step, sigma_update=self.greedy_sigmas[0],
+                                       sigma_total=self.greedy_sigmas[1], shrink=shrink, iters=self.greedy_iters, bins=self.bins,
+                                       metric=self.metric, window=self.window, mind_radius=self.mind_radius,
+                                       mind_dilation=self.mind_dilation, **masks, **smooth)
+                with torch.no_grad():
+                    grid = ops.displacement_grid(disp, mat)
+                    warped = align_img(grid, img_m)
+                    counted = counted_voxels(grid, mask_f, mask_m, self.inside) if masked else None
+                    res = {"grid": grid, "inverse_grid": fields.invert(grid), "matrix": mat, "disp": disp,
+                           "mi": ops.mutual_information(warped, img_f, self.bins, mask=counted)}
+                    if reported:
+                        res[self.metric] = reported(warped, img_f, img_m)
+            elif deformable:
                 driver, grid_of, inverse_of = deformable
                 ctrl = driver(img_f, img_m, mat, control_spacing=self.control_spacing, bending=self.bending, bins=self.bins,
                               shrink=shrink, iters=self.bspline_iters, lr=self.bspline_lr, metric=self.metric, window=self.window,

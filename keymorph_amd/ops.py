@@ -911,6 +911,113 @@ def svf_compose(u: Tensor, first: Tensor, add: Optional[Tensor] = None) -> Tenso
     return out
 
 
+# --------------------------------------------------------------------------
+# dense displacement fields as a transform model: the grid of a planar voxel displacement, its step scale and the greedy
+# composition (csrc/dense.hip)
+# --------------------------------------------------------------------------
+def _disp_check(who, name, t, like=None):
+    """t: a non-empty float32 (N, 3, D, H, W) field on the GPU with D * H * W * 3 < 2^30 (and of like's shape), or an error."""
+    _need_gpu_f32(who, name, t)
+    if t.dim() != 5 or t.shape[1] != 3 or t.numel() == 0:
+        raise ValueError(f"{who}: {name} must be a non-empty displacement field (N, 3, D, H, W), got {tuple(t.shape)}")
+    if t.shape[2] * t.shape[3] * t.shape[4] * 3 >= 1 << 30 or t.shape[0] > 65535:
+        raise ValueError(f"{who}: {name} needs D * H * W * 3 < 2^30 and N <= 65535, got {tuple(t.shape)}")
+    if like is not None and t.shape != like.shape:
+        raise ValueError(f"{who}: {name} must have the field's shape {tuple(like.shape)}, got {tuple(t.shape)}")
+
+
+class _DisplacementGrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, disp, mat):
+        N, _, D, H, W = disp.shape
+        ctx.mat = mat
+        grid = torch.empty((N, D, H, W, 3), dtype=torch.float32, device=disp.device)
+        if _lib.profiler.enabled:  # 12 B read + 12 B written per voxel
+            _lib.profiler.meta = {"bytes": 24.0 * N * D * H * W}
+        check(_lib.load().kmh_disp_grid_fwd(_p(disp), _p(mat), _p(grid), N, D, H, W, _stream()), "kmh_disp_grid_fwd")
+        return grid
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _prep(g)
+        N, D, H, W, _ = g.shape
+        ddisp = torch.empty((N, 3, D, H, W), dtype=torch.float32, device=g.device)
+        if _lib.profiler.enabled:
+            _lib.profiler.meta = {"bytes": 24.0 * N * D * H * W}
+        check(_lib.load().kmh_disp_grid_bwd(_p(g), _p(ctx.mat), _p(ddisp), N, D, H, W, _stream()), "kmh_disp_grid_bwd")
+        return ddisp, None
+
+
+def displacement_grid(disp: Tensor, mat: Optional[Tensor] = None) -> Tensor:
+    """The sampling grid (N, D, H, W, 3) of a dense displacement field: disp (N, 3, D, H, W) float32 on the current GPU, channels
+    (z, y, x), in voxels of its own lattice (fields.to_displacement's convention), planar so that gaussian_smooth works on it as it
+    is.  With u = disp over S / 2 per axis, reordered to xyz:
+        grid = Ids + u   (mat None: fields.from_displacement(disp), bit for bit)
+        grid = ops.affine_grid(mat, (D, H, W)) + L (s * u),  L = mat[:, :, :3], s = S / (S - 1) per axis   (svf_grid's rule)
+    -- the matrix applied to the deformed point.  Differentiable in disp only (mat is data: one that requires grad raises); the
+    backward is the per-voxel transpose, a direct planar write without atomics, so runs repeat bit for bit and a batch equals its
+    samples.  D * H * W * 3 < 2^30; with a matrix every axis needs two voxels."""
+    who = "displacement_grid"
+    _disp_check(who, "disp", disp)
+    if mat is not None:
+        _need_gpu(who, "mat", mat)
+        if mat.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who}: mat requires grad, and {who} is differentiable in disp only: pass mat.detach()")
+        if mat.dtype != torch.float32 or tuple(mat.shape) != (disp.shape[0], 3, 4):
+            raise ValueError(f"{who}: mat must be float32 ({disp.shape[0]}, 3, 4), got {mat.dtype} {tuple(mat.shape)}")
+        if min(disp.shape[2:]) < 2:
+            raise ValueError(f"{who}: with a matrix every axis needs at least two voxels, got {tuple(disp.shape[2:])}")
+        mat = mat.detach().contiguous()
+    return _DisplacementGrid.apply(disp.contiguous(), mat)
+
+
+def displacement_step_scale(delta: Tensor, step: float) -> Tensor:
+    """(N,) float32 on the device: step / max_w |delta[n, :, w]|_2 of an update field delta (N, 3, D, H, W) -- the factor that makes
+    its longest vector `step` voxels long.  0 where that maximum is 0.  A voxel whose squared norm is not finite (a NaN, an Inf, an
+    overflow) does not enter the maximum.  The maximum is an integer max on float bits: runs repeat bit for bit and a batch equals
+    its samples.  Nothing is read back to the host.  Not differentiable."""
+    who = "displacement_step_scale"
+    _disp_check(who, "delta", delta)
+    step = float(step)
+    if not math.isfinite(step):
+        raise ValueError(f"{who}: step must be finite, got {step!r}")
+    delta = delta.detach().contiguous()
+    N, _, D, H, W = delta.shape
+    out = torch.empty((N,), dtype=torch.float32, device=delta.device)
+    if _lib.profiler.enabled:
+        _lib.profiler.meta = {"bytes": 12.0 * N * D * H * W}
+    check(_lib.load().kmh_disp_step_scale(_p(delta), step, _p(out), N, D, H, W, _stream()), "kmh_disp_step_scale")
+    return out
+
+
+def displacement_update(disp: Tensor, delta: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+    """The greedy composition phi <- phi o (Id + d) on displacement fields (N, 3, D, H, W), d = delta * scale[n] (scale (N,) float32
+    on the device, read inside the kernel; None: delta itself):
+        out[n, :, w] = d[w] + U_n(w + d[w])
+    U_n the trilinear interpolant of disp[n] with border clamping, at the sampler's own coordinate of the grid
+    fields.from_displacement(d): the result is d + align_img(fields.from_displacement(d), disp), bit for bit, in one kernel.
+    Every product and sum is a separately rounded fp32 operation in the order written.  Not differentiable: an input that requires
+    grad raises."""
+    who = "displacement_update"
+    _disp_check(who, "disp", disp)
+    _disp_check(who, "delta", delta, disp)
+    if scale is not None:
+        _need_gpu_f32(who, "scale", scale)
+        if tuple(scale.shape) != (disp.shape[0],):
+            raise ValueError(f"{who}: scale must be ({disp.shape[0]},), got {tuple(scale.shape)}")
+    for name, t in (("disp", disp), ("delta", delta), ("scale", scale)):
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who}: {name} requires grad, and {who} is not differentiable: pass {name}.detach()")
+    disp, delta = disp.detach().contiguous(), delta.detach().contiguous()
+    scale = None if scale is None else scale.detach().contiguous()
+    N, _, D, H, W = disp.shape
+    out = torch.empty_like(disp)
+    if _lib.profiler.enabled:  # 12 B read + 12 B written per voxel, the gathers from cache
+        _lib.profiler.meta = {"bytes": 24.0 * N * D * H * W}
+    check(_lib.load().kmh_disp_update(_p(disp), _p(delta), _p(scale), _p(out), N, D, H, W, _stream()), "kmh_disp_update")
+    return out
+
+
 class _TpsPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, ctrl, pts):
